@@ -7,6 +7,7 @@ A "step" = one pass of the hot path over one batch: policy act (random-init 348-
 All inputs are HBM-resident; the 24-step rollout is replayed as one hipGraph when capture succeeds.
 
     python bench.py --gpus 1 --steps 2400 --warmup 1000
+    python bench.py --gpus 1 --steps 2400 --warmup 1000 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
@@ -81,6 +82,32 @@ def cpu_baseline(task: str, num_envs: int, budget_s: float = 12.0) -> dict:
             "sample": f"{steps} steps x {num_envs} envs of the same task, 0.5*N(0,1) actions, OpenMP over envs, {el:.1f} s"}
 
 
+DUMP_BUDGET_BYTES = 64_000_000 - 9 * 4096  # 64 MB for the nine files, room left for their .npy headers
+
+
+def dump_outputs(out_dir: str, env, storage, t: int) -> dict:
+    """What rollout step t (storage slot t) handed its caller, as float32 .npy files: the policy's sample and the values it
+    stored, the bootstrapped reward and dones, and the observation rows the step left for the next one.  Arrays are per env;
+    when they exceed DUMP_BUDGET_BYTES together, the same seeded sample of env rows (sorted) is kept in every file."""
+    import numpy as np
+
+    arrays = {"actions": storage.actions[t], "action_mean": storage.mu[t], "action_std": storage.sigma[t],
+              "values": storage.values[t], "actions_log_prob": storage.actions_log_prob[t], "rewards": storage.rewards[t],
+              "dones": storage.dones[t], "obs": env.obs_policy, "critic_obs": env.obs_critic}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = env.num_envs
+    total = sum(a.nbytes for a in arrays.values())
+    rows = None
+    if total > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, n * DUMP_BUDGET_BYTES // total, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": out_dir, "storage_slot": t, "envs": n, "env_rows": "all" if rows is None else f"{len(rows)} seeded (numpy default_rng(0))",
+            "bytes": sum(a.nbytes for a in arrays.values())}
+
+
 def _spawn_ranks(args, script: str | None = None, argv: list | None = None) -> int:
     """`python bench.py --gpus N` typed plainly (no torchrun): this parent starts N rank processes of the same script -
     one per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in their environment - BEFORE touching torch or the GPU itself
@@ -124,7 +151,11 @@ def main() -> None:
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager-torch", action="store_true", help="reference-shaped rollout (torch elementwise ops) instead of the fused kernels")
     ap.add_argument("--update-iters", type=int, default=3, help="PPO iterations timed for train_total_fps (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_spawn_ranks(args))
@@ -216,6 +247,9 @@ def main() -> None:
     dist.all_reduce_max_(elapsed)
     elapsed = float(elapsed)
     value = n * args.gpus * args.steps / elapsed
+    dumped = None
+    if args.dump_outputs and dist.rank == 0:  # before the roofline probe below moves the env on
+        dumped = dump_outputs(args.dump_outputs, env, alg.storage, (args.steps - 1) % ROLLOUT)
 
     # ---- roofline of the dominant kernel: live HIP-event timing of lt_step_kernel on the launch stream ----
     with torch.inference_mode():
@@ -348,6 +382,8 @@ def main() -> None:
                           "fused_rollout": fused is not None, "launches_per_step": fused.launches_per_step if fused is not None else None},
                "roofline": roofline, "cpu_baseline": cpu}
         out.update(extra)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out))
     dist.shutdown()
 
