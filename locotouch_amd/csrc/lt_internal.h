@@ -40,3 +40,9 @@ int lt_launch_check(const lt_env* env, void* stream, long long* count);
 const char* lt_hip_error_string(int err);
 
 void lt_set_error(const char* msg);
+
+// implemented in lt_mlp.hip -------------------------------------------------------------------------
+// Allows `kernel` `bytes` of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize) on the current device: the attribute is set
+// at the first call per (kernel, device) and remembered once it is set (thread-safe; one size per kernel).  Returns a hipError_t
+// value as int.
+int lt_ensure_dynamic_lds(const void* kernel, int bytes);

@@ -54,7 +54,9 @@
 // storage-slot writes), so the actor side of a rollout step needs no further launch.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
+#include <mutex>
+#include <set>
+#include <utility>
 
 #include "lt_device_math.h"
 #include "lt_internal.h"
@@ -66,17 +68,9 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-#ifndef LT_MLP_WAVES
-#define LT_MLP_WAVES 8
-#endif
-constexpr int NW = LT_MLP_WAVES;       // waves per workgroup (two per SIMD)
-#ifndef LT_MLP_MIN_WAVES_PER_SIMD
-#define LT_MLP_MIN_WAVES_PER_SIMD (LT_MLP_WAVES / 4)  // register budget: 512 / this per wave (probe builds: four waves at 2 = two workgroups per CU)
-#endif
-#ifndef LT_MLP_RING_GRAIN
-#define LT_MLP_RING_GRAIN (LT_MLP_WAVES > 4 ? 16 : 32)
-#endif
-constexpr int RING = LT_MLP_RING_GRAIN;  // chunk granularity of the packed streams (layers are padded to multiples of it) = the largest ring
+constexpr int NW = 8;  // waves per workgroup (two per SIMD; two four-wave workgroups per CU measured no faster: DESIGN §4)
+constexpr int MIN_WAVES_PER_SIMD = NW / 4;  // register budget: 512 / this per wave
+constexpr int RING = 16;  // chunk granularity of the packed streams (layers are padded to multiples of it) = the largest ring
 constexpr unsigned RS_POLICY = 0x400;  // same Philox stream id as lt_rollout_act
 constexpr int MODE_FORWARD = 0, MODE_POLICY = 1, MODE_BACKWARD = 2;
 constexpr int KIND_GATE = 100;  // the backward chain's "activation": multiply by ELU'(a) of the forward activation a (lt_mlp_backward_pair)
@@ -92,10 +86,7 @@ __host__ __device__ inline int pad32(int x) { return (x + 31) & ~31; }
 // NW waves.  Not below MIN_TILES = 2: a narrow last layer (12 actions = one tile) then runs through the loop code the layer
 // before it has just pulled into the instruction cache, instead of through a one-tile instantiation fetched cold (the
 // second tile is zero weights; 8 KB more in one wave's stream).
-#ifndef LT_MLP_MIN_TILES
-#define LT_MLP_MIN_TILES 2
-#endif
-constexpr int MIN_TILES = LT_MLP_MIN_TILES;
+constexpr int MIN_TILES = 2;
 __host__ __device__ inline int tiles_per_wave(int ntiles) {
   const int per = (ntiles + NW - 1) / NW;
   const int t = per > 4 ? 8 : (per > 2 ? 4 : (per > 1 ? 2 : 1));
@@ -124,18 +115,6 @@ __host__ __device__ inline Plan plan_of(const int* dims, int L, int l, bool with
   p.G = pad32(K) / 32;
   int widest = 0;
   for (int i = 0; i <= L; ++i) widest = dims[i] > widest ? dims[i] : widest;
-#ifndef LT_MLP_WIDE_KSPLIT
-#define LT_MLP_WIDE_KSPLIT 0
-#endif
-  // A hidden layer of exactly two tiles per wave (256 outputs at eight waves) dealt as FOUR tiles to half of the waves, the k-groups
-  // split between the halves: every wave then reads half of the activation image for twice the tiles - the layer's LDS traffic halves
-  // (at four row tiles each wave of such a layer reads the whole 64 x 512 image for 2 tiles: 170 B/clk asked of a 128 B/clk LDS).
-  // MEASURED (probe build -DLT_MLP_WIDE_KSPLIT=1, r04): policy launch 175.8 against 176.0 us at 32768 envs, 29.8 against 29.3 us at
-  // 4096 - the layer is not bound by its LDS reads; left off.
-  if (LT_MLP_WIDE_KSPLIT && l < L - 1 && p.T == 2 && p.nact == NW && p.G >= 2 && (p.G & 1) == 0 && 2 * pad32(N) <= pad32(widest)) {
-    p.T = 4;
-    p.nact = NW / 2;
-  }
   p.ks = (l < L - 1 && 2 * p.nact <= NW && p.G >= 2 && (p.G & 1) == 0 && 2 * pad32(N) <= pad32(widest)) ? 2 : 1;
   p.Gl = p.G / p.ks;
   p.waves = p.nact * p.ks;
@@ -504,13 +483,9 @@ __device__ __forceinline__ float gate_pass(const MlpArgs& a, int l, float* s_act
       const unsigned r = gpr == 1u ? (unsigned)idx : __umulhi((unsigned)idx, magic), j = (unsigned)idx - r * gpr;  // (gpr == 1: the reciprocal wraps to 0)
       row[u] = (int)r;
       at[u] = (int)r * S + 8 * (int)j;
-#ifdef LT_GATE_NO_LOAD  // probe builds (tools/mlp_backward_probe.py)
-      gt[u][0] = gt[u][1] = f32x4{1.f, 1.f, 1.f, 1.f};
-#else
       const float* const gp = gate + (row0 + min((int)r, rmax)) * N + 8 * j;
       gt[u][0] = __builtin_nontemporal_load((const f32x4*)gp);
       gt[u][1] = __builtin_nontemporal_load((const f32x4*)(gp + 4));
-#endif
     }
   }
 #pragma unroll
@@ -546,11 +521,7 @@ __device__ __forceinline__ float gate_pass(const MlpArgs& a, int l, float* s_act
       *(f16x4*)g = hi[0]; *((f16x4*)g + 1) = hi[1];
       *((f16x4*)g + 2) = lo[0]; *((f16x4*)g + 3) = lo[1];
     }
-#ifdef LT_GATE_NO_STORE
-    if (live && x[0][0] == 123.456f) {
-#else
     if (live) {
-#endif
       float* const o = dst + (row0 + row[u]) * N + (at[u] - row[u] * S);
       if (a.dz_split) {  // (uniform) the halves the next chain layer multiplies, as they are - scaled: lt_wgrad divides its sums
         *(u32x4*)o = interleave4(hi[0], lo[0]);
@@ -597,7 +568,7 @@ __device__ __forceinline__ void policy_noise(const MlpArgs& a, long long row0, i
 // One layer for this wave.  `ring` slot s holds chunk c0 + s of the wave's stream; the layer consumes its items in order
 // (item i = k-group i: T x (hi chunk, lo chunk)) and leaves the ring positioned on the next layer's first chunk.
 // RT row tiles (16 rows each) share every weight chunk: RT x the MFMA work per byte streamed from L2.
-// RG = ring slots (chunks in flight per wave): 32, or 16 where the accumulators need the registers (RG divides RING, so a
+// RG = ring slots (chunks in flight per wave): 16, or 8 where the accumulators need the registers (RG divides RING, so a
 // ring round never straddles a layer).
 template <int T, int RT, int RG, int KIND>
 __device__ __forceinline__ void mlp_layer(const MlpArgs& a, int l, bool last, float* s_act, const float* s_bias, const float* s_noise, int wave, int lane,
@@ -624,23 +595,11 @@ __device__ __forceinline__ void mlp_layer(const MlpArgs& a, int l, bool last, fl
     for (int t = 0; t < T; ++t) am[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (active) {
     // software pipeline over items: the (hi, lo) fragments of item i+1 in flight from LDS while item i is in the MFMAs
-#ifndef LT_MLP_SINGLE_FRAG
-#define LT_MLP_SINGLE_FRAG 0
-#endif
-    // SF (four row tiles): ONE fragment set, fetched at the item's start instead of one item ahead - the 32 registers of the second
-    // set pay for a second ring round (16 slots: two items of the widest layer in flight instead of one; with 8 slots every item of a
-    // wide layer waits out an L2 round trip: 11 items x ~1.3 us = the 13.8 us of the first layer).  The LDS latency this exposes (~0.2
-    // us per item) hides behind the SIMD's other wave and the MFMAs still executing.  MEASURED (probe build -DLT_MLP_SINGLE_FRAG=1
-    // -DLT_MLP_RING4=16: 241 VGPRs, no scratch): policy launch 174 against 172 us at 32768 envs, training forward 154.6 against 156.0 us -
-    // the deeper ring buys nothing at four row tiles either; left off.
-    constexpr bool SF = RT >= 4 && LT_MLP_SINGLE_FRAG != 0;
-    f16x8 xh[SF ? 1 : 2][RT], xl[SF ? 1 : 2][RT];
-    if (!SF) {
+    f16x8 xh[2][RT], xl[2][RT];
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) {
-        xh[0][rt] = *(const f16x8*)(xrow + 16 * rt * S);
-        xl[0][rt] = *(const f16x8*)(xrow + 16 * rt * S + 4);
-      }
+    for (int rt = 0; rt < RT; ++rt) {
+      xh[0][rt] = *(const f16x8*)(xrow + 16 * rt * S);
+      xl[0][rt] = *(const f16x8*)(xrow + 16 * rt * S + 4);
     }
     // items incl. the zero-weight pad items of the last RING round: they are walked (refill only) to leave the ring on the
     // next layer's first chunk - except behind the last layer, where nothing follows
@@ -652,17 +611,17 @@ __device__ __forceinline__ void mlp_layer(const MlpArgs& a, int l, bool last, fl
         const int sl = (j % R) * C;  // first ring slot of the item
         if (i < G) {
           // fetch item i+1's fragments (the last item re-reads itself)
-          const int gx = SF ? i : (i + 1 < G ? i + 1 : G - 1);
+          const int gx = i + 1 < G ? i + 1 : G - 1;
 #pragma unroll
           for (int rt = 0; rt < RT; ++rt) {
-            xh[SF ? 0 : ((j & 1) ^ 1)][rt] = *(const f16x8*)(xrow + 16 * rt * S + 32 * gx);
-            xl[SF ? 0 : ((j & 1) ^ 1)][rt] = *(const f16x8*)(xrow + 16 * rt * S + 32 * gx + 4);
+            xh[(j & 1) ^ 1][rt] = *(const f16x8*)(xrow + 16 * rt * S + 32 * gx);
+            xl[(j & 1) ^ 1][rt] = *(const f16x8*)(xrow + 16 * rt * S + 32 * gx + 4);
           }
           // the three products of the split, all into the one accumulator (product-major order - two MFMAs on the same
           // accumulator T x RT apart instead of T - measured the same within noise)
 #pragma unroll
           for (int rt = 0; rt < RT; ++rt) {
-            const f16x8 bh = xh[SF ? 0 : (j & 1)][rt], bl = xl[SF ? 0 : (j & 1)][rt];
+            const f16x8 bh = xh[j & 1][rt], bl = xl[j & 1][rt];
             const f16x8 bs1 = bh * (_Float16)LO_SCALE;  // exact: |x| <= F16_CLAMP
 #pragma unroll
             for (int t = 0; t < T; ++t) am[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ring[sl + 2 * t]), bs1, am[rt][t], 0, 0, 0);
@@ -750,7 +709,7 @@ __device__ __forceinline__ void mlp_layer(const MlpArgs& a, int l, bool last, fl
 // the bias and weight-ring requests behind them left ~3 us late.
 constexpr int IN_ANY = 0, IN_F32X4 = 1, IN_BF16X4 = 2, IN_F32X2 = 3;
 template <int RT, int KIND, int IN>
-__global__ __launch_bounds__(64 * NW, LT_MLP_MIN_WAVES_PER_SIMD) void lt_mlp_kernel(const DualArgs d) {
+__global__ __launch_bounds__(64 * NW, MIN_WAVES_PER_SIMD) void lt_mlp_kernel(const DualArgs d) {
   extern __shared__ __attribute__((aligned(16))) float s_img[];
   constexpr int ROWS = 16 * RT;
   bool second;
@@ -842,16 +801,9 @@ __global__ __launch_bounds__(64 * NW, LT_MLP_MIN_WAVES_PER_SIMD) void lt_mlp_ker
   // weight stream: a full ring in flight.  Two waves per SIMD leave a wave 256 registers: accumulators (16 RT at the widest
   // layer), fragments (16 RT) and a 16-slot ring (64) fit without scratch at two row tiles (a scratch reload in a layer
   // epilogue would sit behind the whole ring in the queue); four row tiles spill 88 bytes.
-#ifndef LT_MLP_RING2
-#define LT_MLP_RING2 16  // ring slots at two row tiles (32 at eight waves: 352 B of scratch)
-#endif
-#ifndef LT_MLP_RING4
-#define LT_MLP_RING4 8   // ring slots at four row tiles: one item of the widest layer - 16 slots spill 72 bytes and measured slower (177 against 171 us at 32768 envs: the launch is not stream-bound there)
-#endif
-#ifndef LT_MLP_RING1
-#define LT_MLP_RING1 (LT_MLP_WAVES > 4 ? 16 : 32)  // ring slots at one row tile
-#endif
-  constexpr int RG = RT >= 4 ? LT_MLP_RING4 : (RT >= 2 ? LT_MLP_RING2 : LT_MLP_RING1);  // (two waves per SIMD: 256 registers each)
+  // Ring slots: 16 at one and two row tiles (32 at two spill 352 B); 8 at four, one item of the widest layer (16 spill 72 B and
+  // measured slower: DESIGN §4).
+  constexpr int RG = RT >= 4 ? 8 : 16;
   const float4* __restrict__ stream = (const float4*)a.packed + a.wave_base[wave] * 64 + lane;
   float4 ring[RG];
 #pragma unroll
@@ -952,10 +904,8 @@ __global__ __launch_bounds__(64 * NW, LT_MLP_MIN_WAVES_PER_SIMD) void lt_mlp_ker
     const int T = a.l_T[l];
     const bool last = KIND != KIND_GATE && l == a.L - 1;  // (the chain's last layer is gated and written like the others)
     const float* const bias_l = s_bias + boff;
-    if (NW <= 4 && T == 8) mlp_layer<(NW <= 4 ? 8 : 4), RT, RG, KIND>(a, l, last, s_act, bias_l, s_noise, wave, lane, row_block, ring, stream, c0);  // (eight waves: at most 4 tiles each)
-    else if (T == 4) mlp_layer<4, RT, RG, KIND>(a, l, last, s_act, bias_l, s_noise, wave, lane, row_block, ring, stream, c0);
-    else if (MIN_TILES >= 2 || T == 2) mlp_layer<(MIN_TILES > 2 ? MIN_TILES : 2), RT, RG, KIND>(a, l, last, s_act, bias_l, s_noise, wave, lane, row_block, ring, stream, c0);
-    else mlp_layer<1, RT, RG, KIND>(a, l, last, s_act, bias_l, s_noise, wave, lane, row_block, ring, stream, c0);
+    if (T == 4) mlp_layer<4, RT, RG, KIND>(a, l, last, s_act, bias_l, s_noise, wave, lane, row_block, ring, stream, c0);  // (T = MIN_TILES .. 4: desc_ok)
+    else mlp_layer<2, RT, RG, KIND>(a, l, last, s_act, bias_l, s_noise, wave, lane, row_block, ring, stream, c0);
     MLP_STAMP(2 + l);
     if (last) break;
     lds_barrier();  // the raw sums of the whole layer are in the image
@@ -1030,7 +980,7 @@ bool desc_ok(const lt_mlp_desc* d) {
   for (int l = 0; l <= d->num_layers; ++l)
     if (d->dims[l] < 1 || d->dims[l] > LT_MLP_MAX_WIDTH) return false;
   for (int l = 1; l <= d->num_layers; ++l)
-    if (d->dims[l] > 512) return false;  // 4 output tiles per wave at most (NW = 8; 8 at NW = 4)
+    if (d->dims[l] > 512) return false;  // 4 output tiles per wave at most
   return true;
 }
 
@@ -1098,23 +1048,20 @@ int input_kind(const MlpArgs& a) {
   return a.in_magic2 ? IN_F32X2 : IN_ANY;
 }
 template <int RT>
-void launch_rt(const DualArgs& d, bool elu, bool gate, int in, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {  // more than the default 64 KB of dynamic LDS
-    attr_set = true;
-    (void)hipFuncSetAttribute((const void*)lt_mlp_kernel<RT, -1, IN_ANY>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_ANY>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_F32X4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_BF16X4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_F32X2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)lt_mlp_kernel<RT, KIND_GATE, IN_ANY>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
+hipError_t launch_rt(const DualArgs& d, bool elu, bool gate, int in, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+  // more than the default 64 KB of dynamic LDS: allowed for every form of this RT at the first launch of any of them on a device
+  const void* const forms[] = {(const void*)lt_mlp_kernel<RT, -1, IN_ANY>, (const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_ANY>,
+                               (const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_F32X4>, (const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_BF16X4>,
+                               (const void*)lt_mlp_kernel<RT, LT_ACT_ELU, IN_F32X2>, (const void*)lt_mlp_kernel<RT, KIND_GATE, IN_ANY>};
+  for (const void* k : forms)
+    if (const int e = lt_ensure_dynamic_lds(k, 160 * 1024)) return (hipError_t)e;
   if (gate) hipLaunchKernelGGL((lt_mlp_kernel<RT, KIND_GATE, IN_ANY>), grid, block, lds, s, d);
   else if (!elu) hipLaunchKernelGGL((lt_mlp_kernel<RT, -1, IN_ANY>), grid, block, lds, s, d);
   else if (in == IN_F32X4) hipLaunchKernelGGL((lt_mlp_kernel<RT, LT_ACT_ELU, IN_F32X4>), grid, block, lds, s, d);
   else if (in == IN_BF16X4) hipLaunchKernelGGL((lt_mlp_kernel<RT, LT_ACT_ELU, IN_BF16X4>), grid, block, lds, s, d);
   else if (in == IN_F32X2) hipLaunchKernelGGL((lt_mlp_kernel<RT, LT_ACT_ELU, IN_F32X2>), grid, block, lds, s, d);
   else hipLaunchKernelGGL((lt_mlp_kernel<RT, LT_ACT_ELU, IN_ANY>), grid, block, lds, s, d);
+  return hipGetLastError();
 }
 
 // row tiles per workgroup and the LDS bytes of a launch of `nets` networks (their shared LDS geometry is written back into d)
@@ -1128,7 +1075,6 @@ int launch_shape(DualArgs& d, int nets, size_t* lds_out) {
   const size_t bias_bytes = (size_t)bias * sizeof(float);
   const long long t0 = (d.net[0].m + 15) / 16, t1 = nets == 2 ? (d.net[1].m + 15) / 16 : 0;
   int rt = pick_row_tiles(t0 + t1);
-  if (const char* o = getenv("LT_MLP_ROW_TILES")) rt = atoi(o) == 4 ? 4 : (atoi(o) == 2 ? 2 : 1);  // diagnostic override
   // one workgroup's activations (+ the policy head's [rows][12 draws + 3 log-density partials + pad] block) must fit the LDS
   while (rt > 1 && (size_t)16 * rt * row_bytes + bias_bytes + (size_t)16 * rt * 64 > 160 * 1024) rt /= 2;
   *lds_out = (size_t)16 * rt * row_bytes + bias_bytes + (size_t)16 * rt * 64;
@@ -1155,11 +1101,8 @@ int launch(DualArgs& d, int nets, hipStream_t s) {
   // the input-staging form as a compile-time constant when both networks of the launch take the same one
   int in = input_kind(d.net[0]);
   if (nets == 2 && input_kind(d.net[1]) != in) in = IN_ANY;
-  if (rt == 4) {
-    launch_rt<4>(d, elu, gate, in, grid, block, lds, s);
-  } else if (rt == 2) launch_rt<2>(d, elu, gate, in, grid, block, lds, s);
-  else launch_rt<1>(d, elu, gate, in, grid, block, lds, s);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = rt == 4 ? launch_rt<4>(d, elu, gate, in, grid, block, lds, s)
+                     : rt == 2 ? launch_rt<2>(d, elu, gate, in, grid, block, lds, s) : launch_rt<1>(d, elu, gate, in, grid, block, lds, s);
   if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
   return LT_OK;
 }
@@ -1245,6 +1188,18 @@ long long fill_pack_backward(const lt_mlp_desc* fwd, const lt_mlp_desc& bd, cons
 }
 
 }  // namespace
+
+int lt_ensure_dynamic_lds(const void* kernel, int bytes) {
+  int dev = 0;
+  if (const hipError_t e = hipGetDevice(&dev)) return (int)e;
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;  // (kernel, device) pairs whose limit is set
+  const std::lock_guard<std::mutex> lock(mu);
+  if (done.count({kernel, dev})) return (int)hipSuccess;
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.insert({kernel, dev});
+  return (int)e;
+}
 
 extern "C" {
 

@@ -508,10 +508,9 @@ extern "C" int lt_head_wgrad(const float* dy, const float* x, int x_split, int64
   const int nn = n <= 1 ? 1 : (n <= 4 ? 4 : (n <= 8 ? 8 : (n <= 12 ? 12 : 16)));
   const size_t lds = (size_t)lanes * nn * k4 * 16 + (size_t)lanes * nn * 4;
   // (13 .. 16 outputs need 64 KiB + the bias lanes: more than the default dynamic-LDS limit)
-  static bool attr_set = false;
-  if (!attr_set) {
-    attr_set = true;
-    (void)hipFuncSetAttribute((const void*)lt_head_wgrad_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
+  if (const int e = lt_ensure_dynamic_lds((const void*)lt_head_wgrad_kernel<16>, 72 * 1024)) {
+    lt_set_error(hipGetErrorString((hipError_t)e));
+    return LT_EHIP;
   }
   if (lds > 72 * 1024) {
     lt_set_error("lt_head_wgrad: n * k too large for one block's LDS partials");

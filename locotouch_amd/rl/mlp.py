@@ -205,8 +205,6 @@ def _alloc_outputs(nets, m, device):
 
 import os as _os
 
-USE_SPLIT_F16_WGRAD = _os.environ.get("LT_SPLIT_F16_WGRAD", "1") != "0"  # 0: the weight gradients as library f32 GEMMs (A/B measurements)
-USE_SPLIT_DZ = _os.environ.get("LT_SPLIT_DZ", "1") != "0"  # 0: the chain writes f32 dz (one scale per workgroup), lt_wgrad splits it on the fly
 USE_FUSED_BACKWARD = _os.environ.get("LT_FUSED_BACKWARD", "1") != "0"  # 0: dz @ W as library GEMMs + lt_elu_backward_bias per layer
 
 
@@ -279,7 +277,7 @@ def backward_chain(weights, biases_out, weights_out, x, acts, dy, sums: SumJobs)
             ws = torch.empty(int(lib.lt_head_wgrad_ws_floats(m, n, k)), device=inp.device, dtype=torch.float32)
             _abi.check(lib.lt_head_wgrad(vp(dz.data_ptr()), vp(inp.data_ptr()), 0, m, n, k, vp(None), vp(None), vp(ws.data_ptr()), stream), "lt_head_wgrad")
             sums.add(ws, nblk, n * k + 16, n * k + n, n * k, weights_out[l], biases_out[l])
-        elif amax is not None and USE_SPLIT_F16_WGRAD and n % 4 == 0 and k % 4 == 0:
+        elif amax is not None and n % 4 == 0 and k % 4 == 0:
             # dW = dz^T x on the f16 matrix cores, f32-equivalent (csrc/lt_wgrad.hip): slices of the rows -> slabs -> the joint sum launch
             sp = int(lib.lt_wgrad_splits(m, n, k))
             slabs = torch.empty(sp * n * k, device=inp.device, dtype=torch.float32)
@@ -386,7 +384,7 @@ class PackedPair:
     def _fused_backward_possible(self, x0, x1) -> bool:
         from .linear import _head_wgrad_ok
 
-        if not (USE_FUSED_BACKWARD and USE_SPLIT_F16_WGRAD):
+        if not USE_FUSED_BACKWARD:
             return False
         if x0.dtype != torch.float32 or x1.dtype != torch.float32 or not x0.is_contiguous() or not x1.is_contiguous():
             return False
@@ -442,7 +440,7 @@ class PackedPair:
             arrs.append((arr(*[a.data_ptr() for a in acts[k]]), arr(*[t.data_ptr() for t in dz]), arr(*[am[l].data_ptr() for l in range(L - 1)])))
         # `dy_amax`: (max |dy0|, max |dy1|) as device scalars (lt_ppo_loss leaves them): the chain then runs on ONE scale per network
         # and writes every dz in the split format, scaled - what lt_wgrad reads without converting
-        dzsp = int(dy_amax is not None and USE_SPLIT_DZ)
+        dzsp = int(dy_amax is not None)
         scales = torch.empty(2, device=dev, dtype=torch.float32)
         _abi.check(lib.lt_mlp_backward_pair(ctypes.byref(nets[0].desc), vp(nets[0].bpacked.data_ptr()), vp(dys[0].data_ptr()), *arrs[0],
                                             ctypes.byref(nets[1].desc), vp(nets[1].bpacked.data_ptr()), vp(dys[1].data_ptr()), *arrs[1],

@@ -1,6 +1,5 @@
 #!/usr/bin/env python3
-"""Time of lt_mlp_backward_pair alone (both stacks of the LocoTouch ActorCritic, m rows) - and of probe builds without the gate loads /
-the dz stores (tools/build_variant.py <name> -DLT_GATE_NO_LOAD ...; LOCOTOUCH_AMD_LIB selects the library)."""
+"""Time of lt_mlp_backward_pair alone (both stacks of the LocoTouch ActorCritic, m rows; LOCOTOUCH_AMD_LIB selects the library)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -30,14 +30,16 @@ for m in [int(a) for a in sys.argv[1:]] or [4096]:
     if hasattr(lib, "lt_debug_mlp_stamps"):
         import ctypes, numpy as np
         net(x, out); torch.cuda.synchronize()
-        NWV = int(os.environ.get("NWV", "4"))
+        NWV = 8  # waves per workgroup (NW in csrc/lt_mlp.hip)
         buf = (ctypes.c_uint64 * (1024 * 8 * NWV))()
         lib.lt_debug_mlp_stamps(buf)
-        nb = min(1024, (m + 15) // 16 // int(os.environ.get("LT_MLP_ROW_TILES", "1")))
+        t16 = (m + 15) // 16
+        rt = 4 if t16 // 4 >= 256 else (2 if t16 // 2 >= 256 else 1)  # row tiles per workgroup (pick_row_tiles in csrc/lt_mlp.hip)
+        nb = min(1024, (t16 + rt - 1) // rt)
         st = np.array(buf, dtype=np.uint64).reshape(1024, NWV, 8)[:nb].astype(np.int64)
         L = len(dims) - 1
         t0 = st[:, :, 0].min()
-        print("stamps (10 ns ticks -> ns), mean over blocks, per wave 0..3; times since kernel start")
+        print(f"stamps (10 ns ticks -> ns), mean over blocks, per wave 0..{NWV - 1}; times since kernel start")
         names = ["start", "input staged"] + [f"layer {l} done" for l in range(L)]
         for i, nm in enumerate(names):
             print(f"   {nm:16s}", " ".join(f"{(st[:, w, i] - t0).mean() * 10:8.0f}" for w in range(NWV)))
