@@ -14,6 +14,7 @@
  *   env.episode_length_buf = ... (on_policy_runner:121)   lt_env_get_view(LT_F_EP_LEN) (int64, writable)
  *   env.get_observations() (on_policy_runner.py:32,127)   lt_env_get_view(LT_F_OBS_POLICY / _CRITIC)
  *   env.scene[...].data.* / sensors[...].data.* (B3)      lt_env_get_view(field)
+ *   sensors[...].data.net_forces_w_history (vectors)     lt_env_bind_contact_forces (opt-in side buffer)
  *   command_term.set_ranges (mdp/commands.py:471)         device-side in lt_env_step (tail of the step kernel),
  *                                                         host override: lt_env_set_command_ranges
  *   term-level evaluation for parity tests                lt_env_eval_terms
@@ -33,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LT_ABI_VERSION 17
+#define LT_ABI_VERSION 18
 
 /* error codes */
 #define LT_OK 0
@@ -363,6 +364,19 @@ int lt_env_destroy(lt_env* env);
 /* Size of the caller-owned device arena. */
 int lt_env_state_bytes(const lt_cfg* cfg, size_t* bytes);
 int lt_env_bind(lt_env* env, void* device_arena, size_t bytes);
+/* Contact-force VECTORS, opt-in: IsaacLab's ContactSensorData.net_forces_w_history [DEP] of the robot's contact sensor
+ * (locomotion_base_env_cfg.py:34-38, history_length 3) and of the object's (object_transport_teacher_env_cfg.py:68-72): the
+ * world-frame net force acting ON each body at the last three sim steps of an env step, newest first.  The arena keeps only their
+ * norms (LT_F_FORCE_HIST, LT_F_TRUNK_FORCE_HIST); component-reading terms (mdp/robotlab_reward_funcs.py:428-436 feet_stumble:
+ * |F_xy| against |F_z|) need the vectors.  The buffer is caller-owned side memory, not part of the arena: quad arrays
+ * float[slot 3][k 14][npad][4] (lane = leg), k = type * 3 + comp for hip / thigh / calf / foot x (x, y, z), k = 12 the trunk and
+ * k = 13 the object (lanes 0-2 = x, y, z, lane 3 = 0; all zeros in the locomotion task); 672 B per env.
+ * lt_env_bind_contact_forces: NULL unbinds; LT_EINVAL for a buffer smaller than lt_env_contact_force_bytes, one not 256-byte
+ * aligned, or cfg.decimation < 3 (each step rewrites all three slots from its last three sim steps, write-only; fewer sim steps
+ * per env step would need the history shifted).  Launches nothing.  While a buffer is bound every env step writes it (envs that
+ * reset in the step: all-zero slots) and lt_env_reset_all zeroes it; a hipGraph captured while bound records the writing step. */
+int lt_env_contact_force_bytes(const lt_env* env, size_t* bytes);
+int lt_env_bind_contact_forces(lt_env* env, void* device_buf, size_t bytes);
 /* Startup events + reset of every env + first observation (RslRlVecEnvWrapper.__init__ calls env.reset()). */
 int lt_env_reset_all(lt_env* env, void* stream);
 /* One ManagerBasedRLEnv.step(): actions float[N][12] (device).  Outputs live in the arena views

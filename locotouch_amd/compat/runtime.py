@@ -256,7 +256,10 @@ def make_env(task_id: str, cfg):
 
     lt, sizes = translate_env_cfg(task_id, cfg)
     device = getattr(getattr(cfg, "sim", None), "device", None) or "cuda:0"
-    return ManagedEnv(task_id, cfg, LocoTouchVecEnv(task_id, device=device, cfg=lt, object_sizes=sizes),
+    # LT_CONTACT_FORCE_VECTORS=1: the contact sensors' net_forces_w(_history) carry the true world-frame vectors (for user terms
+    # that read force components, e.g. mdp/robotlab_reward_funcs.py:428-436); without it they carry |F| in z (scene_views.py)
+    fvec = os.environ.get("LT_CONTACT_FORCE_VECTORS", "0") not in ("", "0")
+    return ManagedEnv(task_id, cfg, LocoTouchVecEnv(task_id, device=device, cfg=lt, object_sizes=sizes, contact_force_vectors=fvec),
                       extra_rewards=getattr(lt, "extra_reward_terms", ()), extra_terminations=getattr(lt, "extra_termination_terms", ()),
                       extra_observations=getattr(lt, "extra_observation_terms", ()))
 

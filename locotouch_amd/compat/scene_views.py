@@ -14,9 +14,13 @@ adds `weight * dt * value` to the reward the kernel computed (the SLOW path: a h
 Limits, stated:
 * the step kernel resets finished envs inside the step, so a user term sees the post-reset state of an env that just finished and
   its value is dropped there (the fused terms are evaluated before the reset, as the RewardManager does [DEP]);
-* contact forces are stored as norms - `net_forces_w_history` carries each body's |F| in the z component (norm-exact: every
-  reference term takes `torch.linalg.norm(..., dim=-1)` of it; direction not kept); air / contact timers exist for the four
-  feet (the reference's sensor has them for all 17 bodies; only the feet are read, rewards.py:79-92, commands.py:396);
+* contact forces: by default the arena keeps norms only - `net_forces_w_history` carries each body's |F| in the z component
+  (norm-exact: every term of rewards.py takes `torch.linalg.norm(..., dim=-1)` of it; direction not kept, so a term that reads
+  components - feet_stumble, mdp/robotlab_reward_funcs.py:428-436, compares |F_xy| with |F_z| - is silently wrong) and the
+  object sensor has no forces.  An env built with `contact_force_vectors=True` (LT_CONTACT_FORCE_VECTORS=1 in runtime.py) serves
+  the true world-frame vectors: the robot sensor's `net_forces_w(_history)` and the object sensor's `net_forces_w(_history)`
+  (N, 3, 1, 3) (object_transport_teacher_env_cfg.py:68-72).  Air / contact timers exist for the four feet (the reference's
+  sensor has them for all 17 bodies; only the feet are read, rewards.py:79-92, commands.py:396);
 * link poses / velocities other than the feet (`body_pos_w`, `body_quat_w`, `body_lin_vel_w`, `body_ang_vel_w`) are forward
   kinematics in torch from the root and joint state (the feet are the kernel's own LT_F_FOOT_POS_W / _VEL_W);
 * user TERMINATION terms are evaluated on the state a step left and take effect through the kernel's own termination stage one
@@ -451,7 +455,11 @@ class TermEnv:
             tr = f("LT_F_TRUNK_FORCE_HIST")[:, 0, :3]
             return torch.cat([tr.unsqueeze(-1), fh.reshape(n, 3, 16)], dim=-1)
 
+        vectors = bool(getattr(vec, "contact_force_vectors", False))
+
         def forces_hist():
+            if vectors:  # world-frame vectors (LocoTouchVecEnv(contact_force_vectors=True))
+                return vec.contact_forces_w_history
             out = torch.zeros(n, 3, 17, 3, device=self.device)
             out[..., 2] = force_norms()
             return out
@@ -480,8 +488,11 @@ class TermEnv:
                                                    f("LT_F_OBJ_ANG_VEL_W")[:, 0, :3]], dim=1),
             }), ["Object"])
             ot = lambda i: (lambda: f("LT_F_OBJ_TIMERS")[:, 0, i:i + 1].clone())  # noqa: E731
-            sensors["object_contact_sensor"] = _Entity(_Data({"current_air_time": ot(0), "current_contact_time": ot(1), "last_air_time": ot(2),
-                                                              "last_contact_time": ot(3)}), ["Object"])
+            osens = {"current_air_time": ot(0), "current_contact_time": ot(1), "last_air_time": ot(2), "last_contact_time": ot(3)}
+            if vectors:
+                osens["net_forces_w_history"] = lambda: vec.object_forces_w_history
+                osens["net_forces_w"] = lambda: vec.object_forces_w_history[:, 0]
+            sensors["object_contact_sensor"] = _Entity(_Data(osens), ["Object"])
         self.scene = Scene(ents, sensors, n)
         self.command_manager = _Commands(self)
         self.action_manager = _Actions(self)

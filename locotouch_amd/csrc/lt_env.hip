@@ -52,6 +52,9 @@ struct KArgs {
   // yet - workgroup 0's RNG wave runs it beside this step's first physics substep (lt_post.h, chained form)
   int step_offset;
   int decide_first;
+  // contact-force vectors (lt_env_bind_contact_forces; read by the FVEC instantiations only): caller-owned quad arrays
+  // [slot 3][k 14][npad][4] f32, k = type * 3 + comp for the leg bodies, 12 trunk, 13 object.  Null when none is bound.
+  float* fvec;
 };
 static_assert(sizeof(lt_dev_args) <= LT_DEV_ARGS_BYTES, "lt_dev_args outgrew its arena slot");
 
@@ -511,7 +514,11 @@ struct HelperParts {
 
 // RB: the observation rows behind a.obs_prev / a.obs_next are bf16 (rollout-storage slots of BASELINE config 5), two columns per
 // 32-bit word; the newest frame is rounded to nearest-even when it enters a row, older frames are carried bit for bit.
-template <int TASK, int MODE, bool HELPERS, bool RB = false>
+// FVEC (MODE_STEP only): the step also writes the world-frame contact-force vectors of the last three sim steps to a.fvec -
+// IsaacLab's net_forces_w_history (newest first, force ON the body).  Write-only: with decimation >= 3 (lt_env_bind_contact_forces
+// refuses less) decimation iteration d >= decimation - 3 stores slot decimation - 1 - d from its own Report, so no history is
+// loaded or held in registers; envs that reset in the step get all-zero slots, as their |F| history does.
+template <int TASK, int MODE, bool HELPERS, bool RB = false, bool FVEC = false>
 __global__ __launch_bounds__(HELPERS ? 256 : 64, HELPERS ? 1 : LT_STEP_MIN_WAVES_LARGE) void lt_step_kernel(const KArgs a) {
 #ifdef LT_STAMPS
   unsigned long long stamps_[8], bar_wait_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -530,6 +537,8 @@ __global__ __launch_bounds__(HELPERS ? 256 : 64, HELPERS ? 1 : LT_STEP_MIN_WAVES
   const long long q4 = a.npad * 4;
   char* const arena = a.arena;
   auto F = [&](int field, int q) -> float* { return (float*)arena + (long long)(k_cumq.v[field] + q) * q4 + gid; };
+  static_assert(!FVEC || MODE == MODE_STEP, "contact-force vectors are an output of the env step");
+  auto FV = [&](int slot, int k) -> float* { return a.fvec + (long long)(slot * 14 + k) * q4 + gid; };  // (FVEC only)
 
   // ---- prologue: ONE memory round trip.  The (cfg, layout) block (two 16-B loads per lane, staged into LDS: ~130 scattered
   //      scalar loads - each its own L2 round trip for a lone wave - become cheap ds_reads) and the state the physics needs
@@ -1057,6 +1066,18 @@ __global__ __launch_bounds__(HELPERS ? 256 : 64, HELPERS ? 1 : LT_STEP_MIN_WAVES
       X.trunk_fh[2] = X.trunk_fh[1]; X.trunk_fh[1] = X.trunk_fh[0];
       X.trunk_fh[0] = norm(qsum(rep.trunk_part));
       if (HAS_OBJ) timers_update(O.cur_air, O.cur_con, O.last_air, O.last_con, norm(qsum(rep.obj_part)) > c.contact_force_threshold, c.sim_dt);
+      if constexpr (FVEC) {  // the same Report as vectors: lane = leg for the leg bodies, lanes 0-2 = x, y, z for trunk and object
+        const int slot = c.decimation - 1 - d;
+        if (slot < 3) {
+#pragma unroll
+          for (int ty = 0; ty < 4; ++ty) {
+            ST_STATE(FV(slot, ty * 3 + 0), rep.body[ty].x); ST_STATE(FV(slot, ty * 3 + 1), rep.body[ty].y); ST_STATE(FV(slot, ty * 3 + 2), rep.body[ty].z);
+          }
+          const V3 ft = qsum(rep.trunk_part), fo = HAS_OBJ ? qsum(rep.obj_part) : v3(0, 0, 0);
+          ST_STATE(FV(slot, 12), sel4(leg, ft.x, ft.y, ft.z, 0.f));
+          ST_STATE(FV(slot, 13), sel4(leg, fo.x, fo.y, fo.z, 0.f));
+        }
+      }
     }
     if (HELPERS && HAS_OBJ) {  // the object as its helper wave left it (written before the last barrier B)
       O.p = v3(s_mb_ofin[0][lane], s_mb_ofin[1][lane], s_mb_ofin[2][lane]);
@@ -1323,6 +1344,12 @@ __global__ __launch_bounds__(HELPERS ? 256 : 64, HELPERS ? 1 : LT_STEP_MIN_WAVES
     G.cur_air = G.cur_con = G.last_air = G.last_con = 0.f;
     G.g_last_air = G.g_last_con = G.g_valid = 0.f; G.g_flags = 0;                                               // rewards.py:107-114
     X.trunk_fh[0] = X.trunk_fh[1] = X.trunk_fh[2] = 0.f;
+    if constexpr (FVEC) {  // (overwrites this step's vectors, stored in the decimation loop before the reset was known)
+#pragma unroll
+      for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int k = 0; k < 14; ++k) ST_STATE(FV(s, k), 0.f);
+    }
     X.gait_cmd = v3(0, 0, 0); X.gait_step = 0.f;
     if (HAS_OBJ) {
       u = draw(RS_RESET_MAT, 3, 0);                                                                            // E3 (events.py:160-196), E2
@@ -1717,10 +1744,35 @@ KArgs make_args(const lt_env* env, const float* actions) {
   k.obs_next[0] = rp; k.obs_next[1] = rc;
   k.rec_values = nullptr; k.rec_gamma = 0.f; k.rec_rewards = nullptr; k.rec_dones = nullptr;
   k.step_offset = 0; k.decide_first = 0;
+  k.fvec = (float*)env->fvec;
   return k;
 }
 
 struct RecordArgs { const float* values; float gamma; float* rewards; unsigned char* dones; };
+
+// the step kernel instantiation of this launch: task x form (helpers) x row format (rb) x contact-force vectors (FV)
+template <int MODE, bool FV>
+int launch_form(const lt_env* env, const KArgs& k, const dim3 grid, const bool helpers, const bool rb, hipStream_t s) {
+  if (rb && env->cfg.task == LT_TASK_LOCOMOTION) {
+    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE_STEP, true, true, FV>), grid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE_STEP, false, true, FV>), grid, dim3(64), 0, s, k);
+  } else if (rb && !env->cfg.tactile_enabled) {
+    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE_STEP, true, true, FV>), grid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE_STEP, false, true, FV>), grid, dim3(64), 0, s, k);
+  } else if (rb) {
+    return (int)hipErrorInvalidValue;  // (tactile tasks keep f32 rows)
+  } else if (env->cfg.task == LT_TASK_LOCOMOTION) {
+    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE, MODE == MODE_STEP, false, FV>), grid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE, false, false, FV>), grid, dim3(64), 0, s, k);
+  } else if (env->cfg.tactile_enabled) {
+    if (helpers) hipLaunchKernelGGL((lt_step_kernel<K_TASK_TACTILE, MODE, MODE == MODE_STEP, false, FV>), grid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL((lt_step_kernel<K_TASK_TACTILE, MODE, false, false, FV>), grid, dim3(64), 0, s, k);
+  } else {
+    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE, MODE == MODE_STEP, false, FV>), grid, dim3(256), 0, s, k);
+    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE, false, false, FV>), grid, dim3(64), 0, s, k);
+  }
+  return 0;
+}
 
 template <int MODE>
 int launch_step(const lt_env* env, const float* actions, hipStream_t s, const float* const* prev = nullptr, float* const* next = nullptr,
@@ -1760,24 +1812,13 @@ int launch_step(const lt_env* env, const float* actions, hipStream_t s, const fl
   // (no row pointer at all - lt_env_step, lt_env_step_profiled - means the arena's own f32 rows, whatever the format of caller rows)
   const bool any_rows = (prev && (prev[0] || prev[1])) || (next && (next[0] || next[1]));
   if (MODE == MODE_STEP && env->rows_bf16 && any_rows && !rb) return (int)hipErrorInvalidValue;
-  if (rb && env->cfg.task == LT_TASK_LOCOMOTION) {
-    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE_STEP, true, true>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE_STEP, false, true>), grid, dim3(64), 0, s, k);
-  } else if (rb && !env->cfg.tactile_enabled) {
-    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE_STEP, true, true>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE_STEP, false, true>), grid, dim3(64), 0, s, k);
-  } else if (rb) {
-    return (int)hipErrorInvalidValue;  // (tactile tasks keep f32 rows)
-  } else if (env->cfg.task == LT_TASK_LOCOMOTION) {
-    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE, MODE == MODE_STEP>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_LOCOMOTION, MODE, false>), grid, dim3(64), 0, s, k);
-  } else if (env->cfg.tactile_enabled) {
-    if (helpers) hipLaunchKernelGGL((lt_step_kernel<K_TASK_TACTILE, MODE, MODE == MODE_STEP>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((lt_step_kernel<K_TASK_TACTILE, MODE, false>), grid, dim3(64), 0, s, k);
+  int rc;
+  if constexpr (MODE == MODE_STEP) {  // a bound contact-force buffer selects the FVEC instantiation of the same form
+    rc = k.fvec ? launch_form<MODE, true>(env, k, grid, helpers, rb, s) : launch_form<MODE, false>(env, k, grid, helpers, rb, s);
   } else {
-    if (helpers) hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE, MODE == MODE_STEP>), grid, dim3(256), 0, s, k);
-    else hipLaunchKernelGGL((lt_step_kernel<LT_TASK_TRANSPORT_TEACHER, MODE, false>), grid, dim3(64), 0, s, k);
+    rc = launch_form<MODE, false>(env, k, grid, helpers, rb, s);
   }
+  if (rc != 0) return rc;
   // the population pass of the step (curriculum decision, population gate, step counter): one wave behind the step kernel,
   // unless the caller places it itself (lt_env_defer_gate: beside the next policy launch in the rollout graph)
   if (MODE == MODE_STEP) {
@@ -1804,6 +1845,7 @@ int lt_launch_reset_all(const lt_env* env, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(env->arena, 0, (size_t)env->layout.off_obj_sizes, s);  // LT_F_OBJ_SIZES and the (cfg, layout) block survive
   if (e != hipSuccess) return (int)e;
+  if (env->fvec && (e = hipMemsetAsync(env->fvec, 0, env->fvec_bytes, s)) != hipSuccess) return (int)e;  // no contact forces before a step
   e = hipMemcpyAsync((char*)env->arena + env->layout.off_dev_args, &env->dev_args, sizeof(lt_dev_args), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return (int)e;
   const KArgs k = make_args(env, nullptr);

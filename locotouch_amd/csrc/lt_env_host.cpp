@@ -77,6 +77,29 @@ int lt_env_bind(lt_env* env, void* device_arena, size_t bytes) {
   return LT_OK;
 }
 
+// 3 slots x 14 quad arrays (12 leg-body components, trunk, object) x npad x 16 B
+static size_t contact_force_bytes(const lt_env* env) { return (size_t)3 * 14 * (size_t)env->layout.npad * 16; }
+
+int lt_env_contact_force_bytes(const lt_env* env, size_t* bytes) {
+  if (!env || !bytes) return LT_EINVAL;
+  *bytes = contact_force_bytes(env);
+  return LT_OK;
+}
+
+int lt_env_bind_contact_forces(lt_env* env, void* device_buf, size_t bytes) {
+  if (!env) return LT_EINVAL;
+  if (!device_buf) { env->fvec = nullptr; env->fvec_bytes = 0; return LT_OK; }
+  if (env->cfg.decimation < 3) {
+    lt_set_error("lt_env_bind_contact_forces: cfg.decimation must be at least 3 (each step rewrites the 3-slot history from its last 3 sim steps)");
+    return LT_EINVAL;
+  }
+  if (bytes < contact_force_bytes(env)) { lt_set_error("lt_env_bind_contact_forces: buffer too small (lt_env_contact_force_bytes)"); return LT_EINVAL; }
+  if (((uintptr_t)device_buf & 255) != 0) { lt_set_error("lt_env_bind_contact_forces: buffer must be 256-byte aligned"); return LT_EINVAL; }
+  env->fvec = device_buf;
+  env->fvec_bytes = contact_force_bytes(env);
+  return LT_OK;
+}
+
 int lt_env_get_view(lt_env* env, int field, lt_view* v) {
   if (!env || !v) return LT_EINVAL;
   const lt_layout& L = env->layout;

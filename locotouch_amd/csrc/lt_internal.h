@@ -19,6 +19,8 @@ struct lt_env {
   mutable int gate_pending = 0;   // a population pass is outstanding
   int rows_bf16 = 0;         // lt_env_set_row_format: the row pointers of lt_env_step_rows / _rollout are bf16 rows
   mutable int test_chain_skew = 0;  // lt_env_defer_gate mode 3 (test hook): the next chained launch announces a wrong step id
+  void* fvec = nullptr;       // lt_env_bind_contact_forces: caller-owned contact-force vector buffer (null: none bound)
+  size_t fvec_bytes = 0;
 };
 
 // implemented in lt_env.hip -------------------------------------------------------------------------

@@ -44,10 +44,13 @@ class LocoTouchVecEnv:
 
     def __init__(self, task: str | int = "Isaac-RandCylinderTransportTeacher-LocoTouch-v1", num_envs: int | None = None,
                  device: str | torch.device = "cuda:0", seed: int = 42, cfg: _abi.LtCfg | None = None,
-                 object_sizes: torch.Tensor | None = None, **overrides):
+                 object_sizes: torch.Tensor | None = None, contact_force_vectors: bool = False, **overrides):
         """`task`: a registered gym id (its preset; `num_envs=None` keeps the registration's default, e.g. 50 for -Play-) or
         an LT_TASK_* kind.  `cfg`: a complete lt_cfg instead (e.g. translated from a reference cfg tree,
-        locotouch_amd/compat/cfg_translate.py).  `object_sizes` [N][2]: explicit per-env cylinder (radius, length)."""
+        locotouch_amd/compat/cfg_translate.py).  `object_sizes` [N][2]: explicit per-env cylinder (radius, length).
+        `contact_force_vectors`: every step also writes the world-frame contact-force vectors (lt_env_bind_contact_forces;
+        `contact_forces_w_history`, `object_forces_w_history`).  Bound here, before the first reset, and never rebound, so a graph
+        captured from this env always records the writing step kernel."""
         self.device = torch.device(device)
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise RuntimeError("LocoTouchVecEnv needs a HIP device (there is no CPU path in the product; "
@@ -83,6 +86,17 @@ class LocoTouchVecEnv:
         self._arena_aligned = self.arena[pad:pad + nbytes.value]
         _abi.check(self._lib.lt_env_bind(self._handle, ctypes.c_void_p(self._arena_aligned.data_ptr()), nbytes.value), "lt_env_bind")
         self._views: dict[int, torch.Tensor] = {}
+        self.contact_force_vectors = bool(contact_force_vectors)
+        self._fvec_mem = self._fvec = None
+        if self.contact_force_vectors:
+            fbytes = ctypes.c_size_t()
+            _abi.check(self._lib.lt_env_contact_force_bytes(self._handle, ctypes.byref(fbytes)), "lt_env_contact_force_bytes")
+            with torch.cuda.device(self.device):
+                self._fvec_mem = torch.zeros(fbytes.value + 256, dtype=torch.uint8, device=self.device)
+            fpad = (-self._fvec_mem.data_ptr()) % 256
+            self._fvec = self._fvec_mem[fpad:fpad + fbytes.value].view(torch.float32).view(3, 14, -1, 4)
+            _abi.check(self._lib.lt_env_bind_contact_forces(self._handle, ctypes.c_void_p(self._fvec.data_ptr()), fbytes.value),
+                       "lt_env_bind_contact_forces")
         self.obs_policy = self.view(C["LT_F_OBS_POLICY"])
         self.obs_critic = self.view(C["LT_F_OBS_CRITIC"])
         self.reward_buf = self.view(C["LT_F_REWARD"])
@@ -342,6 +356,22 @@ class LocoTouchVecEnv:
         t = self.field("LT_F_EVENT_TIMERS")[:, 0, :]
         return {"error_vel_xy": t[:, 2], "error_vel_yaw": t[:, 3], "foot_air_time_variance": self.field("LT_F_TRUNK_FORCE_HIST")[:, 0, 3]}
 
+    @property
+    def contact_forces_w_history(self) -> torch.Tensor:
+        """(N, 3, 17, 3): the robot contact sensor's net_forces_w_history [DEP] - world-frame force on each body at the last three
+        sim steps, newest first; bodies in scene_views.BODY_NAMES order (trunk, then 1 + type * 4 + leg).  A fresh tensor."""
+        return robot_forces_from_buffer(self._bound_forces(), self.num_envs)
+
+    @property
+    def object_forces_w_history(self) -> torch.Tensor:
+        """(N, 3, 1, 3): the object contact sensor's net_forces_w_history [DEP] (zeros in the locomotion task).  A fresh tensor."""
+        return object_forces_from_buffer(self._bound_forces(), self.num_envs)
+
+    def _bound_forces(self) -> torch.Tensor:
+        if self._fvec is None:
+            raise RuntimeError("contact-force vectors are off: construct the env with contact_force_vectors=True")
+        return self._fvec
+
     def close(self) -> None:
         if getattr(self, "_handle", None):
             self._lib.lt_env_destroy(self._handle)
@@ -352,6 +382,19 @@ class LocoTouchVecEnv:
             self.close()
         except Exception:
             pass
+
+
+def robot_forces_from_buffer(buf: torch.Tensor, n: int) -> torch.Tensor:
+    """The contact-force buffer (lt_env_bind_contact_forces: float [slot 3][k 14][npad][4], k = type * 3 + comp per leg lane, 12 the
+    trunk in lanes 0-2) -> (n, 3 slots, 17 bodies, 3): trunk, then body 1 + type * 4 + leg."""
+    legs = buf[:, :12, :n].reshape(3, 4, 3, n, 4).permute(3, 0, 1, 4, 2).reshape(n, 3, 16, 3)  # [env][slot][type][leg][comp]
+    trunk = buf[:, 12, :n, :3].permute(1, 0, 2).unsqueeze(2)
+    return torch.cat([trunk, legs], dim=2)
+
+
+def object_forces_from_buffer(buf: torch.Tensor, n: int) -> torch.Tensor:
+    """... -> (n, 3 slots, 1, 3): the object (k = 13, lanes 0-2)."""
+    return buf[:, 13, :n, :3].permute(1, 0, 2).unsqueeze(2).clone()
 
 
 def reset_batch_means(rows: torch.Tensor) -> list[float]:
@@ -368,5 +411,5 @@ def make(task: str, num_envs: int | None = None, device: str = "cuda:0", seed: i
     return LocoTouchVecEnv(task, num_envs=num_envs, device=device, seed=seed, **kw)
 
 
-__all__ = ["LocoTouchVecEnv", "make", "task_ids", "reset_batch_means", "REWARD_TERM_NAMES", "TERMINATION_NAMES"]
+__all__ = ["LocoTouchVecEnv", "make", "task_ids", "reset_batch_means", "robot_forces_from_buffer", "object_forces_from_buffer", "REWARD_TERM_NAMES", "TERMINATION_NAMES"]
 _ = math
