@@ -25,18 +25,25 @@
 /* ------------------------------------------------------------------------------------------------ */
 /* model tables                                                                                      */
 /* ------------------------------------------------------------------------------------------------ */
-static const float k_link_mass[4][3] = LT_LINK_MASS_INIT;
-static const float k_link_com[4][3][3] = LT_LINK_COM_INIT;
-static const float k_link_icom[4][3][6] = LT_LINK_ICOM_INIT;
-static const float k_joint_off[4][3][3] = LT_JOINT_OFFSET_INIT;
+/* `real` tables holding the header's f32 literals: the f64 build (-DLT_REAL=double) widens the model, it does not change it */
+static const real k_link_mass[4][3] = LT_LINK_MASS_INIT;
+static const real k_link_com[4][3][3] = LT_LINK_COM_INIT;
+static const real k_link_icom[4][3][6] = LT_LINK_ICOM_INIT;
+static const real k_joint_off[4][3][3] = LT_JOINT_OFFSET_INIT;
 static const int k_joint_axis[3] = LT_JOINT_AXIS_INIT;
-static const float k_joint_lo[3] = LT_JOINT_LOWER_INIT;
-static const float k_joint_hi[3] = LT_JOINT_UPPER_INIT;
-static const float k_joint_default[4][3] = LT_JOINT_DEFAULT_INIT;
-static const float k_trunk_com[3] = LT_TRUNK_COM_INIT;
-static const float k_trunk_icom[6] = LT_TRUNK_ICOM_INIT;
-static const float k_hip_cyl_y[4] = LT_HIP_CYL_Y_INIT;
-static const float k_trunk_half[3] = LT_TRUNK_BOX_HALF_INIT;
+static const real k_joint_lo[3] = LT_JOINT_LOWER_INIT;
+static const real k_joint_hi[3] = LT_JOINT_UPPER_INIT;
+static const real k_joint_default[4][3] = LT_JOINT_DEFAULT_INIT;
+static const real k_trunk_com[3] = LT_TRUNK_COM_INIT;
+static const real k_trunk_icom[6] = LT_TRUNK_ICOM_INIT;
+static const real k_hip_cyl_y[4] = LT_HIP_CYL_Y_INIT;
+static const real k_trunk_half[3] = LT_TRUNK_BOX_HALF_INIT;
+
+/* f32 ABI <-> real.  WIDEN / NARROW take true arrays (struct fields, locals), never array parameters. */
+static void widen(real* o, const float* a, int n) { for (int i = 0; i < n; ++i) o[i] = a[i]; }
+static void narrow(float* o, const real* a, int n) { for (int i = 0; i < n; ++i) o[i] = (float)a[i]; }
+#define WIDEN(o, a) widen((real*)(o), (const float*)(a), (int)(sizeof(a) / sizeof(float)))
+#define NARROW(o, a) narrow((float*)(o), (const real*)(a), (int)(sizeof(o) / sizeof(float)))
 
 #define NB 13 /* dynamic bodies: trunk + 4 x (hip, thigh, calf+foot) */
 #define BODY(leg, k) (1 + (leg)*3 + (k))
@@ -226,14 +233,20 @@ static void scatter(const env_t* E, void* arena, const lt_layout* L, int64_t e) 
 /* K1: action term + DC-motor PD                                                                     */
 /* ------------------------------------------------------------------------------------------------ */
 /* reference locotouch/mdp/actions.py:30-44 (shift prev<-raw, clip +-clip, scale) */
-void lt_oracle_process_action(const lt_cfg* cfg, const float a[12], float raw[12], float prev[12], float prev2[12]) {
+static void process_action_r(const lt_cfg* cfg, const float a[12], real raw[12], real prev[12], real prev2[12]) {
   for (int j = 0; j < 12; ++j) {
     prev2[j] = prev[j];
     prev[j] = raw[j];
-    float x = a[j];
+    real x = a[j];
     x = x < -cfg->action_clip ? -cfg->action_clip : (x > cfg->action_clip ? cfg->action_clip : x);
     raw[j] = x * cfg->action_scale;
   }
+}
+void lt_oracle_process_action(const lt_cfg* cfg, const float a[12], float raw[12], float prev[12], float prev2[12]) {
+  real r[12], p[12], p2[12];
+  widen(r, raw, 12); widen(p, prev, 12); widen(p2, prev2, 12);
+  process_action_r(cfg, a, r, p, p2);
+  narrow(raw, r, 12); narrow(prev, p, 12); narrow(prev2, p2, 12);
 }
 
 /* DCMotor explicit PD with torque-speed clipping: reference assets/go1.py:41-49 + IsaacLab DCMotor [DEP] */
@@ -797,8 +810,64 @@ static void sensors_update(const lt_cfg* cfg, env_t* E, const contact_report* re
 /* ------------------------------------------------------------------------------------------------ */
 static const int k_gait_order[4] = {0, 3, 1, 2}; /* gait foot columns [FR, RL, FL, RR] (rewards.py:89-92) as leg ids */
 
+/* `real` twins of the f32 ABI records lt_term_in / lt_gait_io (lt_oracle.h, same fields in the same order).  The term code
+ * works on these; the exported float entry points widen their inputs and narrow the results, and the step path fills them
+ * straight from env_t, so the f64 build computes every term in double. */
+typedef struct {
+  real root_pos[3], root_quat[4], root_lin[3], root_ang[3];
+  real q[4][3], qd[4][3], qdd[4][3], tau[4][3];
+  real act_raw[4][3], act_prev[4][3];
+  real fhist[3][4][4];
+  real trunk_fhist[3];
+  real foot_pos[4][3], foot_vel[4][3];
+  real obj_pos[3], obj_quat[4], obj_lin[3], obj_ang[3];
+  real obj_timers[4];
+  real cmd[3];
+  int32_t terminated;
+} term_in_r;
+typedef struct {
+  real cur_air[4], cur_con[4], sensor_last_air[4];
+  real cmd[3];
+  real lin_err, ang_err;
+  real obj_xy_yaw[2];
+  int32_t any_nonzero_cmd;
+  real last_step_air[4], last_step_con[4], valid_last_air[4];
+  int32_t swinging_in_zero_cmd[4], valid_prev_contact[4];
+  real last_cmd[3];
+  real step_from_change;
+} gait_io_r;
+
+
+static void term_in_widen(const lt_term_in* in, term_in_r* r) {
+  WIDEN(r->root_pos, in->root_pos); WIDEN(r->root_quat, in->root_quat); WIDEN(r->root_lin, in->root_lin); WIDEN(r->root_ang, in->root_ang);
+  WIDEN(r->q, in->q); WIDEN(r->qd, in->qd); WIDEN(r->qdd, in->qdd); WIDEN(r->tau, in->tau);
+  WIDEN(r->act_raw, in->act_raw); WIDEN(r->act_prev, in->act_prev); WIDEN(r->fhist, in->fhist); WIDEN(r->trunk_fhist, in->trunk_fhist);
+  WIDEN(r->foot_pos, in->foot_pos); WIDEN(r->foot_vel, in->foot_vel);
+  WIDEN(r->obj_pos, in->obj_pos); WIDEN(r->obj_quat, in->obj_quat); WIDEN(r->obj_lin, in->obj_lin); WIDEN(r->obj_ang, in->obj_ang);
+  WIDEN(r->obj_timers, in->obj_timers); WIDEN(r->cmd, in->cmd);
+  r->terminated = in->terminated;
+}
+static void gait_io_widen(const lt_gait_io* G, gait_io_r* r) {
+  WIDEN(r->cur_air, G->cur_air); WIDEN(r->cur_con, G->cur_con); WIDEN(r->sensor_last_air, G->sensor_last_air); WIDEN(r->cmd, G->cmd);
+  r->lin_err = G->lin_err; r->ang_err = G->ang_err; WIDEN(r->obj_xy_yaw, G->obj_xy_yaw);
+  r->any_nonzero_cmd = G->any_nonzero_cmd;
+  WIDEN(r->last_step_air, G->last_step_air); WIDEN(r->last_step_con, G->last_step_con); WIDEN(r->valid_last_air, G->valid_last_air);
+  memcpy(r->swinging_in_zero_cmd, G->swinging_in_zero_cmd, sizeof(r->swinging_in_zero_cmd));
+  memcpy(r->valid_prev_contact, G->valid_prev_contact, sizeof(r->valid_prev_contact));
+  WIDEN(r->last_cmd, G->last_cmd); r->step_from_change = G->step_from_change;
+}
+static void gait_io_narrow(const gait_io_r* r, lt_gait_io* G) {
+  NARROW(G->cur_air, r->cur_air); NARROW(G->cur_con, r->cur_con); NARROW(G->sensor_last_air, r->sensor_last_air); NARROW(G->cmd, r->cmd);
+  G->lin_err = (float)r->lin_err; G->ang_err = (float)r->ang_err; NARROW(G->obj_xy_yaw, r->obj_xy_yaw);
+  G->any_nonzero_cmd = r->any_nonzero_cmd;
+  NARROW(G->last_step_air, r->last_step_air); NARROW(G->last_step_con, r->last_step_con); NARROW(G->valid_last_air, r->valid_last_air);
+  memcpy(G->swinging_in_zero_cmd, r->swinging_in_zero_cmd, sizeof(G->swinging_in_zero_cmd));
+  memcpy(G->valid_prev_contact, r->valid_prev_contact, sizeof(G->valid_prev_contact));
+  NARROW(G->last_cmd, r->last_cmd); G->step_from_change = (float)r->step_from_change;
+}
+
 /* rewards.py:158-200 : _update_valid_last_air_contact_time.  Arrays are in gait column order. */
-static void gait_update(const lt_cfg* cfg, lt_gait_io* G) {
+static void gait_update(const lt_cfg* cfg, gait_io_r* G) {
   const real judge = cfg->gait_judge_time;
   real cn = (real)sqrt((double)(G->cmd[0] * G->cmd[0] + G->cmd[1] * G->cmd[1] + G->cmd[2] * G->cmd[2]));
   int nonzero = cn > 0;
@@ -830,7 +899,7 @@ static void gait_update(const lt_cfg* cfg, lt_gait_io* G) {
 static real clampr(real x, real lo, real hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 /* rewards.py:243-346 : _swinging_bonus for the pair (f0, f1) given in gait columns */
-static real gait_swing_bonus(const lt_cfg* cfg, const lt_gait_io* G, int f0, int f1, real step_dt) {
+static real gait_swing_bonus(const lt_cfg* cfg, const gait_io_r* G, int f0, int f1, real step_dt) {
   const real judge = cfg->gait_judge_time, ub = cfg->gait_rwd_upper, lb = cfg->gait_rwd_lower, tol = cfg->gait_tolerance_proportion;
   const real scale = ub / ((real)1.0 / (cfg->gait_soft_min_frequency * (real)2.0));            /* :72,:78 */
   real tbar = (G->cur_air[f0] + G->cur_air[f1]) / 2;
@@ -873,7 +942,7 @@ static real gait_swing_bonus(const lt_cfg* cfg, const lt_gait_io* G, int f0, int
 }
 
 /* rewards.py:116-156 (+ :202-241, :348-368, :371-392).  Returns the gait term and updates the state. */
-float lt_oracle_gait(const lt_cfg* cfg, lt_gait_io* G, float step_dt) {
+static real gait_r(const lt_cfg* cfg, gait_io_r* G, real step_dt) {
   const real judge = cfg->gait_judge_time, ab = cfg->gait_air_bound, cb_ = cfg->gait_contact_bound;
   const real async_judge = judge + cfg->gait_async_tolerance;
   gait_update(cfg, G);
@@ -914,9 +983,16 @@ float lt_oracle_gait(const lt_cfg* cfg, lt_gait_io* G, float step_dt) {
   real stance = (all_stance ? 1 : 0) * cfg->gait_stance_scale;
   return nonzero ? stepping : stance;                                                           /* :153-154 */
 }
+float lt_oracle_gait(const lt_cfg* cfg, lt_gait_io* G, float step_dt) {
+  gait_io_r r;
+  gait_io_widen(G, &r);
+  const real v = gait_r(cfg, &r, step_dt);
+  gait_io_narrow(&r, G);
+  return (float)v;
+}
 
 /* All reward terms of one env from a B3-style record; zero-weight terms are skipped (IsaacLab [DEP]). */
-void lt_oracle_rewards(const lt_cfg* cfg, const lt_term_in* in, lt_gait_io* G, float step_dt, float* terms) {
+static void rewards_r(const lt_cfg* cfg, const term_in_r* in, gait_io_r* G, real step_dt, real* terms) {
   const real* cmd = in->cmd;
   real R0[9];
   quat_to_mat(R0, in->root_quat);
@@ -961,7 +1037,7 @@ void lt_oracle_rewards(const lt_cfg* cfg, const lt_term_in* in, lt_gait_io* G, f
       quat_apply_inv(o, qy, d);
       G->obj_xy_yaw[0] = o[0]; G->obj_xy_yaw[1] = o[1];
     }
-    terms[LT_R_GAIT] = lt_oracle_gait(cfg, G, step_dt);
+    terms[LT_R_GAIT] = gait_r(cfg, G, step_dt);
   }
   if (w[LT_R_TRACK_BASE_HEIGHT] != 0) { real d = in->root_pos[2] - cfg->base_height_target; terms[LT_R_TRACK_BASE_HEIGHT] = d * d; } /* :398-402 */
   if (w[LT_R_BASE_Z_VELOCITY] != 0) terms[LT_R_BASE_Z_VELOCITY] = vb[2] * vb[2];                /* :404-408 */
@@ -1045,9 +1121,19 @@ void lt_oracle_rewards(const lt_cfg* cfg, const lt_term_in* in, lt_gait_io* G, f
     terms[LT_R_OBJECT_DANGEROUS_STATE] = danger ? 1 : 0;
   }
 }
+void lt_oracle_rewards(const lt_cfg* cfg, const lt_term_in* in, lt_gait_io* G, float step_dt, float* terms) {
+  term_in_r r;
+  gait_io_r g;
+  real t[LT_REWARD_SLOTS];
+  term_in_widen(in, &r);
+  gait_io_widen(G, &g);
+  rewards_r(cfg, &r, &g, step_dt, t);
+  gait_io_narrow(&g, G);
+  narrow(terms, t, LT_REWARD_SLOTS);
+}
 
 /* terminations: stock terms [DEP] (cfg locomotion_base_env_cfg.py:296-313) + reference mdp/terminations.py:10-23 */
-int lt_oracle_terminations(const lt_cfg* cfg, const lt_term_in* in, int64_t ep_len, int64_t max_len) {
+static int terminations_r(const lt_cfg* cfg, const term_in_r* in, int64_t ep_len, int64_t max_len) {
   int bits = 0;
   real gz[3] = {0, 0, -1}, gb[3];
   quat_apply_inv(gb, in->root_quat, gz);
@@ -1077,10 +1163,15 @@ int lt_oracle_terminations(const lt_cfg* cfg, const lt_term_in* in, int64_t ep_l
   }
   return bits;
 }
+int lt_oracle_terminations(const lt_cfg* cfg, const lt_term_in* in, int64_t ep_len, int64_t max_len) {
+  term_in_r r;
+  term_in_widen(in, &r);
+  return terminations_r(cfg, &r, ep_len, max_len);
+}
 
 /* object_state_in_robot_frame, reference locotouch/mdp/observations.py:38-91.  `noise16` = 16 uniforms
  * (13 additive + 3 euler) or NULL for the critic flavour. */
-void lt_oracle_object_state_obs(const lt_cfg* cfg, const lt_term_in* in, const float* noise16, float out[13]) {
+static void object_state_obs_r(const lt_cfg* cfg, const term_in_r* in, const float* noise16, real out[13]) {
   real dpos[3], dlin[3], dang[3], s[13], qi[4];
   v3_sub(dpos, in->obj_pos, in->root_pos);
   v3_sub(dlin, in->obj_lin, in->root_lin);
@@ -1104,6 +1195,13 @@ void lt_oracle_object_state_obs(const lt_cfg* cfg, const lt_term_in* in, const f
   }
   for (int i = 0; i < 13; ++i) out[i] = s[i] * cfg->obj_scale[i];                               /* :85-89 */
 }
+void lt_oracle_object_state_obs(const lt_cfg* cfg, const lt_term_in* in, const float* noise16, float out[13]) {
+  term_in_r r;
+  real o[13];
+  term_in_widen(in, &r);
+  object_state_obs_r(cfg, &r, noise16, o);
+  narrow(out, o, 13);
+}
 
 /* ------------------------------------------------------------------------------------------------ */
 /* K7: command term (reference locotouch/mdp/commands.py:517-576 + UniformVelocityCommand [DEP])     */
@@ -1111,8 +1209,9 @@ void lt_oracle_object_state_obs(const lt_cfg* cfg, const lt_term_in* in, const f
 /* explicit-uniform form (pinned by tests/golden/mdp_replay.npz, which replays recorded uniforms through the reference's own
  * _resample_command): ub = bin draws (torch.multinomial by inverse CDF over (p, 1-2p, p)), uv = value draws, ustand = the
  * standing draw, utime = the resampling-period draw [DEP CommandTerm]. */
-void lt_oracle_command_resample_u(const lt_cfg* cfg, const float* P, const float ub[3], const float uv[3], float ustand, float utime,
-                                  float cmd[3], float cmd_buf[3], float* standing, float* time_left) {
+/* P (the command / curriculum parameter table) and the uniforms stay f32 in both builds: the spec defines them as f32 */
+static void command_resample_r(const lt_cfg* cfg, const float* P, const float ub[3], const float uv[3], float ustand, float utime,
+                               real cmd[3], real cmd_buf[3], real* standing, real* time_left) {
   for (int d = 0; d < 3; ++d) {
     real lo = P[2 * d], hi = P[2 * d + 1];
     if (cfg->cmd_multi_sampling && P[12 + d] == 0) {                                            /* commands.py:530-553 */
@@ -1134,19 +1233,32 @@ void lt_oracle_command_resample_u(const lt_cfg* cfg, const float* P, const float
   *time_left = cfg->cmd_resample_time[0] + (real)utime * (cfg->cmd_resample_time[1] - cfg->cmd_resample_time[0]);
   for (int d = 0; d < 3; ++d) cmd_buf[d] = cmd[d];                                              /* :558 */
 }
+void lt_oracle_command_resample_u(const lt_cfg* cfg, const float* P, const float ub[3], const float uv[3], float ustand, float utime,
+                                  float cmd[3], float cmd_buf[3], float* standing, float* time_left) {
+  real c[3], b[3], st, tl;
+  widen(c, cmd, 3); widen(b, cmd_buf, 3); st = *standing; tl = *time_left;
+  command_resample_r(cfg, P, ub, uv, ustand, utime, c, b, &st, &tl);
+  narrow(cmd, c, 3); narrow(cmd_buf, b, 3); *standing = (float)st; *time_left = (float)tl;
+}
 static void command_resample(const lt_cfg* cfg, const float* P, uint64_t seed, uint32_t env, uint64_t step, uint32_t stream,
                              real cmd[3], real cmd_buf[3], real* standing, real* time_left) {
-  float u0[4], u1[4];
+  float u0[4], u1[4]; /* Philox uniforms: f32 by the spec, exact in both builds */
   lt_rng4(seed, env, step, stream, u0);
   lt_rng4(seed, env, step, stream + 1, u1);
   const float ub[3] = {u0[0], u0[2], u1[0]}, uv[3] = {u0[1], u0[3], u1[1]};
-  lt_oracle_command_resample_u(cfg, P, ub, uv, u1[2], u1[3], cmd, cmd_buf, standing, time_left);
+  command_resample_r(cfg, P, ub, uv, u1[2], u1[3], cmd, cmd_buf, standing, time_left);
 }
 /* commands.py:561-576 + base class standing zero */
-void lt_oracle_command_update(int64_t ep_len, int zero_steps, const float buf[3], int standing, float cmd[3]) {
-  if (ep_len < zero_steps) for (int d = 0; d < 3; ++d) cmd[d] = buf[d] * 0.0f;
+static void command_update_r(int64_t ep_len, int zero_steps, const real buf[3], int standing, real cmd[3]) {
+  if (ep_len < zero_steps) for (int d = 0; d < 3; ++d) cmd[d] = buf[d] * (real)0;
   if (ep_len == zero_steps) for (int d = 0; d < 3; ++d) cmd[d] = buf[d];
-  if (standing) for (int d = 0; d < 3; ++d) cmd[d] = 0.0f;
+  if (standing) for (int d = 0; d < 3; ++d) cmd[d] = 0;
+}
+void lt_oracle_command_update(int64_t ep_len, int zero_steps, const float buf[3], int standing, float cmd[3]) {
+  real b[3], c[3];
+  widen(b, buf, 3); widen(c, cmd, 3);
+  command_update_r(ep_len, zero_steps, b, standing, c);
+  narrow(cmd, c, 3);
 }
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -1403,7 +1515,7 @@ enum {
 static void startup_env(const lt_cfg* cfg, env_t* E, uint32_t env, const float* sizes) {
   /* startup events: trunk mass (locomotion_base_env_cfg.py:224-232), foot material (:233-244 + teacher override),
    * and the per-env cylinder size (rand_cylinder_transport_teacher_env_cfg.py:21-27; seeded here, quirk Q2) */
-  float u[4];
+  float u[4]; /* Philox uniforms (f32 by the spec) */
   const uint64_t st = ~(uint64_t)0;
   lt_rng4(cfg->seed, env, st, RS_STARTUP, u);
   E->trunk_mass_add = lt_lerp(cfg->trunk_mass_add, u[0]);
@@ -1413,7 +1525,7 @@ static void startup_env(const lt_cfg* cfg, env_t* E, uint32_t env, const float* 
   for (int l = 0; l < 4; ++l) {
     lt_rng4(cfg->seed, env, st, RS_STARTUP + 0x10 + l, u);
     if (cfg->foot_material_buckets > 0) { /* bucketed materials [DEP randomize_rigid_body_material]: pool entry b = the draw keyed by b */
-      int b = (int)(u[0] * (float)cfg->foot_material_buckets);
+      int b = (int)(u[0] * (float)cfg->foot_material_buckets); /* bucket index in f32, as the spec computes it */
       if (b > cfg->foot_material_buckets - 1) b = cfg->foot_material_buckets - 1;
       lt_rng4(cfg->seed, (uint32_t)b, st, RS_BUCKET_FEET, u);
     }
@@ -1425,20 +1537,26 @@ static void startup_env(const lt_cfg* cfg, env_t* E, uint32_t env, const float* 
 
 /* E3 randomize_friction_restitution.__call__ (events.py:160-196): (static, dynamic, restitution) = lo + u * (hi - lo), then
  * make_consistent => dynamic = min(static, dynamic).  Explicit-uniform form, pinned by tests/golden/mdp_replay.npz. */
-void lt_oracle_material_u(const float range_static[2], const float range_dynamic[2], const float range_restitution[2],
-                          const float u[3], float out[3]) {
+static void material_r(const float range_static[2], const float range_dynamic[2], const float range_restitution[2],
+                       const float u[3], real out[3]) {
   out[0] = lt_lerp(range_static, u[0]);
   out[1] = lt_lerp(range_dynamic, u[1]);
   out[2] = lt_lerp(range_restitution, u[2]);
   if (out[0] < out[1]) out[1] = out[0];
 }
+void lt_oracle_material_u(const float range_static[2], const float range_dynamic[2], const float range_restitution[2],
+                          const float u[3], float out[3]) {
+  real o[3];
+  material_r(range_static, range_dynamic, range_restitution, u, o);
+  narrow(out, o, 3);
+}
 /* E6 ResetObjectStateUniform.__call__ (events.py:85-109): offset added in WORLD axes (:98), + height/2 (:99), orientation
  * = robot quat (x) euler(roll, pitch, yaw) (:100-101), velocity = robot root velocity (+ zero-range samples) (:104-105).
  * cfg->obj_reset_robot_frame selects the function variant reset_object_state_uniform (:13-53): offset rotated by the robot quat.
  * Explicit-uniform form, pinned by tests/golden/mdp_replay.npz. */
-void lt_oracle_reset_object_u(const lt_cfg* cfg, const float root_pos[3], const float root_quat[4], const float root_lin[3],
-                              const float root_ang[3], float obj_length, const float u_pose[6], float pos[3], float quat[4],
-                              float lin[3], float ang[3]) {
+static void reset_object_r(const lt_cfg* cfg, const real root_pos[3], const real root_quat[4], const real root_lin[3],
+                           const real root_ang[3], real obj_length, const float u_pose[6], real pos[3], real quat[4],
+                           real lin[3], real ang[3]) {
   real d[3], dw[3];
   for (int c = 0; c < 3; ++c) d[c] = lt_lerp(cfg->obj_reset_pos[c], u_pose[c]);
   d[2] += obj_length / 2;
@@ -1450,9 +1568,17 @@ void lt_oracle_reset_object_u(const lt_cfg* cfg, const float root_pos[3], const 
   quat_mul(quat, root_quat, dq);
   for (int c = 0; c < 3; ++c) { lin[c] = root_lin[c]; ang[c] = root_ang[c]; }
 }
+void lt_oracle_reset_object_u(const lt_cfg* cfg, const float root_pos[3], const float root_quat[4], const float root_lin[3],
+                              const float root_ang[3], float obj_length, const float u_pose[6], float pos[3], float quat[4],
+                              float lin[3], float ang[3]) {
+  real rp[3], rq[4], rl[3], ra[3], op[3], oq[4], ol[3], oa[3];
+  widen(rp, root_pos, 3); widen(rq, root_quat, 4); widen(rl, root_lin, 3); widen(ra, root_ang, 3);
+  reset_object_r(cfg, rp, rq, rl, ra, obj_length, u_pose, op, oq, ol, oa);
+  narrow(pos, op, 3); narrow(quat, oq, 4); narrow(lin, ol, 3); narrow(ang, oa, 3);
+}
 
 static void reset_env(const lt_cfg* cfg, const float* P, env_t* E, uint32_t env, uint64_t step, int has_object) {
-  float u[4], w[4];
+  float u[4], w[4]; /* Philox uniforms (f32 by the spec) */
   /* E4 reset_root_state_uniform [DEP], params locomotion_base_env_cfg.py:249-267 / teacher :144-160 */
   lt_rng4(cfg->seed, env, step, RS_RESET_ROOT, u);
   E->root_pos[0] = lt_lerp(cfg->reset_root_pos[0], u[0]);
@@ -1485,7 +1611,7 @@ static void reset_env(const lt_cfg* cfg, const float* P, env_t* E, uint32_t env,
     /* E3 randomize_friction_restitution (events.py:160-196, make_consistent) and E2 object material */
     lt_rng4(cfg->seed, env, step, RS_RESET_MAT, u);
     if (cfg->obj_material_buckets > 0) { /* E2: the object's (friction, restitution) come from a pool of obj_material_buckets entries */
-      float ub[4];
+      float ub[4]; /* Philox uniforms; the bucket index is computed in f32 as the spec does */
       int b = (int)(u[2] * (float)cfg->obj_material_buckets);
       if (b > cfg->obj_material_buckets - 1) b = cfg->obj_material_buckets - 1;
       lt_rng4(cfg->seed, (uint32_t)b, ~(uint64_t)0, RS_BUCKET_OBJ, ub);
@@ -1493,20 +1619,20 @@ static void reset_env(const lt_cfg* cfg, const float* P, env_t* E, uint32_t env,
     }
     {
       /* the dynamic-friction range of both cfgs is (1, 1): its draw does not matter (object_transport_teacher_env_cfg.py:121-143) */
-      const float one[2] = {1.0f, 1.0f};
+      const float one[2] = {1.0f, 1.0f}; /* a cfg-style range and Philox uniforms: f32 by the spec */
       const float ut[3] = {u[0], 0.0f, u[1]}, uo[3] = {u[2], 0.0f, u[3]};
-      float m[3];
-      lt_oracle_material_u(cfg->trunk_friction, one, cfg->trunk_restitution, ut, m);
+      real m[3];
+      material_r(cfg->trunk_friction, one, cfg->trunk_restitution, ut, m);
       E->trunk_mu = m[1]; E->trunk_rest = m[2];       /* the contact law takes the consistent (dynamic) coefficient */
-      lt_oracle_material_u(cfg->obj_friction, one, cfg->obj_restitution, uo, m);
+      material_r(cfg->obj_friction, one, cfg->obj_restitution, uo, m);
       E->obj_mu = m[1]; E->obj_rest = m[2];
     }
     /* E6 ResetObjectStateUniform.__call__ (events.py:85-109): world-axis offset, + length/2, robot velocity */
     lt_rng4(cfg->seed, env, step, RS_RESET_OBJ, u);
     lt_rng4(cfg->seed, env, step, RS_RESET_OBJ + 1, w);
     {
-      const float up[6] = {u[0], u[1], u[2], w[0], w[1], w[2]};
-      lt_oracle_reset_object_u(cfg, E->root_pos, E->root_quat, E->root_lin, E->root_ang, E->obj_length, up, E->obj_pos, E->obj_quat,
+      const float up[6] = {u[0], u[1], u[2], w[0], w[1], w[2]}; /* Philox uniforms */
+      reset_object_r(cfg, E->root_pos, E->root_quat, E->root_lin, E->root_ang, E->obj_length, up, E->obj_pos, E->obj_quat,
                                E->obj_lin, E->obj_ang);
     }
     /* E1 object mass: default 1.0 + U (operation add on the default) */
@@ -1528,13 +1654,14 @@ static void reset_env(const lt_cfg* cfg, const float* P, env_t* E, uint32_t env,
 /* ------------------------------------------------------------------------------------------------ */
 /* newest frame of every term, policy (noisy) and critic flavours; term order locomotion_base_env_cfg.py:74-109
  * then object_state (object_transport_teacher_env_cfg.py:37-43).  Noise model: AdditiveUniformNoise [DEP]. */
-static int obs_frame(const lt_cfg* cfg, const env_t* E, uint32_t env, uint64_t step, int has_object, float* pol, float* cri) {
+static void term_in_from_env(const env_t* E, int terminated, term_in_r* in);
+static int obs_frame(const lt_cfg* cfg, const env_t* E, uint32_t env, uint64_t step, int has_object, real* pol, real* cri) {
   real R0[9], wb[3], gb[3], gz[3] = {0, 0, -1};
   quat_to_mat(R0, E->root_quat);
   m3_tmulv(wb, R0, E->root_ang);
   m3_tmulv(gb, R0, gz);
   int n = 0;
-  float ua[4], ug[4], uj[4][4], uv[4][4];
+  float ua[4], ug[4], uj[4][4], uv[4][4]; /* Philox uniforms (f32 by the spec) */
   lt_rng4(cfg->seed, env, step, RS_NOISE_BASE, ua);
   lt_rng4(cfg->seed, env, step, RS_NOISE_BASE + 1, ug);
   for (int l = 0; l < 4; ++l) { lt_rng4(cfg->seed, env, step, RS_NOISE_JPOS + l, uj[l]); lt_rng4(cfg->seed, env, step, RS_NOISE_JVEL + l, uv[l]); }
@@ -1548,17 +1675,12 @@ static int obs_frame(const lt_cfg* cfg, const env_t* E, uint32_t env, uint64_t s
   for (int k = 0; k < 3; ++k) for (int l = 0; l < 4; ++l) { pol[n] = E->act_raw[l][k]; cri[n] = E->act_raw[l][k]; ++n; }
 #undef NZ
   if (has_object) {
-    lt_term_in in;
-    memset(&in, 0, sizeof(in));
-    memcpy(in.root_pos, E->root_pos, sizeof(in.root_pos)); memcpy(in.root_quat, E->root_quat, sizeof(in.root_quat));
-    memcpy(in.root_lin, E->root_lin, sizeof(in.root_lin)); memcpy(in.root_ang, E->root_ang, sizeof(in.root_ang));
-    memcpy(in.obj_pos, E->obj_pos, sizeof(in.obj_pos)); memcpy(in.obj_quat, E->obj_quat, sizeof(in.obj_quat));
-    memcpy(in.obj_lin, E->obj_lin, sizeof(in.obj_lin)); memcpy(in.obj_ang, E->obj_ang, sizeof(in.obj_ang));
-    memcpy(in.obj_timers, E->obj_timers, sizeof(in.obj_timers));
-    float u16[16];
+    term_in_r in;
+    term_in_from_env(E, 0, &in);
+    float u16[16]; /* Philox uniforms */
     for (int b = 0; b < 4; ++b) lt_rng4(cfg->seed, env, step, RS_NOISE_OBJ + b, u16 + 4 * b);
-    lt_oracle_object_state_obs(cfg, &in, noisy ? u16 : NULL, pol + n);
-    lt_oracle_object_state_obs(cfg, &in, NULL, cri + n);
+    object_state_obs_r(cfg, &in, noisy ? u16 : NULL, pol + n);
+    object_state_obs_r(cfg, &in, NULL, cri + n);
     n += 13;
   }
   return n;
@@ -1581,7 +1703,7 @@ void lt_oracle_obs_push(const int* term_dims, int nterms, int hist, const float*
 /* ------------------------------------------------------------------------------------------------ */
 /* full env step                                                                                      */
 /* ------------------------------------------------------------------------------------------------ */
-static void term_in_from_env(const env_t* E, int terminated, lt_term_in* in) {
+static void term_in_from_env(const env_t* E, int terminated, term_in_r* in) {
   memset(in, 0, sizeof(*in));
   memcpy(in->root_pos, E->root_pos, sizeof(in->root_pos)); memcpy(in->root_quat, E->root_quat, sizeof(in->root_quat));
   memcpy(in->root_lin, E->root_lin, sizeof(in->root_lin)); memcpy(in->root_ang, E->root_ang, sizeof(in->root_ang));
@@ -1595,7 +1717,7 @@ static void term_in_from_env(const env_t* E, int terminated, lt_term_in* in) {
   memcpy(in->obj_timers, E->obj_timers, sizeof(in->obj_timers)); memcpy(in->cmd, E->cmd, sizeof(in->cmd));
   in->terminated = terminated;
 }
-static void gait_io_from_env(const env_t* E, lt_gait_io* G) {
+static void gait_io_from_env(const env_t* E, gait_io_r* G) {
   memset(G, 0, sizeof(*G));
   for (int f = 0; f < 4; ++f) {
     int l = k_gait_order[f];
@@ -1607,7 +1729,7 @@ static void gait_io_from_env(const env_t* E, lt_gait_io* G) {
   for (int c = 0; c < 3; ++c) G->last_cmd[c] = E->gait_cmd[c];
   G->step_from_change = E->gait_step_from_change;
 }
-static void gait_io_to_env(const lt_gait_io* G, env_t* E) {
+static void gait_io_to_env(const gait_io_r* G, env_t* E) {
   for (int f = 0; f < 4; ++f) {
     int l = k_gait_order[f];
     E->gait_last_air[l] = G->last_step_air[f]; E->gait_last_con[l] = G->last_step_con[f];
@@ -1637,9 +1759,9 @@ static void step_one(const lt_cfg* cfg, void* arena, const lt_layout* L, const f
   int terminated = 0, time_out = 0, bits = 0, reset = 0;
   if (mode == LT_ORACLE_MODE_STEP) {
     /* 1. action term (A1) */
-    float raw[12], prev[12], prev2[12];
+    real raw[12], prev[12], prev2[12];
     for (int l = 0; l < 4; ++l) for (int k = 0; k < 3; ++k) { raw[k * 4 + l] = E.act_raw[l][k]; prev[k * 4 + l] = E.act_prev[l][k]; prev2[k * 4 + l] = E.act_prev2[l][k]; }
-    lt_oracle_process_action(cfg, actions + e * 12, raw, prev, prev2);
+    process_action_r(cfg, actions + e * 12, raw, prev, prev2);
     for (int l = 0; l < 4; ++l) for (int k = 0; k < 3; ++k) { E.act_raw[l][k] = raw[k * 4 + l]; E.act_prev[l][k] = prev[k * 4 + l]; E.act_prev2[l][k] = prev2[k * 4 + l]; }
     /* 2. decimation x (PD -> physics -> sensors) */
     /* tactile ContactSensor cadence [DEP] (update_period 0.025 s, object_transport_student_env_cfg.py:195-201): the taxel
@@ -1667,9 +1789,9 @@ static void step_one(const lt_cfg* cfg, void* arena, const lt_layout* L, const f
   }
   if (mode != LT_ORACLE_MODE_RESET_ALL) {
     /* 4. terminations */
-    lt_term_in in;
+    term_in_r in;
     term_in_from_env(&E, 0, &in);
-    bits = lt_oracle_terminations(cfg, &in, E.ep_len, max_len);
+    bits = terminations_r(cfg, &in, E.ep_len, max_len);
     /* a termination the caller requested on the state the previous step left (include/lt_env.h, LT_T_USER) */
     if (mode == LT_ORACLE_MODE_STEP && ((((const int32_t*)((char*)arena + L->off_term_bits))[e] >> LT_TERM_REQUEST_BIT) & 1)) bits |= 1 << LT_T_USER;
     if (mode == LT_ORACLE_MODE_STEP && ((((const int32_t*)((char*)arena + L->off_term_bits))[e] >> LT_TIMEOUT_REQUEST_BIT) & 1)) bits |= 1 << LT_T_USER_TIME_OUT;
@@ -1679,11 +1801,11 @@ static void step_one(const lt_cfg* cfg, void* arena, const lt_layout* L, const f
     /* the terms-only hook takes `terminated` (for the alive term) from the arena */
     in.terminated = mode == LT_ORACLE_MODE_TERMS ? ((uint8_t*)arena + L->off_terminated)[e] : terminated;
     /* 5. rewards */
-    lt_gait_io G;
+    gait_io_r G;
     gait_io_from_env(&E, &G);
     G.any_nonzero_cmd = any_nonzero_cmd;
-    float terms[LT_REWARD_SLOTS];
-    lt_oracle_rewards(cfg, &in, &G, step_dt, terms);
+    real terms[LT_REWARD_SLOTS];
+    rewards_r(cfg, &in, &G, step_dt, terms);
     gait_io_to_env(&G, &E);
     real rew = 0;
     for (int i = 0; i < LT_NUM_REWARD_TERMS; ++i) {
@@ -1719,8 +1841,8 @@ static void step_one(const lt_cfg* cfg, void* arena, const lt_layout* L, const f
       quat_apply_inv(vb, E.root_quat, E.root_lin);
       quat_apply_inv(wb, E.root_quat, E.root_ang);
       const real ex = E.cmd[0] - vb[0], ey = E.cmd[1] - vb[1];
-      E.m_exy = (real)sqrtf((float)(ex * ex + ey * ey));
-      E.m_eyaw = (real)fabsf((float)(E.cmd[2] - wb[2]));
+      E.m_exy = (real)sqrt((double)(ex * ex + ey * ey));
+      E.m_eyaw = (real)fabs((double)(E.cmd[2] - wb[2]));
       const real mean = (real)0.25 * (((E.foot_last_air[0] + E.foot_last_air[1]) + E.foot_last_air[2]) + E.foot_last_air[3]);
       real v = 0;
       for (int l = 0; l < 4; ++l) v += (E.foot_last_air[l] - mean) * (E.foot_last_air[l] - mean);
@@ -1730,13 +1852,13 @@ static void step_one(const lt_cfg* cfg, void* arena, const lt_layout* L, const f
     if (E.cmd_time_left <= 0)
       command_resample(cfg, P, cfg->seed, EKEY(cfg, e), step, RS_CMD_TIMER, E.cmd, E.cmd_buf, &E.cmd_standing, &E.cmd_time_left);
     {
-      float c[3] = {E.cmd[0], E.cmd[1], E.cmd[2]}, b[3] = {E.cmd_buf[0], E.cmd_buf[1], E.cmd_buf[2]};
-      if (cfg->cmd_multi_sampling) lt_oracle_command_update(E.ep_len, (int)P[15], b, E.cmd_standing != 0, c);
+      real c[3] = {E.cmd[0], E.cmd[1], E.cmd[2]}, b[3] = {E.cmd_buf[0], E.cmd_buf[1], E.cmd_buf[2]};
+      if (cfg->cmd_multi_sampling) command_update_r(E.ep_len, (int)P[15], b, E.cmd_standing != 0, c);
       else if (E.cmd_standing != 0) c[0] = c[1] = c[2] = 0;
       E.cmd[0] = c[0]; E.cmd[1] = c[1]; E.cmd[2] = c[2];
     }
     /* 8. interval events: push_by_setting_velocity [DEP] */
-    float u[4], w[4];
+    float u[4], w[4]; /* Philox uniforms (f32 by the spec) */
     E.push_robot_left -= step_dt;
     if (E.push_robot_left < (real)1e-6) {
       lt_rng4(cfg->seed, EKEY(cfg, e), step, RS_PUSH_ROBOT, u);
@@ -1755,10 +1877,13 @@ static void step_one(const lt_cfg* cfg, void* arena, const lt_layout* L, const f
     }
   }
   /* 9. observations (the terms-only hook and reset-all fill every history slot with the current frame) */
-  float pol[64], cri[64];
+  real polr[64], crir[64];
+  float pol[64], cri[64]; /* the frame as the f32 observation rows store it */
   int dims[8];
   int nt = task_term_dims(cfg, dims);
-  obs_frame(cfg, &E, EKEY(cfg, e), step, has_object, pol, cri);
+  const int nf = obs_frame(cfg, &E, EKEY(cfg, e), step, has_object, polr, crir);
+  narrow(pol, polr, nf);
+  narrow(cri, crir, nf);
   float* rp = (float*)((char*)arena + L->off_obs_policy) + e * L->obs_dim;
   float* rc = (float*)((char*)arena + L->off_obs_critic) + e * L->obs_dim;
   int fill = reset || mode != LT_ORACLE_MODE_STEP;
@@ -1784,10 +1909,10 @@ static int any_nonzero(void* arena, const lt_layout* L) {
 /* K10: tactile observation (student tasks)                                                          */
 /* ------------------------------------------------------------------------------------------------ */
 /* cumulative integral of the piecewise-linear line pressure from the first sample to arc length s */
-static float pressure_integral(const float p[4], float dl, float s) {
-  float acc = 0;
+static real pressure_integral(const real p[4], real dl, real s) {
+  real acc = 0;
   for (int k = 0; k < 3; ++k) {
-    float t = s - (float)k * dl;
+    real t = s - (real)k * dl;
     t = t < 0 ? 0 : (t > dl ? dl : t);
     acc += t * (p[k] + (p[k + 1] - p[k]) * t / (2 * dl));
   }
@@ -1799,38 +1924,44 @@ static float pressure_integral(const float p[4], float dl, float s) {
  * as a 4-sample line, so a taxel's force is the integral, over the part of the contact line inside the taxel's collision box
  * (generate_locotouch_urdf.py:4-8, locotouch.urdf:816-821), of the piecewise-linear line pressure whose cell integrals are
  * the sample forces (end cells are half cells).  Engine restatement: parity unpinned (no PhysX taxel-force fixture exists). */
-void lt_oracle_taxel_forces(const float x[4], const float y[4], const float f_in[4], float* out) {
-  float f[4];
+static void taxel_forces_r(const real x[4], const real y[4], const real f_in[4], real* out) {
+  real f[4];
   for (int k = 0; k < 4; ++k) f[k] = f_in[k] > 0 ? f_in[k] : 0;
-  const float dx = x[3] - x[0], dy = y[3] - y[0];
-  const float len = sqrtf(dx * dx + dy * dy);
-  const float ftot = f[0] + f[1] + f[2] + f[3];
+  const real dx = x[3] - x[0], dy = y[3] - y[0];
+  const real len = (real)sqrt((double)(dx * dx + dy * dy));
+  const real ftot = f[0] + f[1] + f[2] + f[3];
   for (int t = 0; t < LT_TAXEL_ROWS * LT_TAXEL_COLS; ++t) {
     const int row = t / LT_TAXEL_COLS, col = t - row * LT_TAXEL_COLS;
-    const float cx = LT_TAXEL_X0 - LT_TAXEL_DX * (float)row, cy = LT_TAXEL_Y0 - LT_TAXEL_DY * (float)col;
+    const real cx = LT_TAXEL_X0 - LT_TAXEL_DX * (real)row, cy = LT_TAXEL_Y0 - LT_TAXEL_DY * (real)col;
     out[t] = 0;
     if (!(ftot > 0)) continue;
-    if (len < 1e-6f) {
-      if (fabsf(x[0] - cx) <= LT_TAXEL_HALF_X && fabsf(y[0] - cy) <= LT_TAXEL_HALF_Y) out[t] = ftot;
+    if (len < (real)1e-6f) {
+      if ((real)fabs(x[0] - cx) <= LT_TAXEL_HALF_X && (real)fabs(y[0] - cy) <= LT_TAXEL_HALF_Y) out[t] = ftot;
       continue;
     }
-    float t0 = 0, t1 = 1;
-    const float pp[2] = {x[0] - cx, y[0] - cy}, dd[2] = {dx, dy}, hh[2] = {LT_TAXEL_HALF_X, LT_TAXEL_HALF_Y};
+    real t0 = 0, t1 = 1;
+    const real pp[2] = {x[0] - cx, y[0] - cy}, dd[2] = {dx, dy}, hh[2] = {LT_TAXEL_HALF_X, LT_TAXEL_HALF_Y};
     int miss = 0;
     for (int ax = 0; ax < 2 && !miss; ++ax) {
-      if (fabsf(dd[ax]) < 1e-9f) { if (fabsf(pp[ax]) > hh[ax]) miss = 1; }
+      if ((real)fabs(dd[ax]) < (real)1e-9f) { if ((real)fabs(pp[ax]) > hh[ax]) miss = 1; }
       else {
-        float ta = (-hh[ax] - pp[ax]) / dd[ax], tb = (hh[ax] - pp[ax]) / dd[ax];
-        if (ta > tb) { float tt = ta; ta = tb; tb = tt; }
+        real ta = (-hh[ax] - pp[ax]) / dd[ax], tb = (hh[ax] - pp[ax]) / dd[ax];
+        if (ta > tb) { real tt = ta; ta = tb; tb = tt; }
         if (ta > t0) t0 = ta;
         if (tb < t1) t1 = tb;
       }
     }
     if (miss || !(t1 > t0)) continue;
-    const float dl = len / 3;
-    const float p[4] = {f[0] / (0.5f * dl), f[1] / dl, f[2] / dl, f[3] / (0.5f * dl)};
+    const real dl = len / 3;
+    const real p[4] = {f[0] / ((real)0.5 * dl), f[1] / dl, f[2] / dl, f[3] / ((real)0.5 * dl)};
     out[t] = pressure_integral(p, dl, t1 * len) - pressure_integral(p, dl, t0 * len);
   }
+}
+void lt_oracle_taxel_forces(const float x[4], const float y[4], const float f_in[4], float* out) {
+  real xr[4], yr[4], fr[4], o[LT_TAXEL_ROWS * LT_TAXEL_COLS];
+  widen(xr, x, 4); widen(yr, y, 4); widen(fr, f_in, 4);
+  taxel_forces_r(xr, yr, fr, o);
+  narrow(out, o, LT_TAXEL_ROWS * LT_TAXEL_COLS);
 }
 
 /* BinaryTactileSignals with explicit uniforms (reference mdp/observations.py:121-126 thresholds, :154-158 contact map,
@@ -1839,7 +1970,7 @@ void lt_oracle_tactile_signals_u(const lt_cfg* cfg, const float* forces, const f
                                  float* out) {
   const int nt = LT_TAXEL_ROWS * LT_TAXEL_COLS;
   for (int t = 0; t < nt; ++t) {
-    const float n_min = -cfg->tactile_threshold_noise, n_max = cfg->tactile_threshold_noise;
+    const float n_min = -cfg->tactile_threshold_noise, n_max = cfg->tactile_threshold_noise; /* f32 as the channels below */
     const float thr = cfg->tactile_threshold + (u_thr[t] * (n_max - n_min) + n_min);   /* :126 */
     int contact = forces[t] > thr;                                                       /* :158 */
     if (cfg->tactile_dropout_prob > 0 && contact && u_drop[t] < cfg->tactile_dropout_prob) contact = 0;   /* :170-175 */
@@ -1855,6 +1986,8 @@ void lt_oracle_tactile_signals_u(const lt_cfg* cfg, const float* forces, const f
  * get_normalized_forces (:199-203), compute_min_max_normalized_signals (:205-222), compute_discretized_signals (:224-235).
  * Uniforms, each [221]: u_thr (construction), u_drop, u_dropf, u_add, u_addf, u_noise, u_small, u_level.  The reference draws the
  * masked ones only for the selected taxels; here they are indexed by taxel (the golden generator scatters its tape accordingly). */
+/* f32 in both builds: the reference's TactileSignals classes are f32 torch ops on the f32 net forces PhysX reports (the
+ * observation spec), pinned to f32 rounding by tests/golden; the forces reach them rounded to f32 */
 void lt_oracle_tactile_channels_u(const lt_cfg* cfg, int original, const float* forces, const float* u_thr, const float* u_drop,
                                   const float* u_dropf, const float* u_add, const float* u_addf, const float* u_noise,
                                   const float* u_small, const float* u_level, float* contact_out, float* norm_out, float* minmax_out,
@@ -1921,13 +2054,16 @@ static void tactile_pass(const lt_cfg* cfg, void* arena, const lt_layout* L) {
   const int64_t blk = L->npad * (int64_t)LT_TACTILE_WIDE_DIM;
   const int dim = (cfg->tactile_format == LT_TACTILE_PROCESSED || cfg->tactile_format == LT_TACTILE_ORIGINAL) ? LT_TACTILE_WIDE_DIM : LT_TACTILE_DIM;
   for (int64_t e = 0; e < L->n; ++e) {
-    float x[4], y[4], f[4], forces[NT], ut[NT + 4], U[7][NT], u[4];
+    real x[4], y[4], f[4], forces_r[NT];
+    float forces[NT];                 /* what the f32 TactileSignals classes read (lt_oracle_tactile_channels_u) */
+    float ut[NT + 4], U[7][NT], u[4]; /* Philox uniforms */
     for (int k = 0; k < 4; ++k) {
       x[k] = lt_quad(arena, L, LT_F_PLATE_SAMPLES, 0)[e * 4 + k];
       y[k] = lt_quad(arena, L, LT_F_PLATE_SAMPLES, 1)[e * 4 + k];
       f[k] = lt_quad(arena, L, LT_F_PLATE_SAMPLES, 2)[e * 4 + k];
     }
-    lt_oracle_taxel_forces(x, y, f, forces);
+    taxel_forces_r(x, y, f, forces_r);
+    narrow(forces, forces_r, NT);
     for (int term = 0; term < 3; ++term) {
       if (term > 0 && !(cfg->tactile_aux_groups & term)) continue;
       /* stream ids: thresholds RS_TACTILE_THR + 0x40 term + taxel / 4 (startup key); per step RS_TACTILE + 0x200 term + 2 taxel
@@ -2011,6 +2147,8 @@ int lt_oracle_eval_terms(const lt_cfg* cfg, void* arena) {
   for (int64_t e = 0; e < L.n; ++e) step_one(cfg, arena, &L, NULL, e, step, nz, LT_ORACLE_MODE_TERMS);
   return 0;
 }
+
+int lt_oracle_real_bytes(void) { return (int)sizeof(real); }
 
 int64_t lt_oracle_state_bytes(const lt_cfg* cfg) {
   lt_layout L;

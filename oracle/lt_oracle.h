@@ -49,6 +49,8 @@ typedef struct lt_gait_io {
 } lt_gait_io;
 
 int lt_oracle_obs_dim(const lt_cfg* cfg);
+/* sizeof the oracle's working precision: 4 for the default build, 8 for the -DLT_REAL=double reference build */
+int lt_oracle_real_bytes(void);
 int64_t lt_oracle_state_bytes(const lt_cfg* cfg);
 int lt_oracle_reset_all(const lt_cfg* cfg, void* arena);
 int lt_oracle_step(const lt_cfg* cfg, void* arena, const float* actions, int nthreads);

@@ -1,10 +1,15 @@
 """ctypes loader for the CPU oracle (oracle/_build/liblt_oracle.so) - test infrastructure only.
 
+`load("f64")` / `OracleEnv(cfg, precision="f64")` use liblt_oracle_f64.so: the same source built with every continuous
+quantity in double (-DLT_REAL=double) behind the same f32 ABI and arena, a high-precision reference for one step.
+
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
+import inspect
 import os
 import subprocess
 
@@ -14,6 +19,8 @@ from locotouch_amd import _abi
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.path.join(REPO, "oracle", "_build", "liblt_oracle.so")
+ORACLE_SOS = {"f32": ORACLE_SO, "f64": os.path.join(REPO, "oracle", "_build", "liblt_oracle_f64.so")}
+PRECISIONS = tuple(ORACLE_SOS)
 
 f32 = ctypes.c_float
 i32 = ctypes.c_int32
@@ -37,17 +44,19 @@ class GaitIO(ctypes.Structure):
                 ("step_from_change", f32)]
 
 
-_lib = None
+_libs: dict = {}
 
 
-def load() -> ctypes.CDLL:
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(ORACLE_SO) or os.path.getmtime(ORACLE_SO) < os.path.getmtime(os.path.join(REPO, "oracle", "lt_oracle.c")):
+def load(precision: str = "f32") -> ctypes.CDLL:
+    if precision in _libs:
+        return _libs[precision]
+    so = ORACLE_SOS[precision]
+    src = os.path.join(REPO, "oracle", "lt_oracle.c")
+    if not all(os.path.exists(p) and os.path.getmtime(p) >= os.path.getmtime(src) for p in ORACLE_SOS.values()):
         subprocess.run(["make", "-C", os.path.join(REPO, "oracle")], check=True, stdout=subprocess.DEVNULL)
-    lib = ctypes.CDLL(ORACLE_SO)
+    lib = ctypes.CDLL(so)
     P = ctypes.POINTER
+    lib.lt_oracle_real_bytes.argtypes = []
     lib.lt_oracle_obs_dim.argtypes = [P(_abi.LtCfg)]
     lib.lt_oracle_state_bytes.argtypes = [P(_abi.LtCfg)]
     lib.lt_oracle_state_bytes.restype = ctypes.c_int64
@@ -74,8 +83,23 @@ def load() -> ctypes.CDLL:
     lib.lt_oracle_gate_on_sums.argtypes = [P(_abi.LtCfg), P(f32), P(f32), f32, ctypes.c_int, ctypes.c_int, P(i32)]
     lib.lt_oracle_curriculum_apply_global.argtypes = [P(_abi.LtCfg), ctypes.c_void_p, P(f32), ctypes.c_int, ctypes.c_int64]
     lib.lt_oracle_obs_push.argtypes = [P(i32), ctypes.c_int, ctypes.c_int, P(f32), ctypes.c_int, P(f32)]
-    _lib = lib
+    _libs[precision] = lib
     return lib
+
+
+def f64_twin(test):
+    """The same test against the f64 oracle build, as a test of its own (`<name>_f64`): `test` takes `precision="f32"` as its
+    last, defaulted argument, which pytest leaves alone, so the f32 test keeps its id and its fixtures / parametrization."""
+    sig = inspect.signature(test)
+    assert "precision" in sig.parameters, test.__name__
+
+    @functools.wraps(test)
+    def twin(*args, **kw):
+        return test(*args, **kw, precision="f64")
+
+    twin.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != "precision"])
+    twin.__name__ = twin.__qualname__ = test.__name__ + "_f64"
+    return twin
 
 
 def fptr(a: np.ndarray):
@@ -86,9 +110,10 @@ def fptr(a: np.ndarray):
 class OracleEnv:
     """Whole-env oracle on a host arena with the device layout (include/lt_layout.h)."""
 
-    def __init__(self, cfg: _abi.LtCfg):
+    def __init__(self, cfg: _abi.LtCfg, precision: str = "f32"):
         self.cfg = cfg.copy()
-        self.lib = load()
+        self.precision = precision
+        self.lib = load(precision)
         self.nbytes = self.lib.lt_oracle_state_bytes(ctypes.byref(self.cfg))
         self.arena = np.zeros(self.nbytes, dtype=np.uint8)
 

@@ -15,18 +15,20 @@ from tests import oracle_lib
 class OracleVecEnv:
     num_actions = 12
 
-    def __init__(self, task_id: str, num_envs: int | None = None, seed: int = 42, cfg: "_abi.LtCfg | None" = None, object_sizes=None):
-        """`cfg`: a complete lt_cfg (e.g. translated from the reference cfg tree) instead of the registration's preset."""
+    def __init__(self, task_id: str, num_envs: int | None = None, seed: int = 42, cfg: "_abi.LtCfg | None" = None, object_sizes=None,
+                 precision: str = "f32"):
+        """`cfg`: a complete lt_cfg (e.g. translated from the reference cfg tree) instead of the registration's preset.
+        `precision`: the oracle build (oracle_lib.load)."""
         self.cfg = cfg.copy() if cfg is not None else _abi.preset_cfg(task_id, num_envs=num_envs, seed=seed)
         num_envs = int(self.cfg.num_envs)
-        self.o = oracle_lib.OracleEnv(self.cfg)
+        self.o = oracle_lib.OracleEnv(self.cfg, precision)
         if object_sizes is not None:
             self.cfg.obj_size_explicit = self.o.cfg.obj_size_explicit = 1
-            Layout(num_envs, int(oracle_lib.load().lt_oracle_obs_dim(self.o.cfg)), int(self.cfg.tactile_enabled)).arr(self.o.arena, "LT_F_OBJ_SIZES")[:num_envs] = \
+            Layout(num_envs, int(self.o.lib.lt_oracle_obs_dim(self.o.cfg)), int(self.cfg.tactile_enabled)).arr(self.o.arena, "LT_F_OBJ_SIZES")[:num_envs] = \
                 np.asarray(object_sizes, dtype=np.float32)
         self.o.reset_all()
         self.num_envs, self.device = num_envs, torch.device("cpu")
-        self.num_obs = int(oracle_lib.load().lt_oracle_obs_dim(self.o.cfg))
+        self.num_obs = int(self.o.lib.lt_oracle_obs_dim(self.o.cfg))
         self.num_privileged_obs = self.num_obs
         wide = int(self.cfg.tactile_format) in (_abi.CONSTS["LT_TACTILE_PROCESSED"], _abi.CONSTS["LT_TACTILE_ORIGINAL"])
         self.layout = Layout(num_envs, self.num_obs, int(self.cfg.tactile_enabled), 884 if wide else 442)

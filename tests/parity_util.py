@@ -205,3 +205,91 @@ class Tally:
 
 def compare_arenas(env, ora, what: str = "", **kw):
     return compare_host_arenas(env.cfg, device_arena_to_host(env), ora.arena, what=what, **kw)
+
+
+# ---- error against the double-precision oracle (oracle/_build/liblt_oracle_f64.so) ----------------------------------------
+# Continuous per-env outputs: every quad field except the thresholded contact timers / flags, the observation rows and the reward.
+F64_ROW_FIELDS = ("LT_F_OBS_POLICY", "LT_F_OBS_CRITIC", "LT_F_REWARD")
+# e_cand <= F64_RATIO * e_o32 + F64_ULPS * 2^-24 * max|f64| per field (tests/test_hip_f64_parity.py)
+F64_RATIO, F64_ULPS = 8.0, 16.0
+
+
+def f64_fields(cfg) -> list:
+    tactile = int(cfg.tactile_enabled)
+    quad = [nm for nm in QUAD_FIELDS if nm not in FLIP_TOLERANT and nm != "LT_F_GAIT_FLAGS" and (tactile or nm != "LT_F_PLATE_SAMPLES")]
+    return quad + list(F64_ROW_FIELDS)
+
+
+def _band(name: str, ncols: int, obs_tol=(4e-4, 4e-4)):
+    if name in F64_ROW_FIELDS:
+        return np.full(ncols, obs_tol[0], np.float64), np.full(ncols, obs_tol[1], np.float64)
+    atol, rtol = TOL.get(name, TOL["default"])
+    atol, rtol = np.full(ncols, atol, np.float64), np.full(ncols, rtol, np.float64)
+    if name == "LT_F_REWARD_TERMS":
+        for col, (ta, tr) in TERM_TOL.items():
+            atol[col], rtol[col] = ta, tr
+    if name == "LT_F_PLATE_SAMPLES":
+        atol[8:], rtol[8:] = PLATE_FORCE_TOL
+    return atol, rtol
+
+
+def f64_errors(cfg, cand: np.ndarray, ref: np.ndarray, drop_envs=()) -> dict:
+    """Per continuous field: (max |cand - ref|, max |ref|, max error as a fraction of the field's parity band), over the envs not
+    in `drop_envs` (those that flipped a thresholded quantity or took a discontinuous event on either side)."""
+    n = int(cfg.num_envs)
+    obs_dim = (45 if cfg.task == C["LT_TASK_LOCOMOTION"] else 58) * int(cfg.obs_history)
+    wide = int(cfg.tactile_format) in (C["LT_TACTILE_PROCESSED"], C["LT_TACTILE_ORIGINAL"])
+    L = Layout(n, obs_dim, int(cfg.tactile_enabled), C["LT_TACTILE_WIDE_DIM"] if wide else C["LT_TACTILE_DIM"])
+    keep = np.ones(n, bool)
+    keep[list(drop_envs)] = False
+    out = {}
+    for name in f64_fields(cfg):
+        if name in F64_ROW_FIELDS:
+            a, b = L.arr(cand, name)[:n], L.arr(ref, name)[:n]
+            a, b = a.reshape(n, -1), b.reshape(n, -1)
+        else:
+            a, b = L.vec(cand, name), L.vec(ref, name)
+        a, b = a[keep].astype(np.float64), b[keep].astype(np.float64)
+        if name in AIR_VARIANCE_LANES:  # a thresholded-timer statistic: its flips are forgiven, not measured
+            a, b = np.delete(a, AIR_VARIANCE_LANES[name], axis=1), np.delete(b, AIR_VARIANCE_LANES[name], axis=1)
+        if not a.size:
+            out[name] = (0.0, 0.0, 0.0)
+            continue
+        atol, rtol = _band(name, L.vec(ref, name).shape[1] if name not in F64_ROW_FIELDS else a.shape[1])
+        if name in AIR_VARIANCE_LANES:
+            atol, rtol = np.delete(atol, AIR_VARIANCE_LANES[name]), np.delete(rtol, AIR_VARIANCE_LANES[name])
+        d = np.abs(a - b)
+        out[name] = (float(d.max()), float(np.abs(b).max()), float((d / (atol + rtol * np.abs(b))).max()))
+    return out
+
+
+def f64_merge(acc: dict, errs: dict) -> dict:
+    """Running per-field maximum of f64_errors over steps."""
+    for k, v in errs.items():
+        acc[k] = tuple(max(x, y) for x, y in zip(acc.get(k, (0.0, 0.0, 0.0)), v))
+    return acc
+
+
+def f64_ratio_failures(e_cand: dict, e_o32: dict, ratio: float = F64_RATIO, ulps: float = F64_ULPS, exceptions=None) -> list:
+    """Fields where the candidate is further from the f64 oracle than `ratio` times the f32 oracle is, beyond `ulps` f32 ulps of
+    the field's magnitude.  `exceptions`: {field: ratio} for fields whose larger ratio has a located, documented cause."""
+    bad = []
+    for name, (ec, mref, _) in e_cand.items():
+        eo = e_o32[name][0]
+        r = (exceptions or {}).get(name, ratio)
+        if not ec <= r * eo + ulps * 2.0 ** -24 * mref:
+            bad.append((name, ec, eo, r))
+    return bad
+
+
+def f64_table(what: str, cols: dict) -> str:
+    """cols: {label: merged f64_errors}.  One line per field: each column's max error and fraction of the band, then the ratio of
+    the first column to the last."""
+    labels = list(cols)
+    lines = [f"[f64] {what}", f"  {'field':28s}" + "".join(f" {lb + ' err':>12s} {'band':>6s}" for lb in labels) + "    ratio"]
+    for name in cols[labels[-1]]:
+        row = f"  {name:28s}" + "".join(f" {cols[lb][name][0]:12.3e} {cols[lb][name][2]:6.3f}" for lb in labels)
+        first, last = cols[labels[0]][name][0], cols[labels[-1]][name][0]
+        row += f" {first / last:8.2f}" if len(labels) > 1 and last > 0 else ("        -" if len(labels) > 1 else "")
+        lines.append(row)
+    return "\n".join(lines)

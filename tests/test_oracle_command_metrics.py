@@ -9,6 +9,7 @@ import torch
 
 from locotouch_amd import _abi
 from locotouch_amd.env import reset_batch_means
+from tests import oracle_lib as O
 from tests.oracle_vec_env import OracleVecEnv
 
 
@@ -18,13 +19,13 @@ def _quat_apply_inv(q, v):
     return v - w * t + np.cross(u, t)
 
 
-def test_metrics_follow_update_metrics_and_the_reset_batch_log():
+def test_metrics_follow_update_metrics_and_the_reset_batch_log(precision="f32"):
     cfg = _abi.preset_cfg("Isaac-RandCylinderTransportTeacher-LocoTouch-v1", num_envs=48, seed=11)
     cfg.push_robot_interval[0] = cfg.push_robot_interval[1] = 1e6   # no interval pushes: the arena's velocities are the ones compute() saw
     cfg.push_obj_interval[0] = cfg.push_obj_interval[1] = 1e6
     cfg.cmd_resample_time[0] = cfg.cmd_resample_time[1] = 1e6       # no timer resample: a non-reset env keeps its command
     cfg.max_episode_length = 23
-    env = OracleVecEnv("", cfg=cfg)
+    env = OracleVecEnv("", cfg=cfg, precision=precision)
     n = env.num_envs
     f = lambda name: env.field(name).numpy()  # noqa: E731
     assert (f("LT_F_EVENT_TIMERS")[:, 0, 2:] == 0).all() and (f("LT_F_LAST_CMD_METRICS") == 0).all()  # reset() runs no compute()
@@ -65,13 +66,13 @@ def test_metrics_follow_update_metrics_and_the_reset_batch_log():
     np.testing.assert_allclose(reset_batch_means(rows), want, rtol=1e-5)
 
 
-def test_binary_maximal_command_draws_the_eight_corner_commands():
+def test_binary_maximal_command_draws_the_eight_corner_commands(precision="f32"):
     """`binary_maximal_command` (commands.py:95-104, 189-197, 518-521; off in every registered config): a resample picks one of the 8
     sign combinations uniformly and scales it by the current upper range bounds; `is_standing_env` is left alone."""
     cfg = _abi.preset_cfg("Isaac-RandCylinderTransportTeacher-LocoTouch-v1", num_envs=512, seed=3)
     cfg.cmd_binary_maximal = 1
     cfg.cmd_zero_steps = 0
-    env = OracleVecEnv("", cfg=cfg)
+    env = OracleVecEnv("", cfg=cfg, precision=precision)
     P = env.cmd_params.numpy()
     hi = np.array([P[1], P[3], P[5]], np.float32)
     cmd = env.field("LT_F_CMD_BUF").numpy()[:, 0, :3]
@@ -81,3 +82,8 @@ def test_binary_maximal_command_draws_the_eight_corner_commands():
     counts = np.array([sum(1 for c in cmd if tuple(np.sign(c).astype(int)) == k) for k in sorted(combos)])
     assert counts.min() > 512 / 8 * 0.5 and counts.max() < 512 / 8 * 1.6  # uniform over the 8 corners
     assert (env.field("LT_F_CMD_BUF").numpy()[:, 0, 3] == 0).all()  # nobody was made a standing env by the resample
+
+
+# the same checks on the double-precision oracle build (tests/oracle_lib.f64_twin)
+test_metrics_follow_update_metrics_and_the_reset_batch_log_f64 = O.f64_twin(test_metrics_follow_update_metrics_and_the_reset_batch_log)
+test_binary_maximal_command_draws_the_eight_corner_commands_f64 = O.f64_twin(test_binary_maximal_command_draws_the_eight_corner_commands)

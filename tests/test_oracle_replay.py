@@ -28,11 +28,11 @@ def _arr(vals):
     return (f32 * len(vals))(*[float(v) for v in vals])
 
 
-def test_command_resample_matches_reference_replay():
+def test_command_resample_matches_reference_replay(precision="f32"):
     """Bin selection by inverse CDF over (p, 1 - 2p, p), per-bin ranges [new_lo, old_lo], [old_lo, old_hi], [old_hi, new_hi],
     the equal-range shortcut, the standing draw (<=) and the buffer copy."""
     g = np.load(GOLD)
-    lib, cfg = O.load(), _cfg()
+    lib, cfg = O.load(precision), _cfg()
     assert abs(cfg.cmd_new_probs - float(g["cmd_new_probs"])) < 1e-7
     S, n = g["cmd_ub"].shape[:2]
     seen_bins = set()
@@ -61,9 +61,9 @@ def test_command_resample_matches_reference_replay():
     assert seen_bins == {0, 1, 2}
 
 
-def test_trunk_material_matches_reference_replay():
+def test_trunk_material_matches_reference_replay(precision="f32"):
     g = np.load(GOLD)
-    lib, cfg = O.load(), _cfg()
+    lib, cfg = O.load(precision), _cfg()
     # lt_cfg_default carries the reference's resolved ranges (rand_cylinder cfg :56 overrides the static range)
     np.testing.assert_allclose(np.array(cfg.trunk_friction[:]), g["mat_ranges"][0], atol=1e-7)
     np.testing.assert_allclose(np.array(cfg.trunk_restitution[:]), g["mat_ranges"][2], atol=1e-7)
@@ -74,10 +74,10 @@ def test_trunk_material_matches_reference_replay():
     assert (g["mat_out"][:, 1] <= g["mat_out"][:, 0]).all()  # make_consistent
 
 
-def test_reset_object_state_matches_reference_replay():
+def test_reset_object_state_matches_reference_replay(precision="f32"):
     """World-axis offset, + cylinder height / 2, orientation = robot quat (x) euler, velocity = robot root velocity."""
     g = np.load(GOLD)
-    lib, cfg = O.load(), _cfg()
+    lib, cfg = O.load(precision), _cfg()
     pr = g["obj_pose_range"]
     for i in range(3):
         np.testing.assert_allclose(np.array(cfg.obj_reset_pos[i][:]), pr[i], atol=1e-7)
@@ -92,11 +92,11 @@ def test_reset_object_state_matches_reference_replay():
         np.testing.assert_allclose(np.array(lin[:] + ang[:]), g["obj_out_vel"][e], rtol=0, atol=1e-7)
 
 
-def test_noisy_object_state_observation_matches_reference_replay():
+def test_noisy_object_state_observation_matches_reference_replay(precision="f32"):
     """Additive noise on position / velocities, euler noise right-multiplied onto the quaternion, the second draw for envs
     that have not touched the plate yet, then the per-component scale."""
     g = np.load(GOLD)
-    lib, cfg = O.load(), _cfg()
+    lib, cfg = O.load(precision), _cfg()
     nmin, nmax = g["osn_n_min"], g["osn_n_max"]
     np.testing.assert_allclose(-nmin, nmax)
     np.testing.assert_allclose(np.array(cfg.obj_noise[:12]), nmax, atol=1e-7)
@@ -118,11 +118,11 @@ def test_noisy_object_state_observation_matches_reference_replay():
     assert 0 < n_noncontact < T * n
 
 
-def test_binary_tactile_matches_reference_replay():
+def test_binary_tactile_matches_reference_replay(precision="f32"):
     """Thresholds (+ per-taxel offset drawn once), contact map, dropout THEN addition (a dropped taxel can be re-added), two
     identical channels - with the student preset's parameters, which the golden's resolved term params pin."""
     g = np.load(GOLD)
-    lib = O.load()
+    lib = O.load(precision)
     cfg = _abi.preset_cfg("Isaac-RandCylinderTransportStudent_SingleBinaryTac_CNNRNN_Mon-LocoTouch-v1", num_envs=16)
     thr, nmin, nmax, pdrop, padd = g["tac_params"]
     assert abs(cfg.tactile_threshold - thr) < 1e-7 and abs(cfg.tactile_threshold_noise - nmax) < 1e-7 and abs(nmin + nmax) < 1e-12
@@ -167,11 +167,11 @@ def tactile_cfg_for(g, pi, num_envs=16, play=False):
 
 @pytest.mark.parametrize("pi", [0, 1, 2])
 @pytest.mark.parametrize("cname", list(FORMATS))
-def test_every_tactile_signals_class_matches_reference_replay(pi, cname):
+def test_every_tactile_signals_class_matches_reference_replay(pi, cname, precision="f32"):
     """O6: TactileSignals / Binary / Normalized / Discrete / Cotinuous / Processed (observations.py:248-429) on replayed uniforms:
     contact maps exact, force channels to f32 rounding (a discretisation level is 0.2: a flipped level would fail)."""
     g = np.load(GOLD)
-    lib = O.load()
+    lib = O.load(precision)
     cfg = tactile_cfg_for(g, pi)
     fmt = C[FORMATS[cname]]
     pre = f"tf_{pi}_{cname}_"
@@ -196,3 +196,12 @@ def test_every_tactile_signals_class_matches_reference_replay(pi, cname):
     assert stats["contact"] > 50
     if cname in ("discrete", "processed", "original"):
         assert len(stats["levels"]) >= 4  # several discretisation levels occur
+
+
+# the same reference pins on the double-precision oracle build (tests/oracle_lib.f64_twin)
+test_command_resample_matches_reference_replay_f64 = O.f64_twin(test_command_resample_matches_reference_replay)
+test_trunk_material_matches_reference_replay_f64 = O.f64_twin(test_trunk_material_matches_reference_replay)
+test_reset_object_state_matches_reference_replay_f64 = O.f64_twin(test_reset_object_state_matches_reference_replay)
+test_noisy_object_state_observation_matches_reference_replay_f64 = O.f64_twin(test_noisy_object_state_observation_matches_reference_replay)
+test_binary_tactile_matches_reference_replay_f64 = O.f64_twin(test_binary_tactile_matches_reference_replay)
+test_every_tactile_signals_class_matches_reference_replay_f64 = O.f64_twin(test_every_tactile_signals_class_matches_reference_replay)

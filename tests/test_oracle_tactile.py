@@ -17,14 +17,14 @@ ROWS, COLS = C["LT_TACTILE_ROWS"], C["LT_TACTILE_COLS"]
 X0, Y0, DX, DY, HX, HY = 0.1144, 0.0768, 0.0143, 0.0128, 0.00915, 0.00875  # include/lt_go1_model.h LT_TAXEL_*
 
 
-def taxel_forces(x, y, f):
+def taxel_forces(x, y, f, precision="f32"):
     out = np.zeros(ROWS * COLS, np.float32)
     a = [np.ascontiguousarray(v, np.float32) for v in (x, y, f)]
-    O.load().lt_oracle_taxel_forces(O.fptr(a[0]), O.fptr(a[1]), O.fptr(a[2]), O.fptr(out))
+    O.load(precision).lt_oracle_taxel_forces(O.fptr(a[0]), O.fptr(a[1]), O.fptr(a[2]), O.fptr(out))
     return out.reshape(ROWS, COLS)
 
 
-def test_uniform_line_pressure_times_length_inside_each_box():
+def test_uniform_line_pressure_times_length_inside_each_box(precision="f32"):
     """A uniformly loaded line along y through a taxel row's centres: every taxel gets F / L x |line inside its box|."""
     F, row = 6.0, 5
     xs = X0 - DX * row
@@ -32,7 +32,7 @@ def test_uniform_line_pressure_times_length_inside_each_box():
     x = [xs] * 4
     y = list(np.linspace(ya, yb, 4))
     f = [F / 6, F / 3, F / 3, F / 6]  # cell integrals of a constant pressure (end cells are half cells)
-    tf = taxel_forces(x, y, f)
+    tf = taxel_forces(x, y, f, precision=precision)
     L = yb - ya
     for col in range(COLS):
         cy = Y0 - DY * col
@@ -44,7 +44,7 @@ def test_uniform_line_pressure_times_length_inside_each_box():
     assert abs(tf.sum() - F / L * cover) < 1e-4 and tf.sum() > F
 
 
-def test_oblique_line_and_linear_pressure_conserve_the_sample_forces():
+def test_oblique_line_and_linear_pressure_conserve_the_sample_forces(precision="f32"):
     """Any line inside the grid: summing taxel forces over a PARTITION of the plane (each point counted once) gives back the
     summed sample forces; with overlapping boxes the sum can only be larger, and never exceeds the 4-fold cover."""
     rng = np.random.default_rng(3)
@@ -53,35 +53,35 @@ def test_oblique_line_and_linear_pressure_conserve_the_sample_forces():
         p3 = np.array([rng.uniform(-0.09, 0.09), rng.uniform(-0.06, 0.06)])
         pts = np.linspace(p0, p3, 4)
         f = rng.uniform(0.0, 2.0, 4)
-        tf = taxel_forces(pts[:, 0], pts[:, 1], f)
+        tf = taxel_forces(pts[:, 0], pts[:, 1], f, precision=precision)
         assert (tf >= -1e-6).all()
         assert f.sum() * (1 - 1e-4) - 1e-5 <= tf.sum() <= 4 * f.sum() + 1e-5
     # swapping the line's direction changes nothing
-    tf_a = taxel_forces([0.05, 0.02, -0.01, -0.04], [0.03, 0.01, -0.01, -0.03], [0.2, 0.9, 0.4, 0.1])
-    tf_b = taxel_forces([-0.04, -0.01, 0.02, 0.05], [-0.03, -0.01, 0.01, 0.03], [0.1, 0.4, 0.9, 0.2])
+    tf_a = taxel_forces([0.05, 0.02, -0.01, -0.04], [0.03, 0.01, -0.01, -0.03], [0.2, 0.9, 0.4, 0.1], precision=precision)
+    tf_b = taxel_forces([-0.04, -0.01, 0.02, 0.05], [-0.03, -0.01, 0.01, 0.03], [0.1, 0.4, 0.9, 0.2], precision=precision)
     np.testing.assert_allclose(tf_a, tf_b, atol=2e-6)
 
 
-def test_degenerate_and_unloaded_lines():
-    assert (taxel_forces([0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0]) == 0).all()
+def test_degenerate_and_unloaded_lines(precision="f32"):
+    assert (taxel_forces([0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0], precision=precision) == 0).all()
     # negative (adhesive) sample forces are not sensor load
-    assert (taxel_forces([0.01, 0.02, 0.03, 0.04], [0, 0, 0, 0], [-1, -1, -1, -1]) == 0).all()
+    assert (taxel_forces([0.01, 0.02, 0.03, 0.04], [0, 0, 0, 0], [-1, -1, -1, -1], precision=precision) == 0).all()
     # a line collapsed to a point loads the taxel(s) whose box holds it with the whole force
     cx, cy = X0 - DX * 8, Y0 - DY * 6
-    tf = taxel_forces([cx] * 4, [cy] * 4, [0.5, 0.5, 0.5, 0.5])
+    tf = taxel_forces([cx] * 4, [cy] * 4, [0.5, 0.5, 0.5, 0.5], precision=precision)
     assert tf[8, 6] == 2.0 and tf.sum() == 2.0
     # off the sensor: nothing
-    assert (taxel_forces([0.2] * 4, [0.0, 0.01, 0.02, 0.03], [1, 1, 1, 1]) == 0).all()
+    assert (taxel_forces([0.2] * 4, [0.0, 0.01, 0.02, 0.03], [1, 1, 1, 1], precision=precision) == 0).all()
 
 
-def test_student_env_tactile_rows_and_sensor_cadence():
+def test_student_env_tactile_rows_and_sensor_cadence(precision="f32"):
     """Reset + steps of the student task on the oracle: binary two-channel rows; zero forces right after a reset (only
     `addition` noise can light a taxel); the plate samples refresh on sim steps 0, 5, 10, ... since the reset - so an env
     step whose four sim steps hold no multiple of 5 (ep_len % 5 == 4 before the step) leaves them untouched."""
     n = 24
     cfg = _abi.preset_cfg(STUDENT, num_envs=n, seed=5)
     assert cfg.tactile_enabled == 1 and cfg.max_episode_length == 500 and cfg.num_envs == n
-    ora = O.OracleEnv(cfg)
+    ora = O.OracleEnv(cfg, precision)
     ora.reset_all()
     L = Layout(n, 348, 1)
     tac = L.arr(ora.arena, "LT_F_OBS_TACTILE")[:n]
@@ -113,14 +113,14 @@ def test_student_env_tactile_rows_and_sensor_cadence():
     assert L.arr(ora.arena, "LT_F_OBS_POLICY").shape[1] == 348
 
 
-def test_play_env_serves_the_four_channel_groups():
+def test_play_env_serves_the_four_channel_groups(precision="f32"):
     """The -Play- registration's `original_tactile` / `processed_tactile` (object_transport_student_env_cfg.py:170-171) next to
     `tactile`, each with its own thresholds / noise draws, and the channel relations of the TactileSignals classes."""
     import torch
 
     from tests.oracle_vec_env import OracleVecEnv
 
-    env = OracleVecEnv(STUDENT.replace("-v1", "-Play-v1"), seed=3)
+    env = OracleVecEnv(STUDENT.replace("-v1", "-Play-v1"), seed=3, precision=precision)
     n = env.num_envs
     assert n == 20 and env.cfg.tactile_aux_groups == 3
     env.reset()
@@ -141,3 +141,11 @@ def test_play_env_serves_the_four_channel_groups():
         acc["proc"] += proc[:, :221].sum()
         acc["differ"] += int((orig[:, :221] != proc[:, :221]).sum() + (tac[:, :221] != proc[:, :221]).sum())
     assert acc["orig"] > 100 and acc["proc"] > 100 and acc["differ"] > 0  # separate term instances: separate thresholds and noise
+
+
+# the same checks on the double-precision oracle build (tests/oracle_lib.f64_twin)
+test_uniform_line_pressure_times_length_inside_each_box_f64 = O.f64_twin(test_uniform_line_pressure_times_length_inside_each_box)
+test_oblique_line_and_linear_pressure_conserve_the_sample_forces_f64 = O.f64_twin(test_oblique_line_and_linear_pressure_conserve_the_sample_forces)
+test_degenerate_and_unloaded_lines_f64 = O.f64_twin(test_degenerate_and_unloaded_lines)
+test_student_env_tactile_rows_and_sensor_cadence_f64 = O.f64_twin(test_student_env_tactile_rows_and_sensor_cadence)
+test_play_env_serves_the_four_channel_groups_f64 = O.f64_twin(test_play_env_serves_the_four_channel_groups)
