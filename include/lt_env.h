@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LT_ABI_VERSION 18
+#define LT_ABI_VERSION 19
 
 /* error codes */
 #define LT_OK 0
@@ -626,6 +626,49 @@ int lt_rollout_policy_value(const lt_mlp_desc* actor, const float* actor_packed,
                             const float* critic_packed, const float* critic_obs, float* values, int64_t n, uint64_t seed,
                             const int64_t* step_counter, int64_t step_offset, const float* std12, float* st_actions, float* st_mu,
                             float* st_sigma, float* st_logp, float* actions_out, void* stream);
+/* ---- renderer (csrc/lt_render.hip): batched ray casting of the collision primitives, for videos and for users who want depth and
+ * segmentation images.  One view = one env seen from one camera.  Each view's 17 body poses come from forward kinematics of the root
+ * pose and the joint angles in the arena; the scene is the Go1's collision primitives (include/lt_go1_model.h), the carrying plate, the
+ * object cylinder and a 0.5 m checker ground plane. ---- */
+enum lt_render_origin {
+  LT_RENDER_ORIGIN_WORLD = 0,      /* eye and lookat are world points */
+  LT_RENDER_ORIGIN_ASSET_ROOT = 1  /* eye and lookat are offsets from the env's root position (translation only) */
+};
+enum lt_render_flag { LT_RENDER_SHADOWS = 1, LT_RENDER_TAXELS = 2, LT_RENDER_CONTACT_TINT = 4, LT_RENDER_DEFAULT_FLAGS = 7 };
+/* primitive ids written to the id image (-1 = sky) */
+enum lt_render_prim {
+  LT_PRIM_TRUNK = 0, LT_PRIM_BACK_MID = 1, LT_PRIM_PLATE = 2, LT_PRIM_RAIL_LEFT = 3, LT_PRIM_RAIL_RIGHT = 4,
+  LT_PRIM_HIP = 5,    /* + leg (FR, FL, RR, RL) */
+  LT_PRIM_THIGH = 9,  /* + leg */
+  LT_PRIM_CALF = 13,  /* + leg */
+  LT_PRIM_FOOT = 17,  /* + leg */
+  LT_PRIM_OBJECT = 21, LT_PRIM_GROUND = 22, LT_RENDER_NUM_PRIMS = 23
+};
+#define LT_RENDER_MAX_SIZE 8192
+#define LT_RENDER_FAR 1000            /* m: a ray that hits nothing closer sees sky */
+#define LT_RENDER_DEPTH_MISS 1000000  /* depth written where the ray hits nothing (finite) */
+#define LT_RENDER_VIEWS_PER_LAUNCH 32 /* views per kernel launch (they travel in the kernel arguments) */
+typedef struct lt_render_view {
+  int32_t env_id;
+  int32_t origin;     /* lt_render_origin */
+  float eye[3];
+  float lookat[3];
+  float fov_y_deg;    /* vertical field of view, degrees, (0, 179] */
+} lt_render_view;
+typedef struct lt_render_desc {
+  int32_t width, height;
+  int32_t flags;      /* lt_render_flag bits */
+  float light_dir[3]; /* direction TOWARDS the light (normalised by the kernel) */
+} lt_render_desc;
+/* Render `nviews` views: rgba uint32 [nviews][height][width] (one packed dword per pixel, bytes R, G, B, A = 255), and where given
+ * depth float [nviews][height][width] (ray length in m, LT_RENDER_DEPTH_MISS for sky), ids int32 [nviews][height][width] (lt_render_prim,
+ * -1 for sky), poses float [nviews][17][7] (the bodies' world pos + quat wxyz, sensor-body order).  Device pointers, 4-byte aligned;
+ * launches on `stream` without synchronising (graph-capturable), ceil(nviews / LT_RENDER_VIEWS_PER_LAUNCH) launches.  Bit-deterministic.
+ * LT_EINVAL, before any launch, for: an unbound env, nviews <= 0, an env id out of range, a size of 0 or above LT_RENDER_MAX_SIZE,
+ * misaligned or missing rgba, a non-finite camera or light, eye == lookat, a field of view outside (0, 179]. */
+int lt_env_render(lt_env* env, const lt_render_desc* desc, const lt_render_view* views, int nviews, uint32_t* rgba, float* depth,
+                  int32_t* ids, float* poses, void* stream);
+
 /* Device kernel names and static resource usage, for profiling scripts. */
 const char* lt_env_kernel_name(int which);
 

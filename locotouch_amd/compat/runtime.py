@@ -19,6 +19,7 @@ import re
 import sys
 import types
 
+import numpy as np
 import torch
 
 from . import isaaclab_shim
@@ -73,10 +74,23 @@ def _install_gym():
     def make(id, cfg=None, render_mode=None, **kwargs):
         if id not in registry:
             raise KeyError(f"gym.make: no registered env with id {id!r}")
-        return make_env(id, cfg)
+        env = make_env(id, cfg)
+        env.render_mode = render_mode
+        return env
 
-    class RecordVideo:  # there is no renderer: the wrapper is transparent
-        def __new__(cls, env, **kwargs):
+    class RecordVideo:
+        """gymnasium.wrappers.RecordVideo: attaches a video.VideoRecorder to the ManagedEnv and returns that env.  The recorder is not
+        a step wrapper because RslRlVecEnvWrapper.step calls `env.unwrapped.step` directly; ManagedEnv.step and the fused rollout call
+        it after every vectorised step instead.  Only the main rank (RANK / LOCAL_RANK 0) records."""
+
+        def __new__(cls, env, video_folder, episode_trigger=None, step_trigger=None, video_length=0, name_prefix="rl-video",
+                    disable_logger=False, **kwargs):
+            if episode_trigger is not None:
+                raise NotImplementedError("RecordVideo(episode_trigger=...): vectorised envs have no common episode boundary; use step_trigger")
+            if int(os.environ.get("RANK", "0")) != 0 or int(os.environ.get("LOCAL_RANK", "0")) != 0:
+                return env
+            env.unwrapped.attach_recorder(video_folder, name_prefix=name_prefix, step_trigger=step_trigger,
+                                          video_length=int(video_length) if video_length else 200, disable_logger=disable_logger)
             return env
 
     _module("gymnasium", register=register, make=make, spec=spec, registry=registry, Env=object)
@@ -89,6 +103,10 @@ class ManagedEnv:
 
     def __init__(self, task_id: str, cfg, vec_env, extra_rewards=(), extra_terminations=(), extra_observations=()):
         self.task_id, self.cfg, self.vec = task_id, cfg, vec_env
+        self.render_mode = None  # gym.make(render_mode=...)
+        self.recorder = None     # video.VideoRecorder (RecordVideo)
+        self.video_camera = None  # render.Camera of the recorder; None: the chase camera
+        self.video_resolution = None  # (W, H) of the recorder; None: cfg.viewer.resolution
         # reward terms the fused kernels do not know: evaluated in torch on IsaacLab-layout views after every step and added to
         # the kernel's reward (compat/scene_views.py; the slow path of SURVEY.md §8(b) B3)
         self.extra = None
@@ -199,7 +217,62 @@ class ManagedEnv:
                 self.extra.request_terminations(dones)
             self.extra.post_step()
             obs, extras = self._with_user_observations(obs, extras, dones)
+        if self.recorder is not None and getattr(self.vec, "recorder", None) is not self.recorder:  # (the HIP env calls it itself)
+            self.recorder.after_step()
         return obs, rew, dones, extras
+
+    # ---- rendering ------------------------------------------------------------------------------------------
+    def _viewer(self):
+        from .. import render as R
+
+        viewer = getattr(self.cfg, "viewer", None)
+        if viewer is None:
+            return R.chase_camera(), 0, (1280, 720)
+        return R.from_viewer_cfg(viewer)
+
+    def render(self):
+        """gymnasium Env.render: with render_mode "rgb_array", uint8 (H, W, 3) of env cfg.viewer.env_index seen from cfg.viewer
+        (eye, lookat, origin_type) at cfg.viewer.resolution; None for any other render mode."""
+        if self.render_mode != "rgb_array":
+            return None
+        from .. import render as R
+
+        cam, env_index, (w, h) = self._viewer()
+        vec_render = getattr(self.vec, "render", None)
+        if vec_render is None:
+            raise RuntimeError("this env has no renderer")
+        out = vec_render([env_index], cam, width=w, height=h)
+        return out if isinstance(out, np.ndarray) else R.rgba_to_rgb(out["rgba"][0])
+
+    def attach_recorder(self, video_folder: str, name_prefix: str = "rl-video", step_trigger=None, video_length: int = 200,
+                        disable_logger: bool = False):
+        """Record videos of env cfg.viewer.env_index (video.VideoRecorder) with `video_camera` (default: the chase camera) at
+        `video_resolution` (default: cfg.viewer.resolution).  The HIP env's frames stay on the device until the recorder's side-stream
+        copy; the fused rollout calls the recorder through `vec.recorder`."""
+        from .. import render as R
+        from ..video import VideoRecorder
+
+        _, env_index, res = self._viewer()
+        cam = self.video_camera or R.chase_camera()
+        w, h = self.video_resolution or res
+        vec = self.vec
+        if hasattr(vec, "render") and hasattr(vec, "_handle"):  # the HIP env: device frames, one reused output buffer
+            bufs: dict = {}
+
+            def render_fn():
+                bufs.update(vec.render([env_index], cam, width=w, height=h, out=bufs if bufs else None))
+                return bufs["rgba"][0]
+        else:
+            def render_fn():
+                out = vec.render([env_index], cam, width=w, height=h)
+                return out if isinstance(out, np.ndarray) else R.rgba_to_rgb(out["rgba"][0])
+
+        fps = 1.0 / float(getattr(vec, "step_dt", 0.02) or 0.02)
+        self.recorder = VideoRecorder(render_fn, video_folder, name_prefix=name_prefix, step_trigger=step_trigger,
+                                      video_length=video_length, disable_logger=disable_logger, fps=fps)
+        if hasattr(vec, "render") and hasattr(vec, "_handle"):
+            vec.recorder = self.recorder  # the HIP env feeds it from env.step and the fused rollout
+        return self.recorder
 
     @property
     def unwrapped(self):
@@ -217,7 +290,11 @@ class ManagedEnv:
         self.vec.episode_length_buf = value
 
     def close(self):
-        pass
+        if self.recorder is not None:
+            self.recorder.close()
+            if getattr(self.vec, "recorder", None) is self.recorder:
+                self.vec.recorder = None
+            self.recorder = None
 
 
 def translate_env_cfg(task_id: str, cfg):

@@ -291,6 +291,51 @@ int lt_env_set_command_ranges(lt_env* env, const float ranges[6], int zero_steps
   return finish(lt_launch_set_command_ranges(env, ranges, zero_steps, rel_standing, stream), "lt_env_set_command_ranges");
 }
 
+namespace {
+// bit-level finiteness of a float in memory, read as an integer (the library builds with -ffinite-math-only, under which std::isfinite
+// and any test on a float VALUE may fold to true)
+bool finite_f(const float* p) {
+  uint32_t u;
+  std::memcpy(&u, p, 4);
+  return (u & 0x7f800000u) != 0x7f800000u;
+}
+}  // namespace
+
+int lt_env_render(lt_env* env, const lt_render_desc* desc, const lt_render_view* views, int nviews, uint32_t* rgba, float* depth,
+                  int32_t* ids, float* poses, void* stream) {
+  if (!env || !desc || !views) { lt_set_error("lt_env_render: null env, desc or views"); return LT_EINVAL; }
+  if (!env->arena) { lt_set_error("lt_env_render: arena not bound"); return LT_EINVAL; }
+  if (nviews <= 0) { lt_set_error("lt_env_render: nviews must be positive"); return LT_EINVAL; }
+  if (desc->width <= 0 || desc->height <= 0 || desc->width > LT_RENDER_MAX_SIZE || desc->height > LT_RENDER_MAX_SIZE) {
+    lt_set_error("lt_env_render: width and height must lie in [1, LT_RENDER_MAX_SIZE]");
+    return LT_EINVAL;
+  }
+  if (!rgba || (((uintptr_t)rgba | (uintptr_t)depth | (uintptr_t)ids | (uintptr_t)poses) & 3)) {
+    lt_set_error("lt_env_render: rgba is required and every output must be 4-byte aligned");
+    return LT_EINVAL;
+  }
+  const float* l = desc->light_dir;
+  if (!finite_f(&l[0]) || !finite_f(&l[1]) || !finite_f(&l[2]) || l[0] * l[0] + l[1] * l[1] + l[2] * l[2] < 1e-12f) {
+    lt_set_error("lt_env_render: light_dir must be finite and non-zero");
+    return LT_EINVAL;
+  }
+  for (int i = 0; i < nviews; ++i) {
+    const lt_render_view& v = views[i];
+    if (v.env_id < 0 || v.env_id >= env->cfg.num_envs) { lt_set_error("lt_env_render: env id out of range"); return LT_EINVAL; }
+    if (v.origin != LT_RENDER_ORIGIN_WORLD && v.origin != LT_RENDER_ORIGIN_ASSET_ROOT) { lt_set_error("lt_env_render: unknown origin mode"); return LT_EINVAL; }
+    bool ok = finite_f(&v.fov_y_deg);
+    float d2 = 0.f;
+    for (int k = 0; k < 3; ++k) {
+      ok = ok && finite_f(&v.eye[k]) && finite_f(&v.lookat[k]);
+      d2 += (v.lookat[k] - v.eye[k]) * (v.lookat[k] - v.eye[k]);
+    }
+    if (!ok) { lt_set_error("lt_env_render: non-finite camera"); return LT_EINVAL; }
+    if (!(d2 > 0.f)) { lt_set_error("lt_env_render: eye equals lookat"); return LT_EINVAL; }
+    if (!(v.fov_y_deg > 0.f) || v.fov_y_deg > 179.f) { lt_set_error("lt_env_render: fov_y_deg must lie in (0, 179]"); return LT_EINVAL; }
+  }
+  return finish(lt_launch_render(env, desc, views, nviews, rgba, depth, ids, poses, stream), "lt_env_render");
+}
+
 const char* lt_env_kernel_name(int which) {
   switch (which) {
     case 0: return "lt_step_kernel";

@@ -38,6 +38,9 @@ int lt_launch_gate_decide(const lt_env* env, int bump_counter, void* stream);  /
 int lt_launch_set_command_ranges(const lt_env* env, const float ranges[6], int zero_steps, float rel_standing, void* stream);
 int lt_launch_curriculum_apply_global(const lt_env* env, const float* ring_sums, int nsteps, long long n_total, void* stream);
 int lt_launch_tactile(const lt_env* env, void* stream);  // lt_tactile.hip
+// lt_render.hip: the renderer behind lt_env_render (arguments already validated)
+int lt_launch_render(const lt_env* env, const lt_render_desc* desc, const lt_render_view* views, int nviews, uint32_t* rgba, float* depth,
+                     int32_t* ids, float* poses, void* stream);
 int lt_launch_check(const lt_env* env, void* stream, long long* count);
 const char* lt_hip_error_string(int err);
 

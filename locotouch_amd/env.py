@@ -188,6 +188,8 @@ class LocoTouchVecEnv:
         if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.num_envs, 12):
             actions = actions.to(torch.float32).reshape(self.num_envs, 12).contiguous()
         _abi.check(self._lib.lt_env_step(self._handle, ctypes.c_void_p(actions.data_ptr()), self._stream()), "lt_env_step")
+        if self.recorder is not None:
+            self.recorder.after_step()
         return self.obs_policy, self.reward_buf, self.dones_buf, self._extras()
 
     def step_raw(self, actions_ptr: int) -> None:
@@ -355,6 +357,51 @@ class LocoTouchVecEnv:
         """The per-env metric tensors as `command_manager.get_term("base_velocity").metrics` holds them between two steps."""
         t = self.field("LT_F_EVENT_TIMERS")[:, 0, :]
         return {"error_vel_xy": t[:, 2], "error_vel_yaw": t[:, 3], "foot_air_time_variance": self.field("LT_F_TRUNK_FORCE_HIST")[:, 0, 3]}
+
+    # ---- rendering (lt_env_render) -------------------------------------------------------------------
+    recorder = None  # a video.VideoRecorder attached by the gymnasium shim's RecordVideo; the fused rollout calls it after each step
+
+    def render(self, env_ids=None, camera=None, width: int = 320, height: int = 240, depth: bool = False, ids: bool = False, out=None,
+               poses: bool = False, flags: int | None = None, light_dir=None) -> dict:
+        """Render one view per env of `env_ids` (default: env 0) with `camera` (render.Camera, or one per env; default the chase
+        camera).  Returns device tensors: "rgba" int32 [V, H, W] holding packed RGBA8 (bytes R, G, B, A; render.rgba_to_rgb unpacks), and when asked
+        "depth" float32 [V, H, W] (m; render.DEPTH_MISS for sky), "ids" int32 [V, H, W] (LT_PRIM_*, -1 sky), "poses" float32 [V, 17, 7].
+        `out`: a dict from an earlier call with the same shapes, whose tensors are written again.  Launches only (no host sync)."""
+        from . import render as R
+
+        if env_ids is None:
+            env_ids = [0]
+        env_ids = [int(e) for e in (env_ids.tolist() if hasattr(env_ids, "tolist") else env_ids)]
+        cams = camera if isinstance(camera, (list, tuple)) else [camera or R.chase_camera()] * len(env_ids)
+        if len(cams) != len(env_ids):
+            raise ValueError("one camera per view, or a single camera for all")
+        views = (_abi.LtRenderView * len(env_ids))(*[c.view(e) for c, e in zip(cams, env_ids)])
+        desc = _abi.LtRenderDesc()
+        desc.width, desc.height, desc.flags = int(width), int(height), R.DEFAULT_FLAGS if flags is None else int(flags)
+        for k, x in enumerate(R.DEFAULT_LIGHT if light_dir is None else light_dir):
+            desc.light_dir[k] = float(x)
+        shape = (len(env_ids), int(height), int(width))
+        res = out if out is not None else {}
+
+        def buf(name, dtype, shp, want):
+            if not want:
+                return None
+            t = res.get(name)
+            if t is None or tuple(t.shape) != shp or t.dtype != dtype:
+                if out is not None and t is not None:
+                    raise ValueError(f"out[{name!r}] has shape {tuple(t.shape)} / {t.dtype}, expected {shp} / {dtype}")
+                t = torch.empty(shp, dtype=dtype, device=self.device)
+                res[name] = t
+            return t
+
+        rgba = buf("rgba", torch.int32, shape, True)
+        dep = buf("depth", torch.float32, shape, depth)
+        idt = buf("ids", torch.int32, shape, ids)
+        pos = buf("poses", torch.float32, (len(env_ids), 17, 7), poses)
+        p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        _abi.check(self._lib.lt_env_render(self._handle, ctypes.byref(desc), views, len(env_ids), p(rgba), p(dep), p(idt), p(pos),
+                                           self._stream()), "lt_env_render")
+        return res
 
     @property
     def contact_forces_w_history(self) -> torch.Tensor:

@@ -1,0 +1,103 @@
+"""Cameras for the HIP renderer (csrc/lt_render.hip, lt_env_render in include/lt_env.h).
+
+A `Camera` is an eye point, a look-at point, an origin mode and a vertical field of view.  `ORIGIN_WORLD` takes eye and lookat as world
+points; `ORIGIN_ASSET_ROOT` takes them as offsets that follow the env's root position (translation only, like IsaacLab's viewer with
+origin_type="asset_root").  `from_viewer_cfg` translates IsaacLab's `ViewerCfg`.  The camera math here (`basis`, `ray_directions`) is
+the kernel's, written out in numpy for tests and tools.
+"""
+from __future__ import annotations
+
+import dataclasses
+import math
+
+import numpy as np
+
+from . import _abi
+
+C = _abi.CONSTS
+ORIGIN_WORLD = C["LT_RENDER_ORIGIN_WORLD"]
+ORIGIN_ASSET_ROOT = C["LT_RENDER_ORIGIN_ASSET_ROOT"]
+DEFAULT_FLAGS = C["LT_RENDER_DEFAULT_FLAGS"]
+DEPTH_MISS = float(C["LT_RENDER_DEPTH_MISS"])
+DEFAULT_FOV_Y = 60.0
+DEFAULT_LIGHT = (0.4, 0.3, 1.0)  # direction towards the light
+
+
+@dataclasses.dataclass
+class Camera:
+    eye: tuple = (1.2, -1.2, 0.8)
+    lookat: tuple = (0.0, 0.0, 0.0)
+    origin: int = ORIGIN_ASSET_ROOT
+    fov_y_deg: float = DEFAULT_FOV_Y
+
+    def view(self, env_id: int) -> _abi.LtRenderView:
+        v = _abi.LtRenderView()
+        v.env_id, v.origin, v.fov_y_deg = int(env_id), int(self.origin), float(self.fov_y_deg)
+        for k in range(3):
+            v.eye[k], v.lookat[k] = float(self.eye[k]), float(self.lookat[k])
+        return v
+
+
+def chase_camera() -> Camera:
+    """The default video camera: behind-left of the robot and above it, following the root position."""
+    return Camera(eye=(-1.0, -0.8, 0.55), lookat=(0.0, 0.0, 0.15), origin=ORIGIN_ASSET_ROOT)
+
+
+def from_viewer_cfg(viewer) -> tuple[Camera, int, tuple[int, int]]:
+    """IsaacLab `ViewerCfg` (eye, lookat, origin_type, env_index, asset_name, resolution) -> (Camera, env index, (width, height)).
+
+    origin_type "world" and "env" mean the same here: every env of this project shares one origin (there is no env grid), so an env's
+    origin is the world origin.  "asset_root" follows the root of `asset_name`; the robot is the only articulated asset, so any name
+    other than None / "robot" is refused."""
+    origin_type = getattr(viewer, "origin_type", "world")
+    if origin_type in ("world", "env"):
+        origin = ORIGIN_WORLD
+    elif origin_type == "asset_root":
+        name = getattr(viewer, "asset_name", None)
+        if name not in (None, "robot"):
+            raise ValueError(f"ViewerCfg.asset_name {name!r}: only the robot can be followed")
+        origin = ORIGIN_ASSET_ROOT
+    else:
+        raise ValueError(f"ViewerCfg.origin_type {origin_type!r} is not one of 'world', 'env', 'asset_root'")
+    res = tuple(int(x) for x in getattr(viewer, "resolution", (1280, 720)))
+    cam = Camera(eye=tuple(float(x) for x in viewer.eye), lookat=tuple(float(x) for x in viewer.lookat), origin=origin)
+    return cam, int(getattr(viewer, "env_index", 0)), res
+
+
+def basis(eye, lookat) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(forward, right, up) of a look-at camera with world z up (world y stands in when looking straight up or down)."""
+    eye, lookat = np.asarray(eye, np.float64), np.asarray(lookat, np.float64)
+    f = lookat - eye
+    f = f / np.linalg.norm(f)
+    r = np.cross(f, [0.0, 0.0, 1.0])
+    if float(r @ r) < 1e-12:
+        r = np.cross(f, [0.0, 1.0, 0.0])
+    r = r / np.linalg.norm(r)
+    return f, r, np.cross(r, f)
+
+
+def ray_directions(eye, lookat, fov_y_deg: float, width: int, height: int) -> np.ndarray:
+    """(H, W, 3) unit ray directions through the pixel centres; row 0 is the top of the image."""
+    f, r, u = basis(eye, lookat)
+    t = math.tan(0.5 * math.radians(fov_y_deg))
+    sx = ((np.arange(width) + 0.5) * 2.0 / width - 1.0) * t * (width / height)
+    sy = (1.0 - (np.arange(height) + 0.5) * 2.0 / height) * t
+    d = f[None, None, :] + sx[None, :, None] * r[None, None, :] + sy[:, None, None] * u[None, None, :]
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+def parse_resolution(text: str) -> tuple[int, int]:
+    """"WxH" -> (W, H)."""
+    w, h = text.lower().split("x")
+    return int(w), int(h)
+
+
+def rgba_to_rgb(rgba):
+    """uint32 [..., H, W] packed RGBA (torch or numpy) -> uint8 [..., H, W, 3]."""
+    if hasattr(rgba, "cpu"):
+        rgba = rgba.cpu().numpy()
+    return np.ascontiguousarray(rgba).view(np.uint8).reshape(*rgba.shape, 4)[..., :3]
+
+
+__all__ = ["Camera", "chase_camera", "from_viewer_cfg", "basis", "ray_directions", "parse_resolution", "rgba_to_rgb", "ORIGIN_WORLD",
+           "ORIGIN_ASSET_ROOT", "DEFAULT_FLAGS", "DEPTH_MISS"]

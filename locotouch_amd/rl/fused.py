@@ -79,6 +79,8 @@ class FusedRollout:
         else:
             self._step_torch(t, last)
         self.alg.storage.step = t + 1
+        if self.env.recorder is not None:  # video.VideoRecorder: a render launch on this stream, between two step launches
+            self.env.recorder.after_step()
 
     def _rows(self, t: int, last: bool):
         """(obs, critic obs, next obs ptr, next critic obs ptr) of step t."""

@@ -6,7 +6,8 @@
         --log_dir_distill 2025-... --checkpoint_distill model_7.pt
 
 Flags follow the reference CLI (locotouch/scripts/cli_args.py:11-33,92-124, distill.py:8-20).  The teacher checkpoint is looked
-up as the reference does: logs/rsl_rl/<teacher experiment>/<--load_run>/<--checkpoint> (latest matching).
+up as the reference does: logs/rsl_rl/<teacher experiment>/<--load_run>/<--checkpoint> (latest matching).  `--video` records env 0
+(animated PNG, locotouch_amd/video.py) into <distill log root>/videos/{train,play}.
 """
 from __future__ import annotations
 
@@ -32,13 +33,14 @@ def main() -> None:
     ap.add_argument("--distill_lr", type=float, default=None)
     ap.add_argument("--logger", default=None, choices=["wandb", "tensorboard"])
     ap.add_argument("--play_steps", type=int, default=None, help="play mode: stop after this many env steps (default: run until interrupted)")
+    from locotouch_amd.video import add_video_args
+
+    add_video_args(ap)
     args, _unknown = ap.parse_known_args()
 
     from locotouch_amd.agents import train_cfg
-    from locotouch_amd.compat.runtime import get_checkpoint_path
-    from locotouch_amd.distill import Distillation, distillation_cfg
+    from locotouch_amd.distill import distillation_cfg
     from locotouch_amd.env import make
-    from locotouch_amd.rl import OnPolicyRunner
 
     cfg = distillation_cfg(args.task)
     cfg.device = args.device
@@ -50,6 +52,23 @@ def main() -> None:
     agent = train_cfg(args.task)
     env = make(args.task, num_envs=args.num_envs, device=args.device, seed=args.seed if args.seed is not None else agent["seed"])
     distill_root = os.path.abspath(os.path.join(cfg.log_root_path, cfg.experiment_name))
+    recorder = None
+    if args.video:
+        from locotouch_amd.video import recorder_for
+
+        recorder = recorder_for(env, args, os.path.join(distill_root, "videos", "train" if args.training else "play"))
+    try:
+        _run(args, cfg, agent, env, distill_root)
+    finally:
+        if recorder is not None:
+            recorder.close()
+
+
+def _run(args, cfg, agent, env, distill_root) -> None:
+    from locotouch_amd.compat.runtime import get_checkpoint_path
+    from locotouch_amd.distill import Distillation
+    from locotouch_amd.rl import OnPolicyRunner
+
     if args.training:
         teacher_root = os.path.abspath(os.path.join("logs", "rsl_rl", agent["experiment_name"]))
         resume = get_checkpoint_path(teacher_root, args.load_run or ".*", args.checkpoint or "model_.*.pt")

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Play a trained policy: the reference's `locotouch/scripts/play.py` flow on the MI355X-native env (no renderer: the loop
-steps the policy, prints episode statistics, and optionally exports the actor as TorchScript for the robot-side runtime).
+"""Play a trained policy: the reference's `locotouch/scripts/play.py` flow on the MI355X-native env: the loop steps the policy, prints
+episode statistics, optionally exports the actor as TorchScript for the robot-side runtime, and with `--video` records env 0 (animated
+PNG, locotouch_amd/video.py) into <run>/videos/play.
 
     python -m locotouch_amd.scripts.play --task Isaac-RandCylinderTransportTeacher-LocoTouch-Play-v1 --num_envs 50 --steps 1000 --export
 """
@@ -24,6 +25,9 @@ def main() -> None:
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--steps", type=int, default=None, help="stop after this many env steps (default: run until interrupted)")
     ap.add_argument("--export", action="store_true", help="write <run>/exported/policy.pt (TorchScript: normaliser -> actor)")
+    from locotouch_amd.video import add_video_args
+
+    add_video_args(ap)
     args, _unknown = ap.parse_known_args()
 
     from locotouch_amd.agents import train_cfg
@@ -46,16 +50,25 @@ def main() -> None:
         out = export_policy_as_jit(runner.alg.actor_critic, runner.obs_normalizer if runner.empirical_normalization else None,
                                    path=os.path.join(os.path.dirname(resume), "exported"), filename="policy.pt")
         print(f"[INFO]: Exported policy to: {out}")
+    recorder = None
+    if args.video:
+        from locotouch_amd.video import recorder_for
+
+        recorder = recorder_for(env, args, os.path.join(os.path.dirname(resume), "videos", "play"))
     obs, _ = env.get_observations()
     t, finished, ret_sum = 0, 0, torch.zeros(env.num_envs, device=env.device)
-    with torch.inference_mode():
-        while args.steps is None or t < args.steps:
-            obs, rew, dones, _ = env.step(policy(obs))
-            ret_sum += rew
-            t += 1
-            if t % 200 == 0:
-                log = env.episode_log()
-                print(f"[play] step {t}: " + ", ".join(f"{k}={v:.3f}" for k, v in sorted(log.items()) if k.startswith(("Episode/", "Metrics/"))))
+    try:
+        with torch.inference_mode():
+            while args.steps is None or t < args.steps:
+                obs, rew, dones, _ = env.step(policy(obs))
+                ret_sum += rew
+                t += 1
+                if t % 200 == 0:
+                    log = env.episode_log()
+                    print(f"[play] step {t}: " + ", ".join(f"{k}={v:.3f}" for k, v in sorted(log.items()) if k.startswith(("Episode/", "Metrics/"))))
+    finally:
+        if recorder is not None:
+            recorder.close()
 
 
 if __name__ == "__main__":

@@ -4,8 +4,9 @@
     python -m locotouch_amd.scripts.train --task Isaac-RandCylinderTransportTeacher-LocoTouch-v1 --num_envs 4096 --headless
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m locotouch_amd.scripts.train --task ... (one rank per GPU)
 
-Flags follow the reference CLI (locotouch/scripts/cli_args.py:11-33, train.py:17-29); `--headless` / `--video` are accepted
-and ignored (there is no renderer).  Logs: logs/rsl_rl/<experiment>/<timestamp>/{progress.jsonl, model_<it>.pt, params/{env,agent}.{yaml,pkl}}.
+Flags follow the reference CLI (locotouch/scripts/cli_args.py:11-33, train.py:17-29); `--headless` is accepted and ignored.  `--video`
+records env 0 every --video_interval env steps for --video_length steps (animated PNG, locotouch_amd/video.py) into <log_dir>/videos/train.
+Logs: logs/rsl_rl/<experiment>/<timestamp>/{progress.jsonl, model_<it>.pt, params/{env,agent}.{yaml,pkl}, videos/train/*.apng}.
 """
 from __future__ import annotations
 
@@ -46,6 +47,9 @@ def main() -> None:
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--logger", default="tensorboard")
     ap.add_argument("--log_root", default="logs/rsl_rl")
+    from locotouch_amd.video import add_video_args
+
+    add_video_args(ap)
     args, _unknown = ap.parse_known_args()  # hydra-style overrides of the reference CLI are tolerated and ignored
 
     from locotouch_amd.agents import train_cfg
@@ -68,6 +72,11 @@ def main() -> None:
                cur_gate_external=1 if dist.world_size > 1 else 0)
     log_dir = os.path.join(args.log_root, cfg["experiment_name"], datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
     runner = OnPolicyRunner(env, cfg, log_dir=log_dir, device=device, dist=dist)
+    recorder = None
+    if args.video and dist.is_main:  # only the main rank records
+        from locotouch_amd.video import recorder_for
+
+        recorder = recorder_for(env, args, os.path.join(log_dir, "videos", "train"))
     if args.resume:  # train.py:131-137 of the reference: newest matching run / checkpoint under the experiment's log root
         from locotouch_amd.compat.runtime import get_checkpoint_path
 
@@ -81,6 +90,8 @@ def main() -> None:
     if dist.is_main and runner.history:
         last = runner.history[-1]
         print({k: last[k] for k in ("iter", "Perf/total_fps", "Loss/value_function", "Loss/surrogate", "Loss/learning_rate")})
+    if recorder is not None:
+        recorder.close()
     dist.shutdown()
 
 
