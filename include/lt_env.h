@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LT_ABI_VERSION 19
+#define LT_ABI_VERSION 20
 
 /* error codes */
 #define LT_OK 0
@@ -563,7 +563,10 @@ int lt_rollout_record(int64_t n, float gamma, const float* reward, const int64_t
  * layer - the input rows x / obs and every hidden activation - is SATURATED to [-LT_MLP_INPUT_CLAMP, +LT_MLP_INPUT_CLAMP] before
  * the operand split (64 x must stay a finite f16 number).  Inside that range the results are f32-equivalent (error below an f32
  * GEMM's own rounding); outside it the kernel computes MLP(clamp(x)) per layer, which the reference's fp32 ActorCritic does not.
- * Weights and the outputs of the last layer are not bounded.  The trainer checks the bound on the device once per PPO update
+ * Weights enter as hi + lo / 64 in f16, which resolves an ABSOLUTE 2^-31 per weight (the low half's subnormal step 2^-24, over 64,
+ * halved): the claim holds while a layer's RMS weight is at least ~1e-4 (default-initialised networks sit near 1e-2); below it the
+ * result is that of the weights rounded to hi + lo / 64 - measured on a 128-input layer, 8x an f32 GEMM's error at RMS 5e-5 and 19x at
+ * 2.5e-5 (tests/test_hip_mlp_f64.py, weight sweep).  The outputs of the last layer are not bounded.  The trainer checks the bound on the device once per PPO update
  * (locotouch_amd/rl/mlp.py: PackedPair.domain_max) and warns when it is reached. ---- */
 #define LT_MLP_INPUT_CLAMP 1000
 #define LT_MLP_MAX_LAYERS 6
@@ -671,6 +674,13 @@ int lt_env_render(lt_env* env, const lt_render_desc* desc, const lt_render_view*
 
 /* Device kernel names and static resource usage, for profiling scripts. */
 const char* lt_env_kernel_name(int which);
+/* The instantiation of the MLP kernel an entry point launches for m rows, named as a profiler prints it ("lt_mlp_kernel<RT,KIND,IN>":
+ * RT row tiles of 16 rows per workgroup, KIND -1 / LT_ACT_ELU / 100 = the backward chain, IN the input-staging form), or NULL for a
+ * shape that entry point refuses.  mode LT_MLP_MODE_FORWARD: lt_mlp_forward (d1 NULL) or lt_mlp_forward_pair; LT_MLP_MODE_POLICY:
+ * lt_rollout_policy (d1 NULL) or lt_rollout_policy_value (d1 = the critic); LT_MLP_MODE_BACKWARD: lt_mlp_backward_pair (the FORWARD
+ * descriptors of both networks).  Host-only: no device is touched. */
+enum lt_mlp_mode { LT_MLP_MODE_FORWARD = 0, LT_MLP_MODE_POLICY = 1, LT_MLP_MODE_BACKWARD = 2 };
+const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_null, int64_t m, int mode);
 
 #ifdef __cplusplus
 }

@@ -189,6 +189,8 @@ def load() -> ctypes.CDLL:
     lib.lt_env_render.argtypes = [vp, ctypes.POINTER(LtRenderDesc), ctypes.POINTER(LtRenderView), ctypes.c_int, vp, vp, vp, vp, vp]
     lib.lt_env_kernel_name.argtypes = [ctypes.c_int]
     lib.lt_env_kernel_name.restype = ctypes.c_char_p
+    lib.lt_mlp_kernel_name.argtypes = [dp, dp, ctypes.c_int64, ctypes.c_int]
+    lib.lt_mlp_kernel_name.restype = ctypes.c_char_p
     if lib.lt_cfg_sizeof() != ctypes.sizeof(LtCfg):
         raise ImportError(f"lt_cfg ABI mismatch: C {lib.lt_cfg_sizeof()} vs ctypes {ctypes.sizeof(LtCfg)}")
     if lib.lt_abi_version() != CONSTS["LT_ABI_VERSION"]:
@@ -200,7 +202,7 @@ def load() -> ctypes.CDLL:
 EXPORTS = ["lt_abi_version", "lt_cfg_sizeof", "lt_last_error", "lt_cfg_default", "lt_cfg_preset", "lt_cfg_num_presets", "lt_cfg_preset_id", "lt_cfg_obs_dim", "lt_cfg_tactile_dim", "lt_env_create", "lt_env_tactile_update", "lt_env_defer_gate", "lt_env_gate_update", "lt_env_check", "lt_env_set_row_format", "lt_env_step_rows_profiled", "lt_mlp_forward_pair", "lt_mlp_backward_packed_floats", "lt_mlp_pack_backward", "lt_mlp_backward_blocks", "lt_mlp_backward_pair", "lt_mlp_pack_training", "lt_env_curriculum_apply_global", "lt_gru_forward", "lt_gru_backward", "lt_ppo_loss", "lt_elu_backward_bias", "lt_elu_backward_bias_ws_floats", "lt_elu_backward_bias2", "lt_wgrad", "lt_split_rows", "lt_wgrad_splits", "lt_wgrad_ws_floats", "lt_adam_clip_step", "lt_adam_clip_step_dev", "lt_ppo_lr_rule", "lt_partial_sums", "lt_elu_backward_bias_nblk", "lt_head_wgrad_nblk", "lt_adam_clip_step_ws_floats", "lt_gae", "lt_head_wgrad", "lt_head_wgrad_ws_floats",
            "lt_env_destroy", "lt_env_state_bytes", "lt_env_bind", "lt_env_reset_all", "lt_env_step", "lt_env_step_profiled", "lt_env_eval_terms",
            "lt_env_curriculum_update", "lt_env_step_rows", "lt_env_step_rollout", "lt_env_get_view", "lt_env_set_command_ranges", "lt_rollout_act", "lt_rollout_record", "lt_mlp_packed_floats", "lt_mlp_pack", "lt_mlp_forward", "lt_rollout_policy", "lt_rollout_policy_value",
-           "lt_env_kernel_name", "lt_env_contact_force_bytes", "lt_env_bind_contact_forces", "lt_env_render"]
+           "lt_env_kernel_name", "lt_mlp_kernel_name", "lt_env_contact_force_bytes", "lt_env_bind_contact_forces", "lt_env_render"]
 
 
 def preset_ids() -> list[str]:

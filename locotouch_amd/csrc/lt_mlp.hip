@@ -537,10 +537,10 @@ __device__ __forceinline__ float gate_pass(const MlpArgs& a, int l, float* s_act
   return mx;
 }
 
-// Policy head, first half: the standard-normal draws of this workgroup's rows and the log-density of the sample
-// (Normal.log_prob summed over the 12 actions needs z and sigma only, not mu).  The last wave runs it in the prologue, between
-// requesting the weight ring and the arrival of the input rows - ~250 instructions that would otherwise sit, fetched cold,
-// behind the last layer where nothing overlaps them.  Lane (r, q) owns actions 4q..4q+3 of row r (q == 3: padding).
+// Policy head, first half: the standard-normal draws of this workgroup's rows and the sigma-only part of the log-density,
+// sum of (-log sigma - log sqrt(2 pi)) over the lane's 4 actions.  The last wave runs it in the prologue, between requesting the
+// weight ring and the arrival of the input rows - ~250 instructions that would otherwise sit, fetched cold, behind the last layer
+// where nothing overlaps them.  Lane (r, q) owns actions 4q..4q+3 of row r (q == 3: padding).
 template <int RT>
 __device__ __forceinline__ void policy_noise(const MlpArgs& a, long long row0, int lane, float* s_noise) {
   const int r = lane & 15, q = lane >> 4;
@@ -559,7 +559,7 @@ __device__ __forceinline__ void policy_noise(const MlpArgs& a, long long row0, i
     const float z[4] = {ra * ca, ra * sa, rb * cb, rb * sb};
     float lp = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) lp += -(z[i] * z[i]) * 0.5f - __logf(sgv[i]) - 0.91893853320467274178f;  // Normal.log_prob
+    for (int i = 0; i < 4; ++i) lp += -__logf(sgv[i]) - 0.91893853320467274178f;  // Normal.log_prob without its (x - mu)^2 term (mlp_layer)
     *(float4*)(s_noise + (16 * rt + r) * 16 + 4 * q) = make_float4(z[0], z[1], z[2], z[3]);
     s_noise[(16 * rt + r) * 16 + 12 + q] = lp;
   }
@@ -688,6 +688,14 @@ __device__ __forceinline__ void mlp_layer(const MlpArgs& a, int l, bool last, fl
           const float4 sg = *(const float4*)(a.std12 + 4 * q);
           const long long o = e * 12 + 4 * q;
           const float4 xo = make_float4(out[0][0] + sg.x * zz.x, out[0][1] + sg.y * zz.y, out[0][2] + sg.z * zz.z, out[0][3] + sg.w * zz.w);
+          // Normal(mu, sigma).log_prob of the STORED action, as the reference computes it (ppo.py:135): from the f32 action, not from
+          // the unrounded draw z - at small sigma the rounding of mu + sigma z moves (x - mu) / sigma by ulp(x) / sigma
+          const float sgv[4] = {sg.x, sg.y, sg.z, sg.w}, xv[4] = {xo.x, xo.y, xo.z, xo.w};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float dx = xv[i] - out[0][i];
+            lp -= dx * dx / (2.f * sgv[i] * sgv[i]);
+          }
           *(float4*)(a.st_actions + o) = xo;
           *(float4*)(a.actions_out + o) = xo;
           *(float4*)(a.st_mu + o) = make_float4(out[0][0], out[0][1], out[0][2], out[0][3]);
@@ -1082,9 +1090,29 @@ int launch_shape(DualArgs& d, int nets, size_t* lds_out) {
   return rt;
 }
 
-int launch(DualArgs& d, int nets, hipStream_t s) {
+// The instantiation a launch of `nets` filled networks runs: row tiles, KIND (-1, LT_ACT_ELU or KIND_GATE) and IN.  launch() and
+// lt_mlp_kernel_name() both decide through here, so the query cannot drift from what runs.
+struct Form {
+  int rt, kind, in;
   size_t lds;
-  const int rt = launch_shape(d, nets, &lds);
+};
+Form launch_form(DualArgs& d, int nets) {
+  Form f;
+  f.rt = launch_shape(d, nets, &f.lds);
+  const bool gate = d.net[0].mode == MODE_BACKWARD;
+  const bool elu = d.net[0].activation == LT_ACT_ELU && (nets == 1 || d.net[1].activation == LT_ACT_ELU);
+  f.kind = gate ? KIND_GATE : (elu ? LT_ACT_ELU : -1);
+  // the input-staging form as a compile-time constant when both networks of the launch take the same one (ELU kernels only)
+  int in = input_kind(d.net[0]);
+  if (nets == 2 && input_kind(d.net[1]) != in) in = IN_ANY;
+  f.in = f.kind == LT_ACT_ELU ? in : IN_ANY;
+  return f;
+}
+
+int launch(DualArgs& d, int nets, hipStream_t s) {
+  const Form f = launch_form(d, nets);
+  const int rt = f.rt;
+  const size_t lds = f.lds;
   const long long t0 = (d.net[0].m + 15) / 16, t1 = nets == 2 ? (d.net[1].m + 15) / 16 : 0;
   const long long b0 = (t0 + rt - 1) / rt, b1 = (t1 + rt - 1) / rt;
   d.split = (int)b0;
@@ -1096,11 +1124,8 @@ int launch(DualArgs& d, int nets, hipStream_t s) {
   d.blocks_per_net = (int)b0;
   const long long nblocks = d.xcd_split ? (b0 + 3) / 4 * 8 : b0 + b1;
   const dim3 grid((unsigned)nblocks), block(64 * NW);
-  const bool gate = d.net[0].mode == MODE_BACKWARD;
-  const bool elu = d.net[0].activation == LT_ACT_ELU && (nets == 1 || d.net[1].activation == LT_ACT_ELU);
-  // the input-staging form as a compile-time constant when both networks of the launch take the same one
-  int in = input_kind(d.net[0]);
-  if (nets == 2 && input_kind(d.net[1]) != in) in = IN_ANY;
+  const bool gate = f.kind == KIND_GATE, elu = f.kind == LT_ACT_ELU;
+  const int in = f.in;
   const hipError_t e = rt == 4 ? launch_rt<4>(d, elu, gate, in, grid, block, lds, s)
                      : rt == 2 ? launch_rt<2>(d, elu, gate, in, grid, block, lds, s) : launch_rt<1>(d, elu, gate, in, grid, block, lds, s);
   if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
@@ -1301,6 +1326,45 @@ int lt_rollout_policy_value(const lt_mlp_desc* actor, const float* actor_packed,
   d.net[1].mode = MODE_FORWARD;
   d.net[1].packed = critic_packed; d.net[1].x = critic_obs; d.net[1].m = n; d.net[1].y = values;
   return launch(d, 2, (hipStream_t)stream);
+}
+
+// The instantiation an entry point launches for these networks and rows (launch_form, the function launch() decides with), named as
+// a profiler prints it; NULL for a shape the entry point refuses.  The table is launch_rt()'s list of forms, row tiles 1, 2, 4.
+static_assert(LT_MLP_MODE_FORWARD == MODE_FORWARD && LT_MLP_MODE_POLICY == MODE_POLICY && LT_MLP_MODE_BACKWARD == MODE_BACKWARD, "lt_mlp_mode");
+const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1, int64_t m, int mode) {
+  static const char* const names[3][6] = {
+      {"lt_mlp_kernel<1,-1,0>", "lt_mlp_kernel<1,1,0>", "lt_mlp_kernel<1,1,1>", "lt_mlp_kernel<1,1,2>", "lt_mlp_kernel<1,1,3>", "lt_mlp_kernel<1,100,0>"},
+      {"lt_mlp_kernel<2,-1,0>", "lt_mlp_kernel<2,1,0>", "lt_mlp_kernel<2,1,1>", "lt_mlp_kernel<2,1,2>", "lt_mlp_kernel<2,1,3>", "lt_mlp_kernel<2,100,0>"},
+      {"lt_mlp_kernel<4,-1,0>", "lt_mlp_kernel<4,1,0>", "lt_mlp_kernel<4,1,1>", "lt_mlp_kernel<4,1,2>", "lt_mlp_kernel<4,1,3>", "lt_mlp_kernel<4,100,0>"}};
+  if (!d0 || m <= 0) return nullptr;
+  const int nets = d1 ? 2 : 1;
+  DualArgs d = {};
+  if (mode == MODE_BACKWARD) {  // (lt_mlp_backward_pair: always two networks)
+    lt_mlp_desc b0, b1;
+    if (!d1 || !backward_desc(d0, &b0) || !backward_desc(d1, &b1)) return nullptr;
+    fill_args(&b0, d.net[0]);
+    fill_args(&b1, d.net[1]);
+  } else if (mode == MODE_FORWARD || mode == MODE_POLICY) {
+    const lt_mlp_desc* ds[2] = {d0, d1};
+    for (int k = 0; k < nets; ++k) {
+      if (!desc_ok(ds[k])) return nullptr;
+      fill_args(ds[k], d.net[k]);
+      d.net[k].mode = MODE_FORWARD;
+      if (mode == MODE_FORWARD && nets == 2)  // lt_mlp_forward_pair writes the hidden activations by groups of 4
+        for (int l = 0; l + 1 < ds[k]->num_layers; ++l)
+          if (ds[k]->dims[l + 1] & 3) return nullptr;
+    }
+    if (mode == MODE_POLICY && d0->dims[d0->num_layers] != 12) return nullptr;
+  } else {
+    return nullptr;
+  }
+  for (int k = 0; k < nets; ++k) {
+    d.net[k].m = m;
+    if (k == 0 || mode == MODE_BACKWARD) d.net[k].mode = mode;
+  }
+  const Form f = launch_form(d, nets);
+  const int form = f.kind == KIND_GATE ? 5 : f.kind == -1 ? 0 : 1 + f.in;  // IN_ANY .. IN_F32X2 = 0 .. 3
+  return names[f.rt == 4 ? 2 : f.rt - 1][form];
 }
 
 

@@ -72,8 +72,10 @@ __global__ __launch_bounds__(256) void lt_rollout_act_kernel(const ActArgs a) {
       a.actions_out[e * 12 + k] = x;
       a.st_mu[e * 12 + k] = mu;
       a.st_sigma[e * 12 + k] = sg;
-      // Normal.log_prob: -(x-mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi)
-      lp = -(z * z) * 0.5f - __logf(sg) - 0.91893853320467274178f;
+      // Normal.log_prob of the STORED action x (ppo.py:135): -(x-mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi) - from x, not from z:
+      // at small sigma the rounding of mu + sigma z moves (x - mu) / sigma by ulp(x) / sigma
+      const float dx = x - mu;
+      lp = -(dx * dx) / (2.f * sg * sg) - __logf(sg) - 0.91893853320467274178f;
     }
     // sum over the 16-lane row (DPP row shifts via shuffles; 4 steps)
     lp += __shfl_xor(lp, 8, 64); lp += __shfl_xor(lp, 4, 64); lp += __shfl_xor(lp, 2, 64); lp += __shfl_xor(lp, 1, 64);

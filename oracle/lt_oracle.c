@@ -1892,6 +1892,23 @@ static void step_one(const lt_cfg* cfg, void* arena, const lt_layout* L, const f
   scatter(&E, arena, L, e);
 }
 
+/* The policy head's N(0,1) draws (csrc/lt_mlp.hip policy_noise, csrc/lt_rollout.hip lt_rollout_act_kernel) in double: for env e and
+ * action group q, the uniforms of stream 0x400 + q; (u0, u1) give actions 4q, 4q + 1 and (u2, u3) actions 4q + 2, 4q + 3 by Box-Muller,
+ * r = sqrt(-2 log(1 - u)).  z: [n][12].  Double in both builds (the uniforms are exact f32 numbers). */
+void lt_oracle_policy_normals(uint64_t seed, int64_t n, uint64_t step, double* z) {
+  const double two_pi = 6.283185307179586476925286766559;
+  for (int64_t e = 0; e < n; ++e)
+    for (int q = 0; q < 3; ++q) {
+      float u[4];
+      lt_rng4(seed, (uint32_t)e, step, 0x400u + (uint32_t)q, u);
+      for (int h = 0; h < 2; ++h) {
+        const double r = sqrt(-2.0 * log(1.0 - (double)u[2 * h])), t = two_pi * (double)u[2 * h + 1];
+        z[e * 12 + 4 * q + 2 * h] = r * cos(t);
+        z[e * 12 + 4 * q + 2 * h + 1] = r * sin(t);
+      }
+    }
+}
+
 int lt_oracle_obs_dim(const lt_cfg* cfg) { return (cfg->task == LT_TASK_LOCOMOTION ? 45 : 58) * cfg->obs_history; }
 
 static int64_t* counters(void* arena, const lt_layout* L) { return (int64_t*)((char*)arena + L->off_counters); }

@@ -92,6 +92,8 @@ int lt_oracle_curriculum_update(const lt_cfg* cfg, void* arena, const float* rec
  * arena twin of lt_env_curriculum_apply_global */
 void lt_oracle_gate_on_sums(const lt_cfg* cfg, float* P, const float r[8], float inv_n, int allow_lin, int allow_ang, int out[5]);
 int lt_oracle_curriculum_apply_global(const lt_cfg* cfg, void* arena, const float* ring_sums, int nsteps, int64_t n_total);
+/* the policy head's 12 standard-normal draws per env, [n][12], in double from the kernels' Philox keying (stream 0x400 + group) */
+void lt_oracle_policy_normals(uint64_t seed, int64_t n, uint64_t step, double* z);
 void lt_oracle_obs_push(const int* term_dims, int nterms, int hist, const float* frame, int fill, float* row);
 
 #ifdef __cplusplus

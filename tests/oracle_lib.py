@@ -74,6 +74,7 @@ def load(precision: str = "f32") -> ctypes.CDLL:
     lib.lt_oracle_curriculum.argtypes = [P(_abi.LtCfg), P(f32), ctypes.c_int64, P(f32), P(f32)]
     lib.lt_oracle_command_resample_u.argtypes = [P(_abi.LtCfg), P(f32), P(f32), P(f32), f32, f32, P(f32), P(f32), P(f32), P(f32)]
     lib.lt_oracle_material_u.argtypes = [P(f32), P(f32), P(f32), P(f32), P(f32)]
+    lib.lt_oracle_policy_normals.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint64, P(ctypes.c_double)]
     lib.lt_oracle_taxel_forces.argtypes = [P(f32), P(f32), P(f32), P(f32)]
     lib.lt_oracle_tactile_signals_u.argtypes = [P(_abi.LtCfg)] + [P(f32)] * 5
     lib.lt_oracle_tactile_channels_u.argtypes = [P(_abi.LtCfg), ctypes.c_int] + [P(f32)] * 13
@@ -100,6 +101,13 @@ def f64_twin(test):
     twin.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != "precision"])
     twin.__name__ = twin.__qualname__ = test.__name__ + "_f64"
     return twin
+
+
+def policy_normals(seed: int, n: int, step: int) -> np.ndarray:
+    """The policy head's N(0,1) draws [n][12] in double (lt_oracle_policy_normals)."""
+    z = np.zeros((n, 12), np.float64)
+    load("f64").lt_oracle_policy_normals(seed, n, step, z.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return z
 
 
 def fptr(a: np.ndarray):

@@ -6,6 +6,8 @@ import ctypes
 
 import pytest
 
+from tests.mlp_ref import ref_chain
+
 pytestmark = pytest.mark.gpu
 
 
@@ -24,27 +26,7 @@ def _nets(out0=12, out1=1, hidden=(512, 256, 128), d=348, seed=0, hidden1=None):
     return stack(out0, hidden), stack(out1, hidden1 or hidden)
 
 
-def _ref_chain(seq, x, dy):
-    """f64: (dz per hidden layer, dW per layer, db per layer)."""
-    import torch
-    import torch.nn as nn
-
-    lin = [m for m in seq if isinstance(m, nn.Linear)]
-    a, acts = x.double(), []
-    for l in lin[:-1]:
-        a = torch.nn.functional.elu(a @ l.weight.double().t() + l.bias.double())
-        acts.append(a)
-    g = dy.double()
-    dz, dw, db = {}, {}, {}
-    L = len(lin)
-    for l in range(L - 1, -1, -1):
-        inp = acts[l - 1] if l > 0 else x.double()
-        if l < L - 1:
-            g = g * torch.where(acts[l] > 0, torch.ones_like(acts[l]), acts[l] + 1.0)
-            dz[l] = g
-        dw[l], db[l] = g.t() @ inp, g.sum(0)
-        g = g @ lin[l].weight.double()
-    return dz, dw, db
+_ref_chain = ref_chain  # (moved to tests/mlp_ref.py; the name stays importable)
 
 
 @pytest.mark.parametrize("m,scale", [(24576, 1e-5), (6144, 1.0), (1000, 1e-8), (37, 1e-3)])
