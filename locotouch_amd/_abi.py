@@ -1,9 +1,10 @@
 """ctypes mirror of include/lt_env.h and loader of the HIP library (the product path).
 
-The `lt_cfg` structure is parsed mechanically from the header, so the Python mirror cannot drift from
-the C ABI (a size check against `lt_cfg_sizeof()` guards it at load time).  There is deliberately NO
-fallback: if `liblocotouch_env.so` is missing the import fails loudly - nothing on the product path
-ever routes through the CPU oracle.
+Everything is parsed mechanically from the header - the `LT_*` constants, every structure and the signature of every entry
+point - so the Python mirror cannot drift from the C ABI (a size check against `lt_cfg_sizeof()` guards it at load time) and
+nobody counts pointers by hand.  `call` is the one way the package launches: it converts tensors / addresses / None to
+pointers and raises on a non-zero status.  There is deliberately NO fallback: if `liblocotouch_env.so` is missing the import
+fails loudly - nothing on the product path ever routes through the CPU oracle.
 """
 from __future__ import annotations
 
@@ -16,54 +17,87 @@ REPO = os.path.dirname(_HERE)
 HEADER = os.path.join(REPO, "include", "lt_env.h")
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
-_CTYPES = {"float": ctypes.c_float, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "int64_t": ctypes.c_int64}
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
+            "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+_DECL = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*(?:const\b\s*)?)*)(\w*)\s*((?:\[[^\]]*\]\s*)*)")
 
 
-def _parse_header():
-    src = open(HEADER).read()
-    src_nc = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src_nc = re.sub(r"//[^\n]*", "", src_nc)
-    consts = {}
-    for m in re.finditer(r"#define\s+(LT_\w+)\s+\(?(-?\d+)\)?\s*$", src_nc, flags=re.M):
-        consts[m.group(1)] = int(m.group(2))
-    # enums
-    for m in re.finditer(r"enum\s+\w+\s*\{(.*?)\};", src_nc, flags=re.S):
+def _ctype(decl, structs, opaque, consts, typed, param):
+    """(name, ctypes type) of one C declarator, by the one rule of this binding: scalars by their C type; `const char*` ->
+    c_char_p; pointer to a header structure -> POINTER(it); `size_t*` -> POINTER(c_size_t); pointer to pointer ->
+    POINTER(c_void_p); every other pointer (and an array parameter, which decays to one) -> c_void_p, or with `typed` the
+    typed POINTER.  None if the rule does not cover it."""
+    m = _DECL.fullmatch(decl.strip())
+    if not m:
+        return None
+    base, stars, name, dims = m.groups()
+    depth = stars.count("*")
+    try:
+        dims = [sum(int(t) if t.strip().isdigit() else consts[t.strip()] for t in d.split("+")) for d in re.findall(r"\[([^\]]*)\]", dims)]
+    except KeyError:
+        return None
+    if param and dims:  # an array parameter decays to a pointer to its elements
+        depth, dims = depth + 1, dims[1:]
+    t = structs.get(base) or _SCALARS.get(base)  # None: void, char or an opaque structure - pointers only
+    if (t is None and base not in opaque and base not in ("void", "char")) or depth > 2 or (param and dims):
+        return None
+    if depth == 0 and t is None:
+        return None
+    if depth == 1 and base == "char":
+        t = ctypes.c_char_p
+    elif depth == 1:
+        t = ctypes.POINTER(t) if t is not None and (typed or base in structs or base == "size_t") else ctypes.c_void_p
+    elif depth == 2:
+        t = ctypes.POINTER(ctypes.POINTER(t) if typed and t is not None else ctypes.c_void_p)
+    for d in reversed(dims):
+        t = t * d
+    return name, t
+
+
+def parse_header(text: str, typed: bool = False, structs: dict | None = None, bases: dict | None = None):
+    """(constants, structures by C name, {entry point: (restype, [argtypes])}) of a C header in the style of lt_env.h.
+    `structs`: structures other headers define; `bases`: Python base class per C structure name (for methods); `typed`: data
+    pointers become typed POINTERs instead of c_void_p.  Whatever it cannot type raises ImportError naming it."""
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+(LT_\w+)\s+\(?(-?\d+)\)?\s*$", text, flags=re.M)}
+    for m in re.finditer(r"enum\s+\w+\s*\{(.*?)\};", text, flags=re.S):
         val = -1
-        for item in m.group(1).split(","):
-            item = item.strip()
-            if not item:
-                continue
-            if "=" in item:
-                name, v = [x.strip() for x in item.split("=")]
-                val = int(v, 0)
-            else:
-                name = item
-                val += 1
+        for item in filter(None, (x.strip() for x in m.group(1).split(","))):
+            name, _, v = (x.strip() for x in item.partition("="))
+            val = int(v, 0) if v else val + 1
             consts[name] = val
-    body = re.search(r"typedef struct lt_cfg \{(.*?)\} lt_cfg;", src_nc, flags=re.S).group(1)
-    fields = []
-    for line in body.split(";"):
-        line = line.strip()
-        if not line:
-            continue
-        m = re.match(r"(\w+)\s+(\w+)((?:\[\w+\])*)$", line)
+    structs, opaque = dict(structs or {}), set(re.findall(r"typedef\s+struct\s+\w+\s+(\w+)\s*;", text))
+    for m in re.finditer(r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = []
+        for line in filter(None, (x.strip() for x in m.group(1).split(";"))):
+            first, *more = line.split(",")
+            base = _DECL.match(first.strip())
+            for decl in [first] + [f"{base.group(1) if base else ''} {x}" for x in more]:  # `float a[3], b[4];`
+                field = _ctype(decl, structs, opaque, consts, typed, param=False)
+                if field is None:
+                    raise ImportError(f"cannot type member {decl.strip()!r} of {m.group(2)}")
+                fields.append(field)
+        pyname = "".join(w.capitalize() for w in m.group(2).split("_"))
+        structs[m.group(2)] = type(pyname, ((bases or {}).get(m.group(2), ctypes.Structure),), {"_fields_": fields})
+    rest = re.sub(r"^[ \t]*#[^\n]*$|typedef\s+struct\b[^;{]*(\{.*?\})?[^;{]*;|enum\s+\w+\s*\{.*?\};|extern\s+\"C\"\s*\{", "", text, flags=re.S | re.M)
+    protos = {}
+    for stmt in filter(None, (x.strip() for x in rest.split(";"))):
+        m = re.fullmatch(r"(.*?)\b(\w+)\s*\(([^()]*)\)", stmt, flags=re.S)
         if not m:
-            raise RuntimeError(f"cannot parse lt_cfg member: {line!r}")
-        ctype, name, dims = m.groups()
-        t = _CTYPES[ctype]
-        for d in reversed(re.findall(r"\[(\w+)\]", dims)):
-            t = t * (int(d) if d.isdigit() else consts[d])
-        fields.append((name, t))
-    return consts, fields
+            if stmt == "}":  # closes extern "C"
+                continue
+            raise ImportError(f"cannot parse declaration {stmt!r}")
+        ret, name, args = m.groups()
+        res = (None, None) if ret.strip() == "void" else _ctype(ret, structs, opaque, consts, typed, param=False)
+        args = [] if args.strip() == "void" else [_ctype(a, structs, opaque, consts, typed, param=True) for a in args.split(",")]
+        if res is None or None in args:
+            raise ImportError(f"cannot type prototype {name}: {' '.join(stmt.split())!r}")
+        protos[name] = (res[1], [t for _, t in args])
+    return consts, structs, protos
 
 
-CONSTS, _CFG_FIELDS = _parse_header()
-globals().update(CONSTS)
-
-
-class LtCfg(ctypes.Structure):
-    _fields_ = _CFG_FIELDS
-
+class _CfgMethods(ctypes.Structure):
     def copy(self) -> "LtCfg":
         new = LtCfg()
         ctypes.memmove(ctypes.byref(new), ctypes.byref(self), ctypes.sizeof(self))
@@ -82,25 +116,22 @@ class LtCfg(ctypes.Structure):
         return {name: py(getattr(self, name)) for name, *_ in self._fields_ if not name.startswith("_")}
 
 
-class LtView(ctypes.Structure):
-    _fields_ = [("ptr", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("ndim", ctypes.c_int32),
-                ("shape", ctypes.c_int64 * 3), ("stride", ctypes.c_int64 * 3)]
+CONSTS, STRUCTS, SIGNATURES = parse_header(open(HEADER).read(), bases={"lt_cfg": _CfgMethods})
+globals().update(CONSTS)
+LtCfg, LtView, LtMlpDesc = STRUCTS["lt_cfg"], STRUCTS["lt_view"], STRUCTS["lt_mlp_desc"]
+LtRenderView, LtRenderDesc = STRUCTS["lt_render_view"], STRUCTS["lt_render_desc"]
+EXPORTS = list(SIGNATURES)
 
-
-class LtMlpDesc(ctypes.Structure):
-    _fields_ = [("num_layers", ctypes.c_int32), ("dims", ctypes.c_int32 * (CONSTS["LT_MLP_MAX_LAYERS"] + 1)), ("activation", ctypes.c_int32), ("input_format", ctypes.c_int32)]
-
-
-class LtRenderView(ctypes.Structure):
-    _fields_ = [("env_id", ctypes.c_int32), ("origin", ctypes.c_int32), ("eye", ctypes.c_float * 3), ("lookat", ctypes.c_float * 3),
-                ("fov_y_deg", ctypes.c_float)]
-
-
-class LtRenderDesc(ctypes.Structure):
-    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("flags", ctypes.c_int32), ("light_dir", ctypes.c_float * 3)]
-
+# Entry points that return a VALUE, not an LT_* status (the header's types cannot tell the two apart): never through `call`.
+VALUE_QUERIES = frozenset({
+    "lt_abi_version", "lt_cfg_sizeof", "lt_cfg_num_presets", "lt_cfg_preset_id", "lt_cfg_obs_dim", "lt_cfg_tactile_dim", "lt_last_error",
+    "lt_wgrad_splits", "lt_wgrad_ws_floats", "lt_elu_backward_bias_ws_floats", "lt_head_wgrad_ws_floats", "lt_adam_clip_step_ws_floats",
+    "lt_elu_backward_bias_nblk", "lt_head_wgrad_nblk", "lt_mlp_backward_blocks", "lt_env_kernel_name", "lt_mlp_kernel_name"})
+if not VALUE_QUERIES <= set(EXPORTS) or any(SIGNATURES[n][0] is not ctypes.c_int for n in set(EXPORTS) - VALUE_QUERIES):
+    raise ImportError("_abi.VALUE_QUERIES does not match include/lt_env.h: a query it names is gone, or a new entry point returns no status")
 
 _lib = None
+_calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
 
 def load() -> ctypes.CDLL:
@@ -112,85 +143,12 @@ def load() -> ctypes.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    lib.lt_abi_version.restype = ctypes.c_int
-    lib.lt_cfg_sizeof.restype = ctypes.c_size_t
-    lib.lt_last_error.restype = ctypes.c_char_p
-    lib.lt_cfg_default.argtypes = [ctypes.c_int, ctypes.POINTER(LtCfg)]
-    lib.lt_cfg_obs_dim.argtypes = [ctypes.POINTER(LtCfg)]
-    lib.lt_cfg_tactile_dim.argtypes = [ctypes.POINTER(LtCfg)]
-    lib.lt_cfg_preset.argtypes = [ctypes.c_char_p, ctypes.POINTER(LtCfg)]
-    lib.lt_cfg_preset_id.argtypes = [ctypes.c_int]
-    lib.lt_cfg_preset_id.restype = ctypes.c_char_p
-    lib.lt_env_create.argtypes = [ctypes.POINTER(LtCfg), ctypes.POINTER(ctypes.c_void_p)]
-    lib.lt_env_destroy.argtypes = [ctypes.c_void_p]
-    lib.lt_env_state_bytes.argtypes = [ctypes.POINTER(LtCfg), ctypes.POINTER(ctypes.c_size_t)]
-    lib.lt_env_bind.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-    lib.lt_env_reset_all.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.lt_env_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.lt_env_step_profiled.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-    lib.lt_env_step_rows_profiled.argtypes = [ctypes.c_void_p] * 7 + [ctypes.POINTER(ctypes.c_float)]
-    lib.lt_env_eval_terms.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.lt_env_defer_gate.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.lt_env_gate_update.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.lt_env_check.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.lt_env_set_row_format.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.lt_env_tactile_update.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    lib.lt_env_contact_force_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
-    lib.lt_env_bind_contact_forces.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
-    _vp = ctypes.c_void_p
-    lib.lt_gru_forward.argtypes = [_vp] * 5 + [ctypes.c_int] * 3 + [_vp] * 3
-    lib.lt_gru_backward.argtypes = [_vp] * 6 + [ctypes.c_int] * 3 + [_vp] * 5
-    lib.lt_ppo_loss.argtypes = [_vp] * 11 + [ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int] + [_vp] * 5
-    lib.lt_elu_backward_bias.argtypes = [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp]
-    lib.lt_elu_backward_bias2.argtypes = [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]
-    lib.lt_wgrad.argtypes = [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]
-    lib.lt_split_rows.argtypes = [_vp, _vp, ctypes.c_int64, _vp]
-    lib.lt_wgrad_splits.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int]
-    lib.lt_wgrad_ws_floats.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int]
-    lib.lt_wgrad_ws_floats.restype = ctypes.c_int64
-    lib.lt_elu_backward_bias_ws_floats.argtypes = [ctypes.c_int64, ctypes.c_int]
-    lib.lt_elu_backward_bias_ws_floats.restype = ctypes.c_int64
-    lib.lt_head_wgrad.argtypes = [_vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]
-    lib.lt_head_wgrad_ws_floats.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int]
-    lib.lt_head_wgrad_ws_floats.restype = ctypes.c_int64
-    lib.lt_gae.argtypes = [_vp] * 4 + [ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp]
-    lib.lt_adam_clip_step.argtypes = [_vp] * 4 + [ctypes.c_int64] + [ctypes.c_float] * 6 + [ctypes.c_int64, _vp, _vp, _vp]
-    lib.lt_adam_clip_step_dev.argtypes = [_vp] * 4 + [ctypes.c_int64, ctypes.c_float, _vp] + [ctypes.c_float] * 4 + [ctypes.c_int64, _vp, _vp, _vp]
-    lib.lt_ppo_lr_rule.argtypes = [_vp] + [ctypes.c_float] * 4 + [_vp] * 4 + [ctypes.c_int, _vp]
-    lib.lt_partial_sums.argtypes = [ctypes.c_int] + [_vp] * 8
-    lib.lt_elu_backward_bias_nblk.argtypes = [ctypes.c_int64]
-    lib.lt_head_wgrad_nblk.argtypes = [ctypes.c_int64]
-    lib.lt_adam_clip_step_ws_floats.argtypes = [ctypes.c_int64]
-    lib.lt_adam_clip_step_ws_floats.restype = ctypes.c_int64
-    lib.lt_env_curriculum_apply_global.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]
-    lib.lt_env_curriculum_update.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.lt_env_get_view.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(LtView)]
-    lib.lt_env_set_command_ranges.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int,
-                                              ctypes.c_float, ctypes.c_void_p]
-    vp = ctypes.c_void_p
-    lib.lt_rollout_act.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_uint64] + [vp] * 15
-    lib.lt_rollout_record.argtypes = [ctypes.c_int64, ctypes.c_float] + [vp] * 9
-    lib.lt_env_step_rows.argtypes = [ctypes.c_void_p] + [vp] * 6
-    dp = ctypes.POINTER(LtMlpDesc)
-    lib.lt_mlp_packed_floats.argtypes = [dp, ctypes.POINTER(ctypes.c_size_t)]
-    lib.lt_mlp_pack.argtypes = [dp, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
-    lib.lt_mlp_forward.argtypes = [dp, vp, vp, ctypes.c_int64, vp, vp]
-    lib.lt_mlp_forward_pair.argtypes = [dp, vp, vp, dp, vp, vp, ctypes.c_int64, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int, vp]
-    pvp = ctypes.POINTER(vp)
-    lib.lt_mlp_backward_packed_floats.argtypes = [dp, ctypes.POINTER(ctypes.c_size_t)]
-    lib.lt_mlp_pack_backward.argtypes = [dp, pvp, vp, vp]
-    lib.lt_mlp_pack_training.argtypes = [dp, pvp, pvp, vp, vp, dp, pvp, pvp, vp, vp, vp]
-    lib.lt_mlp_backward_blocks.argtypes = [dp, dp, ctypes.c_int64]
-    lib.lt_mlp_backward_blocks.restype = ctypes.c_int64
-    lib.lt_mlp_backward_pair.argtypes = [dp, vp, vp, pvp, pvp, pvp, dp, vp, vp, pvp, pvp, pvp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp]
-    lib.lt_rollout_policy.argtypes = [dp, vp, vp, ctypes.c_int64, ctypes.c_uint64, vp, ctypes.c_int64] + [vp] * 7
-    lib.lt_rollout_policy_value.argtypes = [dp, vp, vp, dp, vp, vp, vp, ctypes.c_int64, ctypes.c_uint64, vp, ctypes.c_int64] + [vp] * 7
-    lib.lt_env_step_rollout.argtypes = [ctypes.c_void_p] + [vp] * 6 + [ctypes.c_float, vp, vp, vp]
-    lib.lt_env_render.argtypes = [vp, ctypes.POINTER(LtRenderDesc), ctypes.POINTER(LtRenderView), ctypes.c_int, vp, vp, vp, vp, vp]
-    lib.lt_env_kernel_name.argtypes = [ctypes.c_int]
-    lib.lt_env_kernel_name.restype = ctypes.c_char_p
-    lib.lt_mlp_kernel_name.argtypes = [dp, dp, ctypes.c_int64, ctypes.c_int]
-    lib.lt_mlp_kernel_name.restype = ctypes.c_char_p
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+        if name not in VALUE_QUERIES:
+            _calls[name] = (fn, [ptr if t is ctypes.c_void_p else _ref if issubclass(t, ctypes._Pointer) and issubclass(t._type_, ctypes.Structure)
+                                 else None for t in argtypes])
     if lib.lt_cfg_sizeof() != ctypes.sizeof(LtCfg):
         raise ImportError(f"lt_cfg ABI mismatch: C {lib.lt_cfg_sizeof()} vs ctypes {ctypes.sizeof(LtCfg)}")
     if lib.lt_abi_version() != CONSTS["LT_ABI_VERSION"]:
@@ -199,10 +157,45 @@ def load() -> ctypes.CDLL:
     return lib
 
 
-EXPORTS = ["lt_abi_version", "lt_cfg_sizeof", "lt_last_error", "lt_cfg_default", "lt_cfg_preset", "lt_cfg_num_presets", "lt_cfg_preset_id", "lt_cfg_obs_dim", "lt_cfg_tactile_dim", "lt_env_create", "lt_env_tactile_update", "lt_env_defer_gate", "lt_env_gate_update", "lt_env_check", "lt_env_set_row_format", "lt_env_step_rows_profiled", "lt_mlp_forward_pair", "lt_mlp_backward_packed_floats", "lt_mlp_pack_backward", "lt_mlp_backward_blocks", "lt_mlp_backward_pair", "lt_mlp_pack_training", "lt_env_curriculum_apply_global", "lt_gru_forward", "lt_gru_backward", "lt_ppo_loss", "lt_elu_backward_bias", "lt_elu_backward_bias_ws_floats", "lt_elu_backward_bias2", "lt_wgrad", "lt_split_rows", "lt_wgrad_splits", "lt_wgrad_ws_floats", "lt_adam_clip_step", "lt_adam_clip_step_dev", "lt_ppo_lr_rule", "lt_partial_sums", "lt_elu_backward_bias_nblk", "lt_head_wgrad_nblk", "lt_adam_clip_step_ws_floats", "lt_gae", "lt_head_wgrad", "lt_head_wgrad_ws_floats",
-           "lt_env_destroy", "lt_env_state_bytes", "lt_env_bind", "lt_env_reset_all", "lt_env_step", "lt_env_step_profiled", "lt_env_eval_terms",
-           "lt_env_curriculum_update", "lt_env_step_rows", "lt_env_step_rollout", "lt_env_get_view", "lt_env_set_command_ranges", "lt_rollout_act", "lt_rollout_record", "lt_mlp_packed_floats", "lt_mlp_pack", "lt_mlp_forward", "lt_rollout_policy", "lt_rollout_policy_value",
-           "lt_env_kernel_name", "lt_mlp_kernel_name", "lt_env_contact_force_bytes", "lt_env_bind_contact_forces", "lt_env_render"]
+def ptr(x):
+    """c_void_p of a tensor's data_ptr(), of an integer address (0 -> NULL) or of None (NULL); a ctypes object passes through."""
+    if x is None or isinstance(x, int):
+        return ctypes.c_void_p(x or None)
+    data_ptr = getattr(x, "data_ptr", None)
+    return ctypes.c_void_p(data_ptr()) if data_ptr else x
+
+
+def _ref(x):
+    return ctypes.byref(x) if isinstance(x, ctypes.Structure) else x
+
+
+def stream(device=None) -> ctypes.c_void_p:
+    """torch's current stream on `device` as the `void* stream` argument of a launch."""
+    import torch
+
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def ptr_array(tensors):
+    """HOST array of device pointers (None entries -> NULL): the `const float* const*` operands."""
+    return (ctypes.c_void_p * max(1, len(tensors)))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def call(name: str, *args) -> None:
+    """Call a status-returning entry point: tensors / addresses / None become pointers, structures are passed by reference
+    (which positions: decided once per function in load(), from the header), and a non-zero status raises with lt_last_error()."""
+    try:
+        fn, conv = _calls[name]
+    except KeyError:
+        if name in VALUE_QUERIES:
+            raise TypeError(f"{name} returns a value, not a status: call load().{name}(...)") from None
+        if _lib is not None:
+            raise
+        load()
+        fn, conv = _calls[name]
+    rc = fn(*[a if c is None else c(a) for c, a in zip(conv, args, strict=True)])
+    if rc:
+        check(rc, name)
 
 
 def preset_ids() -> list[str]:

@@ -77,26 +77,25 @@ class LocoTouchVecEnv:
         self.max_episode_length_s = float(self.cfg.episode_length_s)
         self.max_episode_length = int(self.cfg.max_episode_length)
         self._handle = ctypes.c_void_p()
-        _abi.check(self._lib.lt_env_create(ctypes.byref(self.cfg), ctypes.byref(self._handle)), "lt_env_create")
+        _abi.call("lt_env_create", self.cfg, ctypes.byref(self._handle))
         nbytes = ctypes.c_size_t()
-        _abi.check(self._lib.lt_env_state_bytes(ctypes.byref(self.cfg), ctypes.byref(nbytes)), "lt_env_state_bytes")
+        _abi.call("lt_env_state_bytes", self.cfg, ctypes.byref(nbytes))
         with torch.cuda.device(self.device):
             self.arena = torch.zeros(nbytes.value + 256, dtype=torch.uint8, device=self.device)
         pad = (-self.arena.data_ptr()) % 256
         self._arena_aligned = self.arena[pad:pad + nbytes.value]
-        _abi.check(self._lib.lt_env_bind(self._handle, ctypes.c_void_p(self._arena_aligned.data_ptr()), nbytes.value), "lt_env_bind")
+        _abi.call("lt_env_bind", self._handle, self._arena_aligned, nbytes.value)
         self._views: dict[int, torch.Tensor] = {}
         self.contact_force_vectors = bool(contact_force_vectors)
         self._fvec_mem = self._fvec = None
         if self.contact_force_vectors:
             fbytes = ctypes.c_size_t()
-            _abi.check(self._lib.lt_env_contact_force_bytes(self._handle, ctypes.byref(fbytes)), "lt_env_contact_force_bytes")
+            _abi.call("lt_env_contact_force_bytes", self._handle, ctypes.byref(fbytes))
             with torch.cuda.device(self.device):
                 self._fvec_mem = torch.zeros(fbytes.value + 256, dtype=torch.uint8, device=self.device)
             fpad = (-self._fvec_mem.data_ptr()) % 256
             self._fvec = self._fvec_mem[fpad:fpad + fbytes.value].view(torch.float32).view(3, 14, -1, 4)
-            _abi.check(self._lib.lt_env_bind_contact_forces(self._handle, ctypes.c_void_p(self._fvec.data_ptr()), fbytes.value),
-                       "lt_env_bind_contact_forces")
+            _abi.call("lt_env_bind_contact_forces", self._handle, self._fvec, fbytes.value)
         self.obs_policy = self.view(C["LT_F_OBS_POLICY"])
         self.obs_critic = self.view(C["LT_F_OBS_CRITIC"])
         self.reward_buf = self.view(C["LT_F_REWARD"])
@@ -128,7 +127,7 @@ class LocoTouchVecEnv:
         if field in self._views:
             return self._views[field]
         v = _abi.LtView()
-        _abi.check(self._lib.lt_env_get_view(self._handle, field, ctypes.byref(v)), "lt_env_get_view")
+        _abi.call("lt_env_get_view", self._handle, field, v)
         dtype = _TORCH_DTYPES[v.dtype]
         esz = torch.empty((), dtype=dtype).element_size()
         off = v.ptr - self._arena_aligned.data_ptr()
@@ -157,11 +156,8 @@ class LocoTouchVecEnv:
     def unwrapped(self):
         return self
 
-    def _stream(self) -> ctypes.c_void_p:
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def reset(self):
-        _abi.check(self._lib.lt_env_reset_all(self._handle, self._stream()), "lt_env_reset_all")
+        _abi.call("lt_env_reset_all", self._handle, _abi.stream(self.device))
         return self.get_observations()
 
     def _extras(self) -> dict:
@@ -177,7 +173,7 @@ class LocoTouchVecEnv:
 
     def tactile_update(self) -> None:
         """lt_env_tactile_update: for drivers of the launch-only row/rollout entry points (lt_env_step runs it itself)."""
-        _abi.check(self._lib.lt_env_tactile_update(self._handle, self._stream()), "lt_env_tactile_update")
+        _abi.call("lt_env_tactile_update", self._handle, _abi.stream(self.device))
 
     def get_observations(self):
         return self.obs_policy, self._extras()
@@ -187,38 +183,34 @@ class LocoTouchVecEnv:
         reference: the trainer copies what it keeps, loco_rl/loco_rl/storage/rollout_storage.py:86-97)."""
         if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.num_envs, 12):
             actions = actions.to(torch.float32).reshape(self.num_envs, 12).contiguous()
-        _abi.check(self._lib.lt_env_step(self._handle, ctypes.c_void_p(actions.data_ptr()), self._stream()), "lt_env_step")
+        _abi.call("lt_env_step", self._handle, actions, _abi.stream(self.device))
         if self.recorder is not None:
             self.recorder.after_step()
         return self.obs_policy, self.reward_buf, self.dones_buf, self._extras()
 
     def step_raw(self, actions_ptr: int) -> None:
         """Launch-only variant for captured (hipGraph) rollouts: no tensor bookkeeping on the host."""
-        _abi.check(self._lib.lt_env_step(self._handle, ctypes.c_void_p(actions_ptr), self._stream()), "lt_env_step")
+        _abi.call("lt_env_step", self._handle, actions_ptr, _abi.stream(self.device))
 
     def step_rows_raw(self, actions_ptr: int, prev_policy: int, prev_critic: int, next_policy: int, next_critic: int) -> None:
         """lt_env_step_rows: observation rows read from / written to caller storage (0 = arena rows)."""
-        vp = ctypes.c_void_p
-        _abi.check(self._lib.lt_env_step_rows(self._handle, vp(actions_ptr), vp(prev_policy or None), vp(prev_critic or None),
-                                              vp(next_policy or None), vp(next_critic or None), self._stream()), "lt_env_step_rows")
+        _abi.call("lt_env_step_rows", self._handle, actions_ptr, prev_policy, prev_critic, next_policy, next_critic, _abi.stream(self.device))
 
     def step_rollout_raw(self, actions_ptr: int, prev_policy: int, prev_critic: int, next_policy: int, next_critic: int, values_ptr: int,
                          gamma: float, st_rewards_ptr: int, st_dones_ptr: int) -> None:
         """lt_env_step_rollout: step_rows_raw + the storage writes of the transition (bootstrapped reward, dones)."""
-        vp = ctypes.c_void_p
-        _abi.check(self._lib.lt_env_step_rollout(self._handle, vp(actions_ptr), vp(prev_policy or None), vp(prev_critic or None),
-                                                 vp(next_policy or None), vp(next_critic or None), vp(values_ptr), float(gamma),
-                                                 vp(st_rewards_ptr), vp(st_dones_ptr), self._stream()), "lt_env_step_rollout")
+        _abi.call("lt_env_step_rollout", self._handle, actions_ptr, prev_policy, prev_critic, next_policy, next_critic, values_ptr,
+                  float(gamma), st_rewards_ptr, st_dones_ptr, _abi.stream(self.device))
 
     def defer_gate(self, mode: int) -> None:
         """lt_env_defer_gate (include/lt_env.h): where the population pass of a step (curriculum decision, population gate, step
         counter) runs - 0 behind every step (default), 1 the caller's `gate_update()`, 2 chained into the next step launch (a
         chain ends with `gate_update()`; until then the command block and the counters lag)."""
-        _abi.check(self._lib.lt_env_defer_gate(self._handle, int(mode)), "lt_env_defer_gate")
+        _abi.call("lt_env_defer_gate", self._handle, int(mode))
 
     def gate_update(self) -> None:
         """The outstanding population pass, if any (lt_env_gate_update)."""
-        _abi.check(self._lib.lt_env_gate_update(self._handle, self._stream()), "lt_env_gate_update")
+        _abi.call("lt_env_gate_update", self._handle, _abi.stream(self.device))
 
     def set_row_format(self, dtype) -> None:
         """Element format of the rows behind step_rows_raw / step_rollout_raw pointers: torch.float32 or torch.bfloat16
@@ -226,11 +218,11 @@ class LocoTouchVecEnv:
         import torch
 
         fmt = {torch.float32: _abi.CONSTS["LT_ROWS_F32"], torch.bfloat16: _abi.CONSTS["LT_ROWS_BF16"]}[dtype]
-        _abi.check(self._lib.lt_env_set_row_format(self._handle, fmt), "lt_env_set_row_format")
+        _abi.call("lt_env_set_row_format", self._handle, fmt)
 
     def check(self) -> None:
         """Raise if a chained step launch lost its population-pass announcement (lt_env_check; waits for the stream)."""
-        _abi.check(self._lib.lt_env_check(self._handle, self._stream()), "lt_env_check")
+        _abi.call("lt_env_check", self._handle, _abi.stream(self.device))
 
     @property
     def handle(self) -> ctypes.c_void_p:
@@ -239,17 +231,15 @@ class LocoTouchVecEnv:
     def step_profiled(self, actions: torch.Tensor) -> float:
         """lt_env_step with HIP events around the step kernel; returns its duration in ms (host-syncing)."""
         ms = ctypes.c_float()
-        _abi.check(self._lib.lt_env_step_profiled(self._handle, ctypes.c_void_p(actions.data_ptr()), self._stream(), ctypes.byref(ms)),
-                   "lt_env_step_profiled")
+        _abi.call("lt_env_step_profiled", self._handle, actions, _abi.stream(self.device), ctypes.byref(ms))
         return float(ms.value)
 
     def step_rows_profiled(self, actions: torch.Tensor, prev_policy: torch.Tensor, prev_critic: torch.Tensor, next_policy: torch.Tensor,
                            next_critic: torch.Tensor) -> float:
         """lt_env_step_rows with HIP events around the step kernel (rows in the current row format); duration in ms."""
         ms = ctypes.c_float()
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        _abi.check(self._lib.lt_env_step_rows_profiled(self._handle, p(actions), p(prev_policy), p(prev_critic), p(next_policy),
-                                                       p(next_critic), self._stream(), ctypes.byref(ms)), "lt_env_step_rows_profiled")
+        _abi.call("lt_env_step_rows_profiled", self._handle, actions, prev_policy, prev_critic, next_policy, next_critic,
+                  _abi.stream(self.device), ctypes.byref(ms))
         return float(ms.value)
 
     def request_termination(self, mask: torch.Tensor, time_out: bool = False) -> None:
@@ -260,13 +250,12 @@ class LocoTouchVecEnv:
         bits.bitwise_or_(mask.to(device=self.device, dtype=torch.int32) << C["LT_TIMEOUT_REQUEST_BIT" if time_out else "LT_TERM_REQUEST_BIT"])
 
     def eval_terms(self) -> None:
-        _abi.check(self._lib.lt_env_eval_terms(self._handle, self._stream()), "lt_env_eval_terms")
+        _abi.call("lt_env_eval_terms", self._handle, _abi.stream(self.device))
 
     def curriculum_update(self, records: torch.Tensor) -> None:
         """The curriculum pass of the step kernel's tail on caller-supplied records [N][4] (parity-test hook)."""
         assert records.dtype == torch.float32 and records.is_contiguous() and records.shape == (self.num_envs, 4) and records.is_cuda
-        _abi.check(self._lib.lt_env_curriculum_update(self._handle, ctypes.c_void_p(records.data_ptr()), self._stream()),
-                   "lt_env_curriculum_update")
+        _abi.call("lt_env_curriculum_update", self._handle, records, _abi.stream(self.device))
 
     def curriculum_sync(self, dist, nsteps: int) -> None:
         """Multi-rank curriculum gate (cfg.cur_gate_external): all-reduce the population sums of the last
@@ -276,15 +265,13 @@ class LocoTouchVecEnv:
             return
         ring = self.view(C["LT_F_GATE_RING"]).clone()
         dist.all_reduce_sum_(ring)
-        _abi.check(self._lib.lt_env_curriculum_apply_global(self._handle, ctypes.c_void_p(ring.data_ptr()), int(nsteps),
-                                                            int(self.num_envs) * int(dist.world_size), self._stream()),
-                   "lt_env_curriculum_apply_global")
+        _abi.call("lt_env_curriculum_apply_global", self._handle, ring, int(nsteps), int(self.num_envs) * int(dist.world_size),
+                  _abi.stream(self.device))
         self._gate_ring_keepalive = ring  # the kernel reads it asynchronously
 
     def set_command_ranges(self, ranges, zero_steps: int, rel_standing: float) -> None:
         arr = (ctypes.c_float * 6)(*[float(x) for x in ranges])
-        _abi.check(self._lib.lt_env_set_command_ranges(self._handle, arr, int(zero_steps), float(rel_standing), self._stream()),
-                   "lt_env_set_command_ranges")
+        _abi.call("lt_env_set_command_ranges", self._handle, arr, int(zero_steps), float(rel_standing), _abi.stream(self.device))
 
     # ---- logging (host sync only when asked) -------------------------------------------------------
     def episode_log(self) -> dict:
@@ -398,9 +385,7 @@ class LocoTouchVecEnv:
         dep = buf("depth", torch.float32, shape, depth)
         idt = buf("ids", torch.int32, shape, ids)
         pos = buf("poses", torch.float32, (len(env_ids), 17, 7), poses)
-        p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
-        _abi.check(self._lib.lt_env_render(self._handle, ctypes.byref(desc), views, len(env_ids), p(rgba), p(dep), p(idt), p(pos),
-                                           self._stream()), "lt_env_render")
+        _abi.call("lt_env_render", self._handle, desc, views, len(env_ids), rgba, dep, idt, pos, _abi.stream(self.device))
         return res
 
     @property

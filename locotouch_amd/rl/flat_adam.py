@@ -9,8 +9,6 @@ a `.to()`) is detected and re-adopted before the next step.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from .. import _abi
@@ -39,8 +37,7 @@ class FlatAdam:
         self.flat_g = torch.zeros(self.n, device=dev)
         self.flat_m = torch.zeros(self.n, device=dev)
         self.flat_v = torch.zeros(self.n, device=dev)
-        self._lib = _abi.load()
-        self._ws = torch.empty(int(self._lib.lt_adam_clip_step_ws_floats(self.n)), device=dev)
+        self._ws = torch.empty(_abi.load().lt_adam_clip_step_ws_floats(self.n), device=dev)
         self.grad_norm = torch.zeros(1, device=dev)
         self._adopt()
 
@@ -120,11 +117,9 @@ class FlatAdam:
         g = self.optimizer.param_groups[0]
         self.step_count += 1
         b1, b2 = g["betas"]
-        vp = ctypes.c_void_p
-        _abi.check(self._lib.lt_adam_clip_step_dev(vp(self.flat_p.data_ptr()), vp(self.flat_g.data_ptr()), vp(self.flat_m.data_ptr()), vp(self.flat_v.data_ptr()),
-                                                   self.n, float(max_norm or 0.0), vp(lr_dev.data_ptr()), float(b1), float(b2), float(g["eps"]),
-                                                   float(g["weight_decay"]), self.step_count, vp(self._ws.data_ptr()), vp(self.grad_norm.data_ptr()),
-                                                   vp(torch.cuda.current_stream(self.flat_p.device).cuda_stream)), "lt_adam_clip_step_dev")
+        _abi.call("lt_adam_clip_step_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n, float(max_norm or 0.0), lr_dev,
+                  float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), self.step_count, self._ws, self.grad_norm,
+                  _abi.stream(self.flat_p.device))
         self._step_t.fill_(float(self.step_count))
 
     def step(self, max_norm: float, gathered: bool = False) -> None:
@@ -135,9 +130,7 @@ class FlatAdam:
         g = self.optimizer.param_groups[0]
         self.step_count += 1
         b1, b2 = g["betas"]
-        vp = ctypes.c_void_p
-        _abi.check(self._lib.lt_adam_clip_step(vp(self.flat_p.data_ptr()), vp(self.flat_g.data_ptr()), vp(self.flat_m.data_ptr()), vp(self.flat_v.data_ptr()),
-                                               self.n, float(max_norm or 0.0), float(g["lr"]), float(b1), float(b2), float(g["eps"]),
-                                               float(g["weight_decay"]), self.step_count, vp(self._ws.data_ptr()), vp(self.grad_norm.data_ptr()),
-                                               vp(torch.cuda.current_stream(self.flat_p.device).cuda_stream)), "lt_adam_clip_step")
+        _abi.call("lt_adam_clip_step", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n, float(max_norm or 0.0), float(g["lr"]),
+                  float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), self.step_count, self._ws, self.grad_norm,
+                  _abi.stream(self.flat_p.device))
         self._step_t.fill_(float(self.step_count))

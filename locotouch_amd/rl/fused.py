@@ -16,7 +16,6 @@ critic on a side stream.
 """
 from __future__ import annotations
 
-import ctypes
 
 import torch
 
@@ -37,7 +36,7 @@ class FusedRollout:
         ac = alg.actor_critic
         if getattr(ac, "noise_std_type", "scalar") != "scalar":
             raise ValueError("FusedRollout supports the 'scalar' noise_std_type of the LocoTouch agent configs")
-        self.env, self.alg, self.lib = env, alg, _abi.load()
+        self.env, self.alg = env, alg
         self.device = env.device
         self.actions = torch.zeros(env.num_envs, 12, device=self.device)
         # Philox key of the policy noise: the kernels key the draws by the LOCAL row index, so rank r (env_index_offset = r * N) gets its
@@ -69,10 +68,6 @@ class FusedRollout:
             st = alg.storage
             self._tail_rows = (torch.zeros_like(st.observations[0]), torch.zeros_like(st.privileged_observations[0]))
 
-    @staticmethod
-    def _p(t: torch.Tensor) -> ctypes.c_void_p:
-        return ctypes.c_void_p(t.data_ptr())
-
     def step(self, t: int, last: bool) -> None:
         if self.actor_mlp is not None:
             self._step_packed(t, last)
@@ -100,31 +95,24 @@ class FusedRollout:
 
     def policy_value_launch(self, t: int) -> None:
         """The MLP launch of step t alone (bench.py times it for the MFMA roofline entry)."""
-        env, alg, st, p = self.env, self.alg, self.alg.storage, self._p
         obs, cobs, _, _ = self._rows(t, False)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _abi.check(self.lib.lt_rollout_policy_value(
-            ctypes.byref(self.actor_mlp.desc), p(self.actor_mlp.packed), p(obs), ctypes.byref(self.critic_mlp.desc),
-            p(self.critic_mlp.packed), p(cobs), p(st.values[t]), env.num_envs, self._noise_seed, p(self._act_counter), t,
-            p(alg.actor_critic.std.data), p(st.actions[t]), p(st.mu[t]), p(st.sigma[t]), p(st.actions_log_prob[t]), p(self.actions), stream),
-            "lt_rollout_policy_value")
+        self._policy_value(t, obs, cobs)
+
+    def _policy_value(self, t: int, obs, cobs) -> None:
+        st = self.alg.storage
+        _abi.call("lt_rollout_policy_value", self.actor_mlp.desc, self.actor_mlp.packed, obs, self.critic_mlp.desc, self.critic_mlp.packed,
+                  cobs, st.values[t], self.env.num_envs, self._noise_seed, self._act_counter, t, self.alg.actor_critic.std.data,
+                  st.actions[t], st.mu[t], st.sigma[t], st.actions_log_prob[t], self.actions, _abi.stream(self.device))
 
     def _step_packed(self, t: int, last: bool) -> None:
         """Two launches on ONE stream (a linear graph: cross-queue edges of a forked graph cost more than they return on this stack):
         [actor + critic MLPs + sampling] -> [env step + storage record (+ the previous step's population pass on an idle wave)]."""
-        env, alg, st, p = self.env, self.alg, self.alg.storage, self._p
-        ac = alg.actor_critic
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        n = env.num_envs
+        env, alg, st = self.env, self.alg, self.alg.storage
         obs, cobs, nxt_p, nxt_c = self._rows(t, last)
         if not self.rows_in_storage:
             st.observations[t].copy_(obs)
             st.privileged_observations[t].copy_(cobs)
-        _abi.check(self.lib.lt_rollout_policy_value(
-            ctypes.byref(self.actor_mlp.desc), p(self.actor_mlp.packed), p(obs), ctypes.byref(self.critic_mlp.desc),
-            p(self.critic_mlp.packed), p(cobs), p(st.values[t]), n, self._noise_seed, p(self._act_counter), t, p(ac.std.data),
-            p(st.actions[t]), p(st.mu[t]), p(st.sigma[t]), p(st.actions_log_prob[t]), p(self.actions), stream),
-            "lt_rollout_policy_value")
+        self._policy_value(t, obs, cobs)
         prev = (obs.data_ptr(), cobs.data_ptr()) if self.rows_in_storage else (0, 0)
         env.step_rollout_raw(self.actions.data_ptr(), prev[0], prev[1], nxt_p, nxt_c, st.values[t].data_ptr(), float(alg.gamma),
                              st.rewards[t].data_ptr(), st.dones[t].data_ptr())
@@ -132,18 +120,16 @@ class FusedRollout:
     def _step_torch(self, t: int, last: bool) -> None:
         """torch modules for the networks (shapes outside lt_mlp's limits): GEMMs -> lt_rollout_act -> env step -> record,
         critic and post pass on forked streams."""
-        env, alg, st, p = self.env, self.alg, self.alg.storage, self._p
+        env, alg, st = self.env, self.alg, self.alg.storage
         ac = alg.actor_critic
         main = torch.cuda.current_stream(self.device)
-        stream = ctypes.c_void_p(main.cuda_stream)
+        stream = _abi.stream(self.device)
         n = env.num_envs
-        null = ctypes.c_void_p(None)
         obs, cobs, nxt_p, nxt_c = self._rows(t, last)
         mu = ac.actor(obs)
-        rows = (null, null, null, null) if self.rows_in_storage else (p(obs), p(cobs), p(st.observations[t]), p(st.privileged_observations[t]))
-        _abi.check(self.lib.lt_rollout_act(n, env.num_obs, self._noise_seed, p(self._act_counter), p(mu), p(ac.std.data), null,
-                                           *rows, p(st.actions[t]), p(st.mu[t]), p(st.sigma[t]), null,
-                                           p(st.actions_log_prob[t]), p(self.actions), stream), "lt_rollout_act")
+        rows = (None, None, None, None) if self.rows_in_storage else (obs, cobs, st.observations[t], st.privileged_observations[t])
+        _abi.call("lt_rollout_act", n, env.num_obs, self._noise_seed, self._act_counter, mu, ac.std.data, None, *rows,
+                  st.actions[t], st.mu[t], st.sigma[t], None, st.actions_log_prob[t], self.actions, stream)
         self.side.wait_stream(main)
         with torch.cuda.stream(self.side):
             value = ac.critic(cobs)
@@ -151,9 +137,8 @@ class FusedRollout:
         env.step_rows_raw(self.actions.data_ptr(), prev[0], prev[1], nxt_p, nxt_c)
         main.wait_stream(self.side)
         value.record_stream(main)
-        _abi.check(self.lib.lt_rollout_record(n, float(alg.gamma), p(env.reward_buf), p(env.dones_buf), p(env.time_out_buf), p(value),
-                                              p(st.rewards[t]), p(st.dones[t]), p(st.values[t]), p(self._act_counter), stream),
-                   "lt_rollout_record")
+        _abi.call("lt_rollout_record", n, float(alg.gamma), env.reward_buf, env.dones_buf, env.time_out_buf, value,
+                  st.rewards[t], st.dones[t], st.values[t], self._act_counter, stream)
 
     def rollout(self, num_steps: int) -> None:
         """`num_steps` consecutive steps into storage slots 0.. (inference mode, capturable)."""

@@ -6,7 +6,6 @@ PyTorch-op chain of `PPO._eager_update` in tests/test_hip_ppo_graph.py.  CUDA te
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
@@ -17,14 +16,12 @@ from .. import _abi
 class _FusedPPOLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, std, value, actions, old_logp, adv, returns, old_values, old_mu, old_sigma, clip, vcoef, ecoef, clipped, idx):
-        lib = _abi.load()
         m, a = mu.shape
         c = lambda t: t.detach().contiguous()  # noqa: E731
         mu_c, std_c, v_c = c(mu), c(std), c(value).view(-1)
         dmu = torch.empty_like(mu_c)
         dvalue = torch.empty(m, device=mu.device, dtype=torch.float32)
         acc = torch.empty(24, device=mu.device, dtype=torch.float32)
-        vp = ctypes.c_void_p
         args = [c(actions), c(old_logp).view(-1), c(adv).view(-1), c(returns).view(-1), c(old_values).view(-1), c(old_mu), c(old_sigma)]
         rows = args[0].shape[0]
         if (any(t.shape[0] != rows for t in args) or any(t.shape != (rows, a) for t in (args[0], args[5], args[6]))
@@ -32,10 +29,8 @@ class _FusedPPOLoss(torch.autograd.Function):
             raise ValueError("fused_ppo_loss: batch tensors do not match the minibatch / index")
         idx_c = None if idx is None else c(idx)
         out = torch.empty(24, device=mu.device, dtype=torch.float32)
-        _abi.check(lib.lt_ppo_loss(vp(mu_c.data_ptr()), vp(std_c.data_ptr()), vp(v_c.data_ptr()), *[vp(t.data_ptr()) for t in args],
-                                   vp(None if idx_c is None else idx_c.data_ptr()), m, a,
-                                   float(clip), float(vcoef), float(ecoef), int(bool(clipped)), vp(dmu.data_ptr()), vp(dvalue.data_ptr()), vp(acc.data_ptr()),
-                                   vp(out.data_ptr()), vp(torch.cuda.current_stream(mu.device).cuda_stream)), "lt_ppo_loss")
+        _abi.call("lt_ppo_loss", mu_c, std_c, v_c, *args, idx_c, m, a, float(clip), float(vcoef), float(ecoef), int(bool(clipped)),
+                  dmu, dvalue, acc, out, _abi.stream(mu.device))
         # out: the finished scalars, written by a one-wave launch behind the main kernel (a dozen 12-float tensor ops otherwise)
         ctx.save_for_backward(dmu, dvalue.view_as(value), out[8:8 + a])
         return out[0], out[1], out[2], out[3], out[4]

@@ -109,31 +109,22 @@ class _GRUSequenceHip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, h0, w_ih, w_hh, b_ih, b_hh):
-        import ctypes
-
         from .. import _abi
 
-        lib = _abi.load()
         L, B, _ = x.shape
         H = w_hh.shape[1]
         ig = (x.reshape(L * B, -1) @ w_ih.t()).view(L, B, 3 * H)
         h0c, w_hh_c = h0.contiguous(), w_hh.contiguous()
         out = x.new_empty(L, B, H)
         ws = x.new_empty(L, B, 4 * H)
-        vp = ctypes.c_void_p
-        stream = vp(torch.cuda.current_stream(x.device).cuda_stream)
-        _abi.check(lib.lt_gru_forward(vp(ig.data_ptr()), vp(h0c.data_ptr()), vp(w_hh_c.data_ptr()), vp(b_ih.data_ptr()), vp(b_hh.data_ptr()),
-                                      L, B, H, vp(out.data_ptr()), vp(ws.data_ptr()), stream), "lt_gru_forward")
+        _abi.call("lt_gru_forward", ig, h0c, w_hh_c, b_ih, b_hh, L, B, H, out, ws, _abi.stream(x.device))
         ctx.save_for_backward(x, h0c, w_ih, w_hh_c, out, ws)
         return out, out[-1]
 
     @staticmethod
     def backward(ctx, dout, dhn):
-        import ctypes
-
         from .. import _abi
 
-        lib = _abi.load()
         x, h0, w_ih, w_hh, out, ws = ctx.saved_tensors
         L, B, _ = x.shape
         H = w_hh.shape[1]
@@ -142,12 +133,8 @@ class _GRUSequenceHip(torch.autograd.Function):
         dhg = x.new_empty(L, B, 3 * H)
         scratch = x.new_empty(3, B, H)
         dh0 = x.new_empty(B, H)
-        vp = ctypes.c_void_p
-        stream = vp(torch.cuda.current_stream(x.device).cuda_stream)
-        dhn_p = vp(dhn.contiguous().data_ptr()) if dhn is not None else vp(None)
-        _abi.check(lib.lt_gru_backward(vp(dout.data_ptr()), dhn_p, vp(out.data_ptr()), vp(ws.data_ptr()), vp(h0.data_ptr()), vp(w_hh.data_ptr()),
-                                       L, B, H, vp(dig.data_ptr()), vp(dhg.data_ptr()), vp(scratch.data_ptr()), vp(dh0.data_ptr()), stream),
-                   "lt_gru_backward")
+        dhn = dhn.contiguous() if dhn is not None else None
+        _abi.call("lt_gru_backward", dout, dhn, out, ws, h0, w_hh, L, B, H, dig, dhg, scratch, dh0, _abi.stream(x.device))
         return _finish_backward(ctx, x, h0, w_ih, out, dig, dhg, dh0)
 
 

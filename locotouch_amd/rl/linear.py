@@ -100,18 +100,13 @@ def _head_wgrad_ok(dy: torch.Tensor, x: torch.Tensor) -> bool:
 
 
 def _head_wgrad(dy: torch.Tensor, x: torch.Tensor):
-    import ctypes
-
     from .. import _abi
 
-    lib = _abi.load()
     m, n, k = x.shape[0], dy.shape[1], x.shape[1]
     dw = torch.empty(n, k, device=x.device, dtype=torch.float32)
     db = torch.empty(n, device=x.device, dtype=torch.float32)
-    ws = torch.empty(int(lib.lt_head_wgrad_ws_floats(m, n, k)), device=x.device, dtype=torch.float32)
-    vp = ctypes.c_void_p
-    _abi.check(lib.lt_head_wgrad(vp(dy.data_ptr()), vp(x.data_ptr()), 0, m, n, k, vp(dw.data_ptr()), vp(db.data_ptr()), vp(ws.data_ptr()),
-                                 vp(torch.cuda.current_stream(x.device).cuda_stream)), "lt_head_wgrad")
+    ws = torch.empty(_abi.load().lt_head_wgrad_ws_floats(m, n, k), device=x.device, dtype=torch.float32)
+    _abi.call("lt_head_wgrad", dy, x, 0, m, n, k, dw, db, ws, _abi.stream(x.device))
     return dw, db
 
 
@@ -129,20 +124,15 @@ class _LinearELU(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, da):
-        import ctypes
-
         from .. import _abi
 
         x, weight, a = ctx.saved_tensors
-        lib = _abi.load()
         m, n = a.shape
         da = da if da.is_contiguous() else da.contiguous()
         dz = torch.empty_like(a)
         db = torch.empty(n, device=a.device, dtype=a.dtype)
-        ws = torch.empty(int(lib.lt_elu_backward_bias_ws_floats(m, n)), device=a.device, dtype=torch.float32)
-        vp = ctypes.c_void_p
-        _abi.check(lib.lt_elu_backward_bias(vp(da.data_ptr()), vp(a.data_ptr()), m, n, float(ctx.alpha), vp(dz.data_ptr()), vp(db.data_ptr()),
-                                            vp(ws.data_ptr()), vp(torch.cuda.current_stream(a.device).cuda_stream)), "lt_elu_backward_bias")
+        ws = torch.empty(_abi.load().lt_elu_backward_bias_ws_floats(m, n), device=a.device, dtype=torch.float32)
+        _abi.call("lt_elu_backward_bias", da, a, m, n, float(ctx.alpha), dz, db, ws, _abi.stream(a.device))
         dx = dz @ weight if ctx.needs_input_grad[0] else None
         dw = _wgrad(dz, x, ctx.splits) if ctx.needs_input_grad[1] else None
         return dx, dw, (db if ctx.needs_input_grad[2] else None), None, None

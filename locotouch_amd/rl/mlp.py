@@ -10,12 +10,14 @@ whenever the optimizer has stepped, e.g. at the start of every rollout - it is s
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 import torch.nn as nn
 
 from .. import _abi
 
+USE_FUSED_BACKWARD = os.environ.get("LT_FUSED_BACKWARD", "1") != "0"  # 0: dz @ W as library GEMMs + lt_elu_backward_bias per layer
 _ACT_IDS = {nn.ELU: "LT_ACT_ELU", nn.ReLU: "LT_ACT_RELU", nn.Tanh: "LT_ACT_TANH", nn.Identity: "LT_ACT_NONE"}
 
 
@@ -62,41 +64,42 @@ class PackedMLP:
         self.desc, self.linears = got
         self.lib = _abi.load()
         n = ctypes.c_size_t()
-        _abi.check(self.lib.lt_mlp_packed_floats(ctypes.byref(self.desc), ctypes.byref(n)), "lt_mlp_packed_floats")
+        _abi.call("lt_mlp_packed_floats", self.desc, ctypes.byref(n))
         dev = self.linears[0].weight.device
-        self.packed = torch.zeros(int(n.value), device=dev, dtype=torch.float32)
+        self.packed = torch.zeros(n.value, device=dev, dtype=torch.float32)
+        self.bpacked = None  # the transposed streams of the fused backward pass (pack_backward / PackedPair.pack_training)
+        self.in_dtype = torch.float32
         self.out_features = self.linears[-1].out_features
         self.in_features = self.linears[0].in_features
         self.pack()
 
-    @staticmethod
-    def _stream() -> ctypes.c_void_p:
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    def weight_ptrs(self):
+        return _abi.ptr_array([l.weight for l in self.linears])
+
+    def bias_ptrs(self):
+        return _abi.ptr_array([l.bias for l in self.linears])
 
     def pack(self) -> None:
-        L = len(self.linears)
-        arr = ctypes.c_void_p * L
-        w = arr(*[l.weight.data_ptr() for l in self.linears])
-        b = arr(*[l.bias.data_ptr() for l in self.linears])
         for l in self.linears:
             if not l.weight.is_contiguous():
                 raise ValueError("Linear.weight must be contiguous")
-        _abi.check(self.lib.lt_mlp_pack(ctypes.byref(self.desc), w, b, ctypes.c_void_p(self.packed.data_ptr()), self._stream()), "lt_mlp_pack")
+        _abi.call("lt_mlp_pack", self.desc, self.weight_ptrs(), self.bias_ptrs(), self.packed, _abi.stream())
 
     def backward_ok(self) -> bool:
         """The chain of input gradients can run through the MLP kernel (lt_mlp_backward_pair): ELU, hidden widths % 8, <= 64 outputs."""
         n = ctypes.c_size_t()
         return self.lib.lt_mlp_backward_packed_floats(ctypes.byref(self.desc), ctypes.byref(n)) == 0
 
+    def alloc_bpacked(self) -> None:
+        if self.bpacked is None:
+            n = ctypes.c_size_t()
+            _abi.call("lt_mlp_backward_packed_floats", self.desc, ctypes.byref(n))
+            self.bpacked = torch.zeros(n.value, device=self.packed.device, dtype=torch.float32)
+
     def pack_backward(self) -> None:
         """The transposed weights in the kernel's stream layout (the backward chain multiplies by W^T); re-packed at every optimizer step."""
-        if getattr(self, "bpacked", None) is None:
-            n = ctypes.c_size_t()
-            _abi.check(self.lib.lt_mlp_backward_packed_floats(ctypes.byref(self.desc), ctypes.byref(n)), "lt_mlp_backward_packed_floats")
-            self.bpacked = torch.zeros(int(n.value), device=self.packed.device, dtype=torch.float32)
-        L = len(self.linears)
-        w = (ctypes.c_void_p * L)(*[l.weight.data_ptr() for l in self.linears])
-        _abi.check(self.lib.lt_mlp_pack_backward(ctypes.byref(self.desc), w, ctypes.c_void_p(self.bpacked.data_ptr()), self._stream()), "lt_mlp_pack_backward")
+        self.alloc_bpacked()
+        _abi.call("lt_mlp_pack_backward", self.desc, self.weight_ptrs(), self.bpacked, _abi.stream())
 
     def set_input_format(self, dtype: torch.dtype) -> None:
         """float32 rows (default) or bfloat16 rows (BASELINE config 5: widened exactly to f32 inside the kernel)."""
@@ -108,16 +111,32 @@ class PackedMLP:
         self.in_dtype = dtype
 
     def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        if x.dim() != 2 or x.shape[1] != self.in_features or x.dtype != getattr(self, "in_dtype", torch.float32) or not x.is_contiguous():
+        if x.dim() != 2 or x.shape[1] != self.in_features or x.dtype != self.in_dtype or not x.is_contiguous():
             raise ValueError("x must be a contiguous [m, in_features] tensor of the input format")
         m = x.shape[0]
         if out is None:
             out = torch.empty(m, self.out_features, device=x.device, dtype=torch.float32)
-        _abi.check(self.lib.lt_mlp_forward(ctypes.byref(self.desc), ctypes.c_void_p(self.packed.data_ptr()), ctypes.c_void_p(x.data_ptr()), m,
-                                           ctypes.c_void_p(out.data_ptr()), self._stream()), "lt_mlp_forward")
+        _abi.call("lt_mlp_forward", self.desc, self.packed, x, m, out, _abi.stream())
         return out
 
     __call__ = forward
+
+
+def _alloc_outputs(nets, m, device):
+    ys, acts = [], []
+    for net in nets:
+        dims = [net.desc.dims[i] for i in range(net.desc.num_layers + 1)]
+        ys.append(torch.empty(m, dims[-1], device=device, dtype=torch.float32))
+        acts.append([torch.empty(m, d, device=device, dtype=torch.float32) for d in dims[1:-1]])
+    return ys, acts
+
+
+def _forward_pair(nets, x0, x1, acts_split: bool):
+    """lt_mlp_forward_pair into fresh tensors: ((y0, y1), (activations of nets[0], of nets[1]))."""
+    ys, acts = _alloc_outputs(nets, x0.shape[0], x0.device)
+    _abi.call("lt_mlp_forward_pair", nets[0].desc, nets[0].packed, x0, nets[1].desc, nets[1].packed, x1, x0.shape[0], ys[0], ys[1],
+              _abi.ptr_array(acts[0]), _abi.ptr_array(acts[1]), int(acts_split), _abi.stream())
+    return ys, acts
 
 
 class _PairForward(torch.autograd.Function):
@@ -128,27 +147,12 @@ class _PairForward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pair, x0, x1, *params):
-        lib = _abi.load()
-        vp = ctypes.c_void_p
-        m = x0.shape[0]
         nets = (pair.a, pair.b)
-        ys, acts = [], []
-        for net in nets:
-            dims = [net.desc.dims[i] for i in range(net.desc.num_layers + 1)]
-            ys.append(torch.empty(m, dims[-1], device=x0.device, dtype=torch.float32))
-            acts.append([torch.empty(m, d, device=x0.device, dtype=torch.float32) for d in dims[1:-1]])
-        arr = [(vp * max(1, len(a)))(*[t.data_ptr() for t in a]) for a in acts]
-        _abi.check(lib.lt_mlp_forward_pair(ctypes.byref(nets[0].desc), vp(nets[0].packed.data_ptr()), vp(x0.data_ptr()),
-                                           ctypes.byref(nets[1].desc), vp(nets[1].packed.data_ptr()), vp(x1.data_ptr()), m,
-                                           vp(ys[0].data_ptr()), vp(ys[1].data_ptr()), arr[0], arr[1], 0, PackedMLP._stream()), "lt_mlp_forward_pair")
-        if pair.check_domain:  # once per PPO update (PackedPair.arm_domain_check): largest |value| that entered any layer
-            pair.check_domain = False
-            with torch.no_grad():
-                m_ = torch.stack([t.abs().max() for t in (x0, x1, *acts[0], *acts[1])]).max()
-                pair.domain_max = m_ if pair.domain_max is None else torch.maximum(pair.domain_max, m_)
+        ys, acts = _forward_pair(nets, x0, x1, acts_split=False)
+        if pair.check_domain:  # once per PPO update (PackedPair.arm_domain_check)
+            pair._record_domain((x0, x1, *acts[0], *acts[1]))
         ctx.nl = (len(nets[0].linears), len(nets[1].linears))
         ctx.save_for_backward(x0, x1, *acts[0], *acts[1], *[p for p in params[0::2]])
-        ctx.alpha = 1.0
         ctx.elu = nets[0].desc.activation == _abi.CONSTS["LT_ACT_ELU"]
         return ys[0], ys[1]
 
@@ -157,7 +161,6 @@ class _PairForward(torch.autograd.Function):
         from .linear import _head_wgrad, _head_wgrad_ok, _wgrad, pick_splits
 
         lib = _abi.load()
-        vp = ctypes.c_void_p
         saved = list(ctx.saved_tensors)
         x = saved[:2]
         n0, n1 = ctx.nl
@@ -177,9 +180,8 @@ class _PairForward(torch.autograd.Function):
                     a = acts[k][l]
                     dz = torch.empty_like(a)
                     db = torch.empty(n, device=a.device, dtype=torch.float32)
-                    scratch = torch.empty(int(lib.lt_elu_backward_bias_ws_floats(m, n)), device=a.device, dtype=torch.float32)
-                    _abi.check(lib.lt_elu_backward_bias(vp(g.data_ptr()), vp(a.data_ptr()), m, n, 1.0, vp(dz.data_ptr()), vp(db.data_ptr()), vp(scratch.data_ptr()),
-                                                        PackedMLP._stream()), "lt_elu_backward_bias")
+                    scratch = torch.empty(lib.lt_elu_backward_bias_ws_floats(m, n), device=a.device, dtype=torch.float32)
+                    _abi.call("lt_elu_backward_bias", g, a, m, n, 1.0, dz, db, scratch, _abi.stream())
                     dw = _wgrad(dz, inp, pick_splits(m, n, inp.shape[1]))
                 else:  # the head: no activation
                     dz = g
@@ -192,20 +194,6 @@ class _PairForward(torch.autograd.Function):
                     g = dz @ w
             grads += layer_grads
         return (None, None, None, *grads)
-
-
-def _alloc_outputs(nets, m, device):
-    ys, acts = [], []
-    for net in nets:
-        dims = [net.desc.dims[i] for i in range(net.desc.num_layers + 1)]
-        ys.append(torch.empty(m, dims[-1], device=device, dtype=torch.float32))
-        acts.append([torch.empty(m, d, device=device, dtype=torch.float32) for d in dims[1:-1]])
-    return ys, acts
-
-
-import os as _os
-
-USE_FUSED_BACKWARD = _os.environ.get("LT_FUSED_BACKWARD", "1") != "0"  # 0: dz @ W as library GEMMs + lt_elu_backward_bias per layer
 
 
 class SumJobs:
@@ -223,20 +211,12 @@ class SumJobs:
         self.jobs.append((ws, int(nblk), int(stride), int(count), int(split), out0, out1))
 
     def launch(self) -> None:
-        lib = _abi.load()
-        vp = ctypes.c_void_p
         while self.jobs:
             batch, self.jobs = self.jobs[:self.MAX], self.jobs[self.MAX:]
             n = len(batch)
-            arr_p = lambda vals: (vp * n)(*vals)  # noqa: E731
-            ws = arr_p([j[0].data_ptr() for j in batch])
-            out0 = arr_p([j[5].data_ptr() for j in batch])
-            out1 = arr_p([None if j[6] is None else j[6].data_ptr() for j in batch])
-            nblk = (ctypes.c_int * n)(*[j[1] for j in batch])
-            stride = (ctypes.c_int64 * n)(*[j[2] for j in batch])
-            count = (ctypes.c_int * n)(*[j[3] for j in batch])
-            split = (ctypes.c_int * n)(*[j[4] for j in batch])
-            _abi.check(lib.lt_partial_sums(n, ws, nblk, stride, count, split, out0, out1, PackedMLP._stream()), "lt_partial_sums")
+            ws, nblk, stride, count, split, out0, out1 = zip(*batch)
+            _abi.call("lt_partial_sums", n, _abi.ptr_array(ws), (ctypes.c_int * n)(*nblk), (ctypes.c_int64 * n)(*stride),
+                      (ctypes.c_int * n)(*count), (ctypes.c_int * n)(*split), _abi.ptr_array(out0), _abi.ptr_array(out1), _abi.stream())
             self._keep = batch  # the launch reads the buffers asynchronously
         for dst, src in self.after:
             dst.copy_(src)
@@ -252,8 +232,7 @@ def backward_chain(weights, biases_out, weights_out, x, acts, dy, sums: SumJobs)
     from .linear import _head_wgrad_ok, pick_splits
 
     lib = _abi.load()
-    vp = ctypes.c_void_p
-    stream = PackedMLP._stream()
+    stream = _abi.stream()
     L = len(weights)
     g = dy if dy.is_contiguous() else dy.contiguous()
     for l in range(L - 1, -1, -1):
@@ -264,24 +243,23 @@ def backward_chain(weights, biases_out, weights_out, x, acts, dy, sums: SumJobs)
         if l < L - 1:  # g is the gradient w.r.t. the activation output: through ELU', with the bias sums in the same pass
             a = acts[l]
             dz = torch.empty_like(a)
-            nblk = int(lib.lt_elu_backward_bias_nblk(m))
+            nblk = lib.lt_elu_backward_bias_nblk(m)
             scratch = torch.empty(nblk * n + nblk, device=a.device, dtype=torch.float32)
             amax = scratch[nblk * n:]  # per-block max |dz|: lt_wgrad scales the gradient into f16's range by it
-            _abi.check(lib.lt_elu_backward_bias2(vp(g.data_ptr()), vp(a.data_ptr()), m, n, 1.0, vp(dz.data_ptr()), vp(None),
-                                                 vp(scratch.data_ptr()), vp(amax.data_ptr()), stream), "lt_elu_backward_bias2")
+            _abi.call("lt_elu_backward_bias2", g, a, m, n, 1.0, dz, None, scratch, amax, stream)
             sums.add(scratch, nblk, n, n, n, biases_out[l])
         else:
             dz, amax = g, None
         if l == L - 1 and _head_wgrad_ok(dz, inp):
-            nblk = int(lib.lt_head_wgrad_nblk(m))
-            ws = torch.empty(int(lib.lt_head_wgrad_ws_floats(m, n, k)), device=inp.device, dtype=torch.float32)
-            _abi.check(lib.lt_head_wgrad(vp(dz.data_ptr()), vp(inp.data_ptr()), 0, m, n, k, vp(None), vp(None), vp(ws.data_ptr()), stream), "lt_head_wgrad")
+            nblk = lib.lt_head_wgrad_nblk(m)
+            ws = torch.empty(lib.lt_head_wgrad_ws_floats(m, n, k), device=inp.device, dtype=torch.float32)
+            _abi.call("lt_head_wgrad", dz, inp, 0, m, n, k, None, None, ws, stream)
             sums.add(ws, nblk, n * k + 16, n * k + n, n * k, weights_out[l], biases_out[l])
         elif amax is not None and n % 4 == 0 and k % 4 == 0:
             # dW = dz^T x on the f16 matrix cores, f32-equivalent (csrc/lt_wgrad.hip): slices of the rows -> slabs -> the joint sum launch
-            sp = int(lib.lt_wgrad_splits(m, n, k))
+            sp = lib.lt_wgrad_splits(m, n, k)
             slabs = torch.empty(sp * n * k, device=inp.device, dtype=torch.float32)
-            _abi.check(lib.lt_wgrad(vp(dz.data_ptr()), 0, vp(None), vp(inp.data_ptr()), 0, m, n, k, vp(amax.data_ptr()), amax.numel(), vp(slabs.data_ptr()), vp(None), stream), "lt_wgrad")
+            _abi.call("lt_wgrad", dz, 0, None, inp, 0, m, n, k, amax, amax.numel(), slabs, None, stream)
             sums.add(slabs, sp, n * k, n * k, n * k, weights_out[l])
         else:
             sp = pick_splits(m, n, k)
@@ -307,6 +285,10 @@ class PackedPair:
         # kernel; the next forward after arm_domain_check() records the largest |input row / hidden activation| on the device
         self.check_domain = False
         self.domain_max: torch.Tensor | None = None
+        self.acts_split = False           # format of the activations the last forward_raw wrote
+        self._bpacked_fresh = False       # the transposed streams match the live weights (pack_training .. the next optimizer step)
+        self._bwd_shapes_ok: bool | None = None
+        self.sat: torch.Tensor | None = None  # device counter of the fused backward chain's saturated workgroups x layers
         for net in (self.a, self.b):
             dims = [net.desc.dims[i] for i in range(net.desc.num_layers + 1)]
             if any(d % 4 for d in dims[1:-1]) or net.desc.activation != _abi.CONSTS["LT_ACT_ELU"]:
@@ -314,6 +296,13 @@ class PackedPair:
 
     def arm_domain_check(self) -> None:
         self.check_domain = True
+
+    def _record_domain(self, tensors) -> None:
+        """The armed check's record: the largest |value| among `tensors` (what entered the layers of one forward), kept on the device."""
+        self.check_domain = False
+        with torch.no_grad():
+            m_ = torch.stack([t.abs().max().float() for t in tensors]).max()
+            self.domain_max = m_ if self.domain_max is None else torch.maximum(self.domain_max, m_)
 
     def domain_violated(self) -> bool:
         """True if a checked forward saw a layer input at or beyond the kernel's saturation bound (host read: call where the
@@ -329,56 +318,38 @@ class PackedPair:
         `split` (default: whenever the fused backward pass will consume them): the activations are written in the kernel's split
         format - one dword per element, f16 hi | f16 lo << 16, value = hi + lo / 64 (include/lt_env.h, lt_mlp_forward_pair) - which
         the backward chain and the weight-gradient kernel read without converting; the tensors keep dtype float32 as a container."""
-        lib = _abi.load()
-        vp = ctypes.c_void_p
-        nets = (self.a, self.b)
-        m = x0.shape[0]
         if split is None:
             split = self._fused_backward_possible(x0, x1)
         self.acts_split = bool(split)
         self.pack_training(with_backward=self.acts_split)
-        ys, acts = _alloc_outputs(nets, m, x0.device)
-        arr = [(vp * max(1, len(a)))(*[t.data_ptr() for t in a]) for a in acts]
-        _abi.check(lib.lt_mlp_forward_pair(ctypes.byref(nets[0].desc), vp(nets[0].packed.data_ptr()), vp(x0.data_ptr()),
-                                           ctypes.byref(nets[1].desc), vp(nets[1].packed.data_ptr()), vp(x1.data_ptr()), m,
-                                           vp(ys[0].data_ptr()), vp(ys[1].data_ptr()), arr[0], arr[1], int(self.acts_split), PackedMLP._stream()), "lt_mlp_forward_pair")
+        ys, acts = _forward_pair((self.a, self.b), x0, x1, self.acts_split)
         if self.check_domain:
-            self.check_domain = False
             hidden = [t.view(torch.float16)[:, 0::2] if self.acts_split else t for t in (*acts[0], *acts[1])]  # (the hi halves carry the magnitude)
-            m_ = torch.stack([t.abs().max().float() for t in (x0, x1, *hidden)]).max()
-            self.domain_max = m_ if self.domain_max is None else torch.maximum(self.domain_max, m_)
+            self._record_domain((x0, x1, *hidden))
         return ys, acts
 
     def pack_training(self, with_backward: bool) -> None:
         """The forward streams of both networks and (with_backward) their transposed streams for the fused backward pass, in ONE
         launch (`lt_mlp_pack_training`): a training step re-packs everything, the optimizer has moved the weights."""
-        lib = _abi.load()
-        vp = ctypes.c_void_p
         args = []
         for net in (self.a, self.b):
-            if with_backward and getattr(net, "bpacked", None) is None:
-                n = ctypes.c_size_t()
-                _abi.check(lib.lt_mlp_backward_packed_floats(ctypes.byref(net.desc), ctypes.byref(n)), "lt_mlp_backward_packed_floats")
-                net.bpacked = torch.zeros(int(n.value), device=net.packed.device, dtype=torch.float32)
-            L = len(net.linears)
-            arr = ctypes.c_void_p * L
-            args += [ctypes.byref(net.desc), arr(*[l.weight.data_ptr() for l in net.linears]), arr(*[l.bias.data_ptr() for l in net.linears]),
-                     vp(net.packed.data_ptr()), vp(net.bpacked.data_ptr()) if with_backward else vp(None)]
-        _abi.check(lib.lt_mlp_pack_training(*args, PackedMLP._stream()), "lt_mlp_pack_training")
+            if with_backward:
+                net.alloc_bpacked()
+            args += [net.desc, net.weight_ptrs(), net.bias_ptrs(), net.packed, net.bpacked if with_backward else None]
+        _abi.call("lt_mlp_pack_training", *args, _abi.stream())
         self._bpacked_fresh = bool(with_backward)
 
     def split_rows(self, x: torch.Tensor) -> torch.Tensor:
         """Observation rows in the split format (lt_split_rows): converted once per PPO update for the first layer's weight gradient.
         A width that is not a multiple of 4 (the locomotion task's 270) is padded with zero columns to the next one: lt_wgrad's
         16-byte operand pieces need it, and the padded columns of dW are dropped again (`_backward_fused`)."""
-        lib = _abi.load()
         k = x.shape[1]
         if k % 4:
             xp = torch.zeros(x.shape[0], k + (-k) % 4, device=x.device, dtype=torch.float32)
             xp[:, :k] = x
             x = xp
         out = torch.empty_like(x, dtype=torch.float32)
-        _abi.check(lib.lt_split_rows(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), x.numel(), PackedMLP._stream()), "lt_split_rows")
+        _abi.call("lt_split_rows", x, out, x.numel(), _abi.stream())
         return out
 
     def _fused_backward_possible(self, x0, x1) -> bool:
@@ -388,7 +359,7 @@ class PackedPair:
             return False
         if x0.dtype != torch.float32 or x1.dtype != torch.float32 or not x0.is_contiguous() or not x1.is_contiguous():
             return False
-        if getattr(self, "_bwd_shapes_ok", None) is None:  # a property of the two networks: decided once
+        if self._bwd_shapes_ok is None:  # a property of the two networks: decided once
             ok = self.a.backward_ok() and self.b.backward_ok()
             for net in (self.a, self.b):
                 dims = [net.desc.dims[i] for i in range(net.desc.num_layers + 1)]
@@ -405,11 +376,10 @@ class PackedPair:
         (lt_mlp_backward_pair: dz of every hidden layer, ELU' applied in the layer epilogue, per-workgroup max |dz|), six weight
         gradients on the matrix cores that also leave the bias gradients' partials (lt_wgrad), one launch of ordered sums."""
         lib = _abi.load()
-        vp = ctypes.c_void_p
-        stream = PackedMLP._stream()
+        stream = _abi.stream()
         m = x0.shape[0]
         nets, xs = (self.a, self.b), (x0, x1)
-        asp = int(getattr(self, "acts_split", False))   # format of `acts` (forward_raw)
+        asp = int(self.acts_split)                      # format of `acts` (forward_raw)
         xsp = int(x_split_rows is not None)             # the observation rows in the split format, from the caller (once per update)
         if not xsp and any(x.shape[1] % 4 for x in xs):  # widths 2 mod 4 reach lt_wgrad padded and split only
             x_split_rows, xsp = (self.split_rows(x0), self.split_rows(x1)), 1
@@ -417,45 +387,42 @@ class PackedPair:
             xs = x_split_rows
         dys = [d if d.is_contiguous() else d.contiguous() for d in (dy0, dy1)]
         dev = x0.device
-        if getattr(self, "sat", None) is None:
-            self.sat = torch.zeros(1, device=dev, dtype=torch.float32)  # workgroups x layers of the chain that saturated (domain check)
-        nblk = int(lib.lt_mlp_backward_blocks(ctypes.byref(nets[0].desc), ctypes.byref(nets[1].desc), m))
+        if self.sat is None:
+            self.sat = torch.zeros(1, device=dev, dtype=torch.float32)
+        nblk = lib.lt_mlp_backward_blocks(ctypes.byref(nets[0].desc), ctypes.byref(nets[1].desc), m)
         dzs, amaxs, arrs = [], [], []
         # one list of ordered sums per network when the caller wants the first network's gradients early (`after_first`: the trainer
         # starts the all-reduce of the actor's half of the bucket under the critic's weight gradients), else one list for both
         per_net = (SumJobs(), SumJobs()) if after_first is not None else (sums, sums)
         for k, net in enumerate(nets):
-            if not getattr(self, "_bpacked_fresh", False):  # (forward_raw packs the transposed streams with the forward ones)
+            if not self._bpacked_fresh:  # (forward_raw packs the transposed streams with the forward ones)
                 net.pack_backward()
             L = len(net.linears)
             n, kk = dys[k].shape[1], acts[k][L - 2].shape[1]
-            ws = torch.empty(int(lib.lt_head_wgrad_ws_floats(m, n, kk)), device=dev, dtype=torch.float32)
-            _abi.check(lib.lt_head_wgrad(vp(dys[k].data_ptr()), vp(acts[k][L - 2].data_ptr()), asp, m, n, kk, vp(None), vp(None), vp(ws.data_ptr()), stream), "lt_head_wgrad")
-            per_net[k].add(ws, int(lib.lt_head_wgrad_nblk(m)), n * kk + 16, n * kk + n, n * kk, grad_of[net.linears[L - 1].weight], grad_of[net.linears[L - 1].bias])
+            ws = torch.empty(lib.lt_head_wgrad_ws_floats(m, n, kk), device=dev, dtype=torch.float32)
+            _abi.call("lt_head_wgrad", dys[k], acts[k][L - 2], asp, m, n, kk, None, None, ws, stream)
+            per_net[k].add(ws, lib.lt_head_wgrad_nblk(m), n * kk + 16, n * kk + n, n * kk, grad_of[net.linears[L - 1].weight], grad_of[net.linears[L - 1].bias])
             dz = [torch.empty_like(a) for a in acts[k]]
             am = torch.empty(L - 1, nblk, device=dev, dtype=torch.float32)
             dzs.append(dz)
             amaxs.append(am)
-            arr = ctypes.c_void_p * (L - 1)
-            arrs.append((arr(*[a.data_ptr() for a in acts[k]]), arr(*[t.data_ptr() for t in dz]), arr(*[am[l].data_ptr() for l in range(L - 1)])))
+            arrs.append((_abi.ptr_array(acts[k]), _abi.ptr_array(dz), _abi.ptr_array([am[l] for l in range(L - 1)])))
         # `dy_amax`: (max |dy0|, max |dy1|) as device scalars (lt_ppo_loss leaves them): the chain then runs on ONE scale per network
         # and writes every dz in the split format, scaled - what lt_wgrad reads without converting
         dzsp = int(dy_amax is not None)
         scales = torch.empty(2, device=dev, dtype=torch.float32)
-        _abi.check(lib.lt_mlp_backward_pair(ctypes.byref(nets[0].desc), vp(nets[0].bpacked.data_ptr()), vp(dys[0].data_ptr()), *arrs[0],
-                                            ctypes.byref(nets[1].desc), vp(nets[1].bpacked.data_ptr()), vp(dys[1].data_ptr()), *arrs[1],
-                                            m, asp, vp(dy_amax[0].data_ptr()) if dzsp else vp(None), vp(dy_amax[1].data_ptr()) if dzsp else vp(None),
-                                            dzsp, vp(scales.data_ptr()), vp(self.sat.data_ptr()), stream), "lt_mlp_backward_pair")
+        in_amax = dy_amax if dzsp else (None, None)
+        _abi.call("lt_mlp_backward_pair", nets[0].desc, nets[0].bpacked, dys[0], *arrs[0], nets[1].desc, nets[1].bpacked, dys[1], *arrs[1],
+                  m, asp, in_amax[0], in_amax[1], dzsp, scales, self.sat, stream)
         for k, net in enumerate(nets):
             for l in range(len(net.linears) - 2, -1, -1):
                 inp = acts[k][l - 1] if l > 0 else xs[k]
                 dz = dzs[k][l]
                 n, kk = dz.shape[1], inp.shape[1]
-                sp = int(lib.lt_wgrad_splits(m, n, kk))
+                sp = lib.lt_wgrad_splits(m, n, kk)
                 slabs = torch.empty(sp * n * kk + sp * n, device=dev, dtype=torch.float32)
                 dbs = slabs[sp * n * kk:]
-                _abi.check(lib.lt_wgrad(vp(dz.data_ptr()), dzsp, vp(scales[k:k + 1].data_ptr()), vp(inp.data_ptr()), asp if l > 0 else xsp, m, n, kk,
-                                        vp(amaxs[k][l].data_ptr()), nblk, vp(slabs.data_ptr()), vp(dbs.data_ptr()), stream), "lt_wgrad")
+                _abi.call("lt_wgrad", dz, dzsp, scales[k:k + 1], inp, asp if l > 0 else xsp, m, n, kk, amaxs[k][l], nblk, slabs, dbs, stream)
                 gw = grad_of[net.linears[l].weight]
                 if kk != gw.shape[1]:  # padded first layer: the sum lands in a [n][kk] scratch, its first columns are the gradient
                     pad = torch.empty(n, kk, device=dev, dtype=torch.float32)
@@ -473,7 +440,7 @@ class PackedPair:
 
     def saturated(self) -> torch.Tensor | None:
         """Device counter of saturated workgroups of the fused backward chain (None: that path has not run)."""
-        return getattr(self, "sat", None)
+        return self.sat
 
     def backward_raw(self, x0, x1, acts, dy0, dy1, grad_of, x_split_rows=None, after_first=None, dy_amax=None) -> None:
         """Both stacks' backward passes, every parameter gradient written into `grad_of[param]` (the flat bucket's views).
@@ -486,7 +453,7 @@ class PackedPair:
             self._backward_fused(x0, x1, acts, dy0, dy1, grad_of, sums, x_split_rows, after_first, dy_amax)
             sums.launch()
             return
-        if getattr(self, "acts_split", False):
+        if self.acts_split:
             raise RuntimeError("PackedPair.backward_raw: the activations are in the split format, which only the fused backward pass reads "
                                "(forward_raw(..., split=False) for the library path)")
         for net, x, a, dy in ((self.a, x0, acts[0], dy0), (self.b, x1, acts[1], dy1)):

@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from .. import _abi
 from .dist import Dist
 from .modules import ActorCritic
 from .storage import RolloutStorage
@@ -137,6 +138,13 @@ class PPO:
                     self._pair = False
         return self._pair or None
 
+    def _flat_storage(self):
+        """(obs, critic obs, [actions, log-probs, advantages, returns, values, mu, sigma]) of the rollout storage as rows."""
+        st = self.storage
+        f = lambda t: t.flatten(0, 1)  # noqa: E731
+        small = [f(t).contiguous() for t in (st.actions, st.actions_log_prob, st.advantages, st.returns, st.values, st.mu, st.sigma)]
+        return f(st.observations), f(st.privileged_observations), small
+
     def _fused_update(self):
         """The update of the plain ActorCritic on the GPU: per minibatch step two row gathers (obs, critic obs), the two MLPs,
         ONE loss launch that reads the seven small per-row tensors of the rollout storage through the minibatch index
@@ -145,9 +153,7 @@ class PPO:
         from .fused_loss import fused_ppo_loss
 
         ac, st = self.actor_critic, self.storage
-        f = lambda t: t.flatten(0, 1)  # noqa: E731
-        obs, cobs = f(st.observations), f(st.privileged_observations)
-        small = [f(t).contiguous() for t in (st.actions, st.actions_log_prob, st.advantages, st.returns, st.values, st.mu, st.sigma)]
+        obs, cobs, small = self._flat_storage()
         stats = torch.zeros(3, device=obs.device)
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         pair = self._packed_pair()
@@ -189,16 +195,8 @@ class PPO:
         all-reduce], clip + Adam with the learning rate read from the device (`lt_adam_clip_step_dev`).  Statistics and the learning
         rate come back in ONE read at the end.  Arithmetic equal to `_fused_update` (tests/test_hip_ppo_graph.py); the host used to
         wait for the KL of every step - 20 stalls per iteration, ~350 us of idle GPU each."""
-        import ctypes
-
-        from .. import _abi
-
-        lib = _abi.load()
-        vp = ctypes.c_void_p
         ac, st, fa = self.actor_critic, self.storage, self._flat_adam
-        f = lambda t: t.flatten(0, 1)  # noqa: E731
-        obs, cobs = f(st.observations), f(st.privileged_observations)
-        small = [f(t).contiguous() for t in (st.actions, st.actions_log_prob, st.advantages, st.returns, st.values, st.mu, st.sigma)]
+        obs, cobs, small = self._flat_storage()
         small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
         dev = obs.device
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
@@ -232,19 +230,15 @@ class PPO:
             dvalue = torch.empty(m, 1, device=dev, dtype=torch.float32)
             acc = torch.empty(24, device=dev, dtype=torch.float32)
             out = torch.empty(24, device=dev, dtype=torch.float32)
-            stream = vp(torch.cuda.current_stream(dev).cuda_stream)
-            _abi.check(lib.lt_ppo_loss(vp(mu.data_ptr()), vp(std_c.data_ptr()), vp(value.data_ptr()), *[vp(t.data_ptr()) for t in small],
-                                       vp(idx.data_ptr()), m, a_dim, float(self.clip_param), float(self.value_loss_coef), float(self.entropy_coef),
-                                       int(bool(self.use_clipped_value_loss)), vp(dmu.data_ptr()), vp(dvalue.data_ptr()), vp(acc.data_ptr()),
-                                       vp(out.data_ptr()), stream), "lt_ppo_loss")
+            stream = _abi.stream(dev)
+            _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                      float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
             kl = None
             if adaptive:
                 kl = out[4:5]
                 if self.dist.world_size > 1:  # every rank must take the same decision; the collective is stream-ordered
                     kl = self.dist.all_reduce_mean_(kl.clone())
-            _abi.check(lib.lt_ppo_lr_rule(vp(kl.data_ptr()) if kl is not None else vp(None), float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5,
-                                          vp(lr_dev.data_ptr()), vp(stats.data_ptr()), vp(out.data_ptr()), vp(grad_of[ac.std].data_ptr()), a_dim, stream),
-                       "lt_ppo_lr_rule")
+            _abi.call("lt_ppo_lr_rule", kl, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out, grad_of[ac.std], a_dim, stream)
             if self.dist.world_size > 1 and two_buckets:
                 # the bucket in two halves (std + actor | critic): the actor's all-reduce runs on RCCL's stream under the critic's
                 # three weight-gradient launches (~105 us at 24 576 rows), only the critic's half stays exposed

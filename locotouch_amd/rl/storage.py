@@ -82,17 +82,13 @@ class RolloutStorage:
                         dist: Dist | None = None) -> None:
         """GAE: delta_t = r_t + gamma (1-d_t) V_{t+1} - V_t ;  A_t = delta_t + gamma lam (1-d_t) A_{t+1} ; R_t = A_t + V_t."""
         if self.rewards.is_cuda:  # one launch instead of ~7 tensor ops per step (csrc/lt_ppo.hip lt_gae)
-            import ctypes
-
             from .. import _abi
 
-            vp = ctypes.c_void_p
             lv = last_values.detach().reshape(-1).contiguous().float()
             if self.advantages.shape != self.returns.shape or not self.advantages.is_contiguous():
                 self.advantages = torch.empty_like(self.returns)
-            _abi.check(_abi.load().lt_gae(vp(self.rewards.data_ptr()), vp(self.dones.data_ptr()), vp(self.values.data_ptr()), vp(lv.data_ptr()),
-                                          float(gamma), float(lam), self.num_steps, self.num_envs, vp(self.returns.data_ptr()),
-                                          vp(self.advantages.data_ptr()), vp(torch.cuda.current_stream(self.rewards.device).cuda_stream)), "lt_gae")
+            _abi.call("lt_gae", self.rewards, self.dones, self.values, lv, float(gamma), float(lam), self.num_steps, self.num_envs,
+                      self.returns, self.advantages, _abi.stream(self.rewards.device))
         else:
             gae = 0
             next_values = last_values

@@ -23,26 +23,11 @@ ORACLE_SOS = {"f32": ORACLE_SO, "f64": os.path.join(REPO, "oracle", "_build", "l
 PRECISIONS = tuple(ORACLE_SOS)
 
 f32 = ctypes.c_float
-i32 = ctypes.c_int32
 
-
-class TermIn(ctypes.Structure):
-    _fields_ = [("root_pos", f32 * 3), ("root_quat", f32 * 4), ("root_lin", f32 * 3), ("root_ang", f32 * 3),
-                ("q", f32 * 3 * 4), ("qd", f32 * 3 * 4), ("qdd", f32 * 3 * 4), ("tau", f32 * 3 * 4),
-                ("act_raw", f32 * 3 * 4), ("act_prev", f32 * 3 * 4),
-                ("fhist", f32 * 4 * 4 * 3), ("trunk_fhist", f32 * 3),
-                ("foot_pos", f32 * 3 * 4), ("foot_vel", f32 * 3 * 4),
-                ("obj_pos", f32 * 3), ("obj_quat", f32 * 4), ("obj_lin", f32 * 3), ("obj_ang", f32 * 3),
-                ("obj_timers", f32 * 4), ("cmd", f32 * 3), ("terminated", i32)]
-
-
-class GaitIO(ctypes.Structure):
-    _fields_ = [("cur_air", f32 * 4), ("cur_con", f32 * 4), ("sensor_last_air", f32 * 4), ("cmd", f32 * 3),
-                ("lin_err", f32), ("ang_err", f32), ("obj_xy_yaw", f32 * 2), ("any_nonzero_cmd", i32),
-                ("last_step_air", f32 * 4), ("last_step_con", f32 * 4), ("valid_last_air", f32 * 4),
-                ("swinging_in_zero_cmd", i32 * 4), ("valid_prev_contact", i32 * 4), ("last_cmd", f32 * 3),
-                ("step_from_change", f32)]
-
+# oracle/lt_oracle.h through the product's header parser, with typed data pointers (the callers pass POINTER(c_float) etc.)
+_, _STRUCTS, _SIGNATURES = _abi.parse_header(open(os.path.join(REPO, "oracle", "lt_oracle.h")).read(), typed=True,
+                                             structs={"lt_cfg": _abi.LtCfg})
+TermIn, GaitIO = _STRUCTS["lt_term_in"], _STRUCTS["lt_gait_io"]
 
 _libs: dict = {}
 
@@ -55,35 +40,9 @@ def load(precision: str = "f32") -> ctypes.CDLL:
     if not all(os.path.exists(p) and os.path.getmtime(p) >= os.path.getmtime(src) for p in ORACLE_SOS.values()):
         subprocess.run(["make", "-C", os.path.join(REPO, "oracle")], check=True, stdout=subprocess.DEVNULL)
     lib = ctypes.CDLL(so)
-    P = ctypes.POINTER
-    lib.lt_oracle_real_bytes.argtypes = []
-    lib.lt_oracle_obs_dim.argtypes = [P(_abi.LtCfg)]
-    lib.lt_oracle_state_bytes.argtypes = [P(_abi.LtCfg)]
-    lib.lt_oracle_state_bytes.restype = ctypes.c_int64
-    lib.lt_oracle_reset_all.argtypes = [P(_abi.LtCfg), ctypes.c_void_p]
-    lib.lt_oracle_step.argtypes = [P(_abi.LtCfg), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    lib.lt_oracle_eval_terms.argtypes = [P(_abi.LtCfg), ctypes.c_void_p]
-    lib.lt_oracle_process_action.argtypes = [P(_abi.LtCfg), P(f32), P(f32), P(f32), P(f32)]
-    lib.lt_oracle_gait.argtypes = [P(_abi.LtCfg), P(GaitIO), f32]
-    lib.lt_oracle_gait.restype = f32
-    lib.lt_oracle_rewards.argtypes = [P(_abi.LtCfg), P(TermIn), P(GaitIO), f32, P(f32)]
-    lib.lt_oracle_terminations.argtypes = [P(_abi.LtCfg), P(TermIn), ctypes.c_int64, ctypes.c_int64]
-    lib.lt_oracle_object_state_obs.argtypes = [P(_abi.LtCfg), P(TermIn), P(f32), P(f32)]
-    lib.lt_oracle_command_update.argtypes = [ctypes.c_int64, ctypes.c_int, P(f32), ctypes.c_int, P(f32)]
-    lib.lt_oracle_cmd_params_init.argtypes = [P(_abi.LtCfg), P(f32)]
-    lib.lt_oracle_curriculum.argtypes = [P(_abi.LtCfg), P(f32), ctypes.c_int64, P(f32), P(f32)]
-    lib.lt_oracle_command_resample_u.argtypes = [P(_abi.LtCfg), P(f32), P(f32), P(f32), f32, f32, P(f32), P(f32), P(f32), P(f32)]
-    lib.lt_oracle_material_u.argtypes = [P(f32), P(f32), P(f32), P(f32), P(f32)]
-    lib.lt_oracle_policy_normals.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint64, P(ctypes.c_double)]
-    lib.lt_oracle_taxel_forces.argtypes = [P(f32), P(f32), P(f32), P(f32)]
-    lib.lt_oracle_tactile_signals_u.argtypes = [P(_abi.LtCfg)] + [P(f32)] * 5
-    lib.lt_oracle_tactile_channels_u.argtypes = [P(_abi.LtCfg), ctypes.c_int] + [P(f32)] * 13
-    lib.lt_oracle_tactile_format_u.argtypes = [P(_abi.LtCfg), ctypes.c_int, P(f32), P(P(f32)), P(f32)]
-    lib.lt_oracle_reset_object_u.argtypes = [P(_abi.LtCfg)] + [P(f32)] * 4 + [f32] + [P(f32)] * 5
-    lib.lt_oracle_curriculum_update.argtypes = [P(_abi.LtCfg), ctypes.c_void_p, P(f32)]
-    lib.lt_oracle_gate_on_sums.argtypes = [P(_abi.LtCfg), P(f32), P(f32), f32, ctypes.c_int, ctypes.c_int, P(i32)]
-    lib.lt_oracle_curriculum_apply_global.argtypes = [P(_abi.LtCfg), ctypes.c_void_p, P(f32), ctypes.c_int, ctypes.c_int64]
-    lib.lt_oracle_obs_push.argtypes = [P(i32), ctypes.c_int, ctypes.c_int, P(f32), ctypes.c_int, P(f32)]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _libs[precision] = lib
     return lib
 
@@ -134,7 +93,7 @@ class OracleEnv:
 
     def step(self, actions: np.ndarray, nthreads: int = 1):
         a = np.ascontiguousarray(actions, dtype=np.float32)
-        self.lib.lt_oracle_step(ctypes.byref(self.cfg), self.ptr, a.ctypes.data_as(ctypes.c_void_p), nthreads)
+        self.lib.lt_oracle_step(ctypes.byref(self.cfg), self.ptr, fptr(a), nthreads)
 
     def curriculum_update(self, records: np.ndarray):
         r = np.ascontiguousarray(records, dtype=np.float32)

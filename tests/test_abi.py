@@ -179,3 +179,129 @@ def test_train_script_dumps_env_and_agent_params(tmp_path):
     assert env["num_envs"] == 128 and env["gym_id"] == task and len(env["reward_weight"]) >= 25
     assert pickle.load(open(tmp_path / "params" / "env.pkl", "rb")) == env
     assert pickle.load(open(tmp_path / "params" / "agent.pkl", "rb")) == yaml.safe_load(open(tmp_path / "params" / "agent.yaml"))
+
+
+# ---- the binding is derived from the header: pinned against literals, not against the parser itself ----
+_vp, _int, _i64, _f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+_P = ctypes.POINTER
+
+
+def test_every_prototype_has_a_derived_signature():
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(_abi.HEADER).read(), flags=re.S))
+    protos = set(re.findall(r"\b(lt_\w+)\s*\([^()]*\)\s*;", src))
+    assert len(protos) == 67 and protos == set(_abi.EXPORTS) == set(_abi.SIGNATURES)
+    assert len(_abi.EXPORTS) == len(set(_abi.EXPORTS))
+    lib = _abi.load()
+    for name, (restype, argtypes) in _abi.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == argtypes and fn.restype is restype, name
+    assert _abi.VALUE_QUERIES <= protos
+    assert all(_abi.SIGNATURES[n][0] is _int for n in protos - _abi.VALUE_QUERIES)
+
+
+def test_derived_signatures_match_literals():
+    """One literal signature per branch of the type rule (scalars, data pointers, const char*, structure pointers, size_t*,
+    pointer to pointer, an array parameter, the opaque handle, every restype)."""
+    S = _abi.SIGNATURES
+    assert S["lt_wgrad"] == (_int, [_vp, _int, _vp, _vp, _int, _i64, _int, _int, _vp, _int, _vp, _vp, _vp])
+    assert S["lt_ppo_loss"] == (_int, [_vp] * 11 + [_i64, _int, _f32, _f32, _f32, _int] + [_vp] * 5)
+    assert S["lt_partial_sums"] == (_int, [_int, _P(_vp), _vp, _vp, _vp, _vp, _P(_vp), _P(_vp), _vp])
+    assert S["lt_env_create"] == (_int, [_P(_abi.LtCfg), _P(_vp)])
+    assert S["lt_env_state_bytes"] == (_int, [_P(_abi.LtCfg), _P(ctypes.c_size_t)])
+    assert S["lt_mlp_backward_blocks"] == (_i64, [_P(_abi.LtMlpDesc), _P(_abi.LtMlpDesc), _i64])
+    assert S["lt_cfg_preset_id"] == (ctypes.c_char_p, [_int])
+    assert S["lt_cfg_preset"] == (_int, [ctypes.c_char_p, _P(_abi.LtCfg)])
+    assert S["lt_env_set_command_ranges"] == (_int, [_vp, _vp, _int, _f32, _vp])
+    assert S["lt_rollout_act"] == (_int, [_i64, _int, ctypes.c_uint64] + [_vp] * 15)
+    assert S["lt_env_render"] == (_int, [_vp, _P(_abi.LtRenderDesc), _P(_abi.LtRenderView), _int, _vp, _vp, _vp, _vp, _vp])
+    assert S["lt_env_get_view"] == (_int, [_vp, _int, _P(_abi.LtView)])
+    assert S["lt_cfg_sizeof"] == (ctypes.c_size_t, []) and S["lt_last_error"] == (ctypes.c_char_p, [])
+    assert S["lt_env_bind"] == (_int, [_vp, _vp, ctypes.c_size_t])
+
+
+def test_derived_structures_match_literals():
+    i32 = ctypes.c_int32
+    want = {
+        "LtView": [("ptr", _vp), ("dtype", i32), ("ndim", i32), ("shape", _i64 * 3), ("stride", _i64 * 3)],
+        "LtMlpDesc": [("num_layers", i32), ("dims", i32 * 7), ("activation", i32), ("input_format", i32)],
+        "LtRenderView": [("env_id", i32), ("origin", i32), ("eye", _f32 * 3), ("lookat", _f32 * 3), ("fov_y_deg", _f32)],
+        "LtRenderDesc": [("width", i32), ("height", i32), ("flags", i32), ("light_dir", _f32 * 3)],
+    }
+    for name, fields in want.items():
+        cls = getattr(_abi, name)
+        assert cls.__name__ == name and issubclass(cls, ctypes.Structure)
+        assert list(cls._fields_) == fields, name
+    assert ctypes.sizeof(_abi.LtView) == 64 and ctypes.sizeof(_abi.LtMlpDesc) == 40
+    assert ctypes.sizeof(_abi.LtRenderView) == 36 and ctypes.sizeof(_abi.LtRenderDesc) == 24
+    assert ctypes.sizeof(_abi.LtCfg) == _abi.load().lt_cfg_sizeof()
+    cfg = _abi.default_cfg(1)
+    assert isinstance(cfg.copy(), _abi.LtCfg) and cfg.copy().to_dict() == cfg.to_dict()
+    assert [n for n, _ in _abi.LtCfg._fields_][:3] == ["seed", "num_envs", "task"] and dict(_abi.LtCfg._fields_)["cmd_range_init"] is _f32 * 2 * 3
+
+
+@pytest.mark.parametrize("fragment,named", [
+    ("int lt_bad(struct foo* x);", "lt_bad"),                    # a type the rule does not know
+    ("int lt_bad(float m[3][3]);", "lt_bad"),                    # an array of arrays as a parameter
+    ("long double lt_bad(void);", "lt_bad"),                     # an unknown return type
+    ("int lt_bad(float*** p);", "lt_bad"),                       # deeper than pointer to pointer
+    ("typedef struct lt_s { short v; } lt_s;", "lt_s"),          # an untypeable member
+    ("typedef struct lt_s { float v[LT_NOPE]; } lt_s;", "lt_s"),  # an unknown array bound
+    ("int lt_ok(int a); static inline int lt_f(int a) { return a; }", "lt_f"),  # not a plain prototype
+], ids=["unknown-type", "array-of-arrays", "unknown-return", "triple-pointer", "member-type", "array-bound", "not-a-prototype"])
+def test_parser_refuses_what_it_cannot_type(fragment, named):
+    with pytest.raises(ImportError, match=named):
+        _abi.parse_header(fragment)
+
+
+def test_parser_on_a_fragment():
+    consts, structs, protos = _abi.parse_header("""
+        #define LT_N 3
+        enum lt_e { LT_A = 4, LT_B };
+        typedef struct lt_h lt_h;
+        typedef struct lt_s { float a[LT_N + 1], b; void* p; } lt_s;
+        void lt_f(lt_h* h, lt_h** out, const lt_s* s, const double* d, const float* const* pp, const float v[2], void* q);
+        float lt_g(void);
+    """)
+    assert consts == {"LT_N": 3, "LT_A": 4, "LT_B": 5}
+    s = structs["lt_s"]
+    assert s.__name__ == "LtS" and list(s._fields_) == [("a", _f32 * 4), ("b", _f32), ("p", _vp)]
+    assert protos == {"lt_f": (None, [_vp, _P(_vp), _P(s), _vp, _P(_vp), _vp, _vp]), "lt_g": (_f32, [])}
+    typed = _abi.parse_header("void lt_f(const double* d, const float* u8[8], float v[2], void* q, const int* n);", typed=True)[2]
+    assert typed["lt_f"] == (None, [_P(ctypes.c_double), _P(_P(_f32)), _P(_f32), _vp, _P(_int)])
+
+
+def test_call_helper():
+    import torch
+
+    t = torch.arange(8, dtype=torch.float32)
+    assert _abi.ptr(t).value == t.data_ptr() and _abi.ptr(t[2:]).value == t.data_ptr() + 8
+    assert _abi.ptr(None).value is None and _abi.ptr(0).value is None and _abi.ptr(4096).value == 4096
+    held = ctypes.c_void_p(32)
+    assert _abi.ptr(held) is held
+    arr = _abi.ptr_array([t, None, t[4:]])
+    assert isinstance(arr, ctypes.c_void_p * 3) and list(arr) == [t.data_ptr(), None, t.data_ptr() + 16]
+    assert len(_abi.ptr_array([])) == 1  # never a zero-length array
+    # a bad argument is LT_EINVAL decided on the host (no launch): RuntimeError carrying lt_last_error()
+    with pytest.raises(RuntimeError, match=r"lt_elu_backward_bias failed with code -22: lt_elu_backward_bias.*multiple of 4"):
+        _abi.call("lt_elu_backward_bias", t, t, 64, 130, 1.0, t, t, t, None)
+    with pytest.raises(RuntimeError, match="lt_head_wgrad"):
+        _abi.call("lt_head_wgrad", 16, 16, 0, 64, 17, 128, 16, 16, 16, 0)
+    # None / 0 reach the library as NULL, a tensor as its address: lt_ppo_loss names the first NULL operand it finds
+    with pytest.raises(RuntimeError, match="lt_ppo_loss"):
+        _abi.call("lt_ppo_loss", None, *[t] * 9, None, 128, 12, 0.2, 1.0, 0.01, 1, t, t, t, t, None)
+    # structures go by reference, statuses of 0 return None
+    cfg, nbytes, h = _abi.default_cfg(1, num_envs=64), ctypes.c_size_t(), ctypes.c_void_p()
+    assert _abi.call("lt_env_state_bytes", cfg, ctypes.byref(nbytes)) is None and nbytes.value > 0
+    assert _abi.call("lt_env_create", cfg, ctypes.byref(h)) is None and h.value
+    v = _abi.LtView()
+    _abi.call("lt_env_get_view", h, C["LT_F_REWARD"], v)
+    assert list(v.shape)[:1] == [64] and v.ndim == 1
+    with pytest.raises(RuntimeError, match="not bound"):
+        _abi.call("lt_env_reset_all", h, None)
+    _abi.call("lt_env_destroy", h)
+    # value-returning queries are not statuses
+    for name in ("lt_wgrad_splits", "lt_abi_version", "lt_mlp_kernel_name"):
+        with pytest.raises(TypeError, match=name):
+            _abi.call(name, 1, 2, 3)
+    with pytest.raises(ValueError):  # a wrong argument count is an error, not a shifted call
+        _abi.call("lt_env_destroy", h, None)
