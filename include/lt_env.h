@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define LT_ABI_VERSION 20
+#define LT_ABI_VERSION 21
 
 /* error codes */
 #define LT_OK 0
@@ -681,6 +681,10 @@ const char* lt_env_kernel_name(int which);
  * descriptors of both networks).  Host-only: no device is touched. */
 enum lt_mlp_mode { LT_MLP_MODE_FORWARD = 0, LT_MLP_MODE_POLICY = 1, LT_MLP_MODE_BACKWARD = 2 };
 const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_null, int64_t m, int mode);
+
+/* ---- running observation normaliser of the trainer (reference loco_rl/loco_rl/modules/normalizer.py:14-76): lt_obs_norm_ws_floats,
+ * lt_obs_norm_update, lt_obs_norm_apply - declared in a header of their own, part of this ABI. */
+#include "lt_obs_norm.h"
 
 #ifdef __cplusplus
 }

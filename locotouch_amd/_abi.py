@@ -15,6 +15,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(_HERE)
 HEADER = os.path.join(REPO, "include", "lt_env.h")
+OBS_NORM_HEADER = os.path.join(REPO, "include", "lt_obs_norm.h")  # included by lt_env.h: the observation normaliser's entry points
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -121,6 +122,9 @@ globals().update(CONSTS)
 LtCfg, LtView, LtMlpDesc = STRUCTS["lt_cfg"], STRUCTS["lt_view"], STRUCTS["lt_mlp_desc"]
 LtRenderView, LtRenderDesc = STRUCTS["lt_render_view"], STRUCTS["lt_render_desc"]
 EXPORTS = list(SIGNATURES)
+OBS_NORM_SIGNATURES = parse_header(open(OBS_NORM_HEADER).read())[2]  # all status-returning: launched through `call`
+if any(r is not ctypes.c_int for r, _ in OBS_NORM_SIGNATURES.values()) or set(OBS_NORM_SIGNATURES) & set(EXPORTS):
+    raise ImportError("include/lt_obs_norm.h: every entry point returns a status and none repeats one of lt_env.h")
 
 # Entry points that return a VALUE, not an LT_* status (the header's types cannot tell the two apart): never through `call`.
 VALUE_QUERIES = frozenset({
@@ -143,7 +147,7 @@ def load() -> ctypes.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
         if name not in VALUE_QUERIES:

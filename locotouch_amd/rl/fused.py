@@ -13,6 +13,13 @@ population pass on a side branch beside the next policy launch, lt_env_defer_gat
 
 Torch path (shapes outside lt_mlp's limits): torch GEMMs -> lt_rollout_act -> lt_env_step_rows -> lt_rollout_record, with the
 critic on a side stream.
+
+Observation normalisation (the runner's `empirical_normalization`, rl/normalizer.py): with normalisers a step is
+    [policy + value on the NORMALISED rows of slot t] -> [env step: raw rows into slot t + 1] -> [lt_obs_norm_update: merge the new raw
+    rows of both networks into the running statistics, snapshot (mean, 1 / (std + eps)) for slot t + 1, normalised rows into two
+    scratch buffers - two launches, one in evaluation mode]
+still on the one stream.  The storage slots stay RAW during the rollout (the step kernel shifts its observation history from slot t
+to slot t + 1), `normalize_storage()` rewrites them in place through the per-slot snapshots before the update reads them.
 """
 from __future__ import annotations
 
@@ -22,13 +29,36 @@ import torch
 from .. import _abi
 
 
+def normalize_rows(normalizer, rows: torch.Tensor, out: torch.Tensor | None = None, snapshot: torch.Tensor | None = None) -> torch.Tensor:
+    """`normalizer(rows)` of ONE EmpiricalNormalization on the device path (csrc/lt_obs_norm.hip): in training mode the rows are
+    merged into the module's buffers in place (no host read), then normalised.  `snapshot` ([2, D]) receives (mean, 1 / (std + eps)).
+    FusedRollout serves both networks of a rollout with the same launches; this is the single-module form for tools and tests."""
+    import ctypes
+
+    n, d = rows.shape
+    if rows.dtype != torch.float32 or not rows.is_contiguous():
+        raise ValueError("normalize_rows takes contiguous f32 rows")
+    out = torch.empty_like(rows) if out is None else out
+    snapshot = torch.empty(2, d, device=rows.device) if snapshot is None else snapshot
+    floats = ctypes.c_size_t()
+    _abi.call("lt_obs_norm_ws_floats", n, d, ctypes.byref(floats))
+    # the workspace carries the f64 state of the recurrence (include/lt_obs_norm.h): one per module, kept with it between calls
+    ws = getattr(normalizer, "_lt_obs_norm_ws", None)
+    if ws is None or ws.numel() != floats.value or ws.device != rows.device:
+        ws = normalizer._lt_obs_norm_ws = torch.zeros(floats.value, device=rows.device)
+    _abi.call("lt_obs_norm_update", n, int(normalizer.training), -1 if normalizer.until is None else int(normalizer.until),
+              float(normalizer.eps), rows, d, normalizer._mean, normalizer._var, normalizer._std, normalizer.count, snapshot, out, ws,
+              None, 0, None, None, None, None, None, None, None, _abi.stream(rows.device))
+    return out
+
+
 class FusedRollout:
     """Drives a LocoTouchVecEnv and a PPO instance through rollout steps without leaving the device (module docstring).
 
     The env writes observation rows straight into the storage slots (slot t+1 from slot t; the last step writes the arena
     rows), so nothing copies observations."""
 
-    def __init__(self, env, alg, use_packed_mlp: bool = True):
+    def __init__(self, env, alg, use_packed_mlp: bool = True, obs_normalizer=None, critic_obs_normalizer=None):
         from ..env import LocoTouchVecEnv
 
         if not isinstance(env, LocoTouchVecEnv):
@@ -67,6 +97,86 @@ class FusedRollout:
             self.critic_mlp.set_input_format(torch.bfloat16)
             st = alg.storage
             self._tail_rows = (torch.zeros_like(st.observations[0]), torch.zeros_like(st.privileged_observations[0]))
+        # running observation normalisers (rl/normalizer.py): their buffers ARE the device state the kernels update in place
+        self.normalizers = None
+        if (obs_normalizer is None) != (critic_obs_normalizer is None):
+            raise ValueError("FusedRollout takes both obs_normalizer and critic_obs_normalizer, or neither")
+        if obs_normalizer is not None:
+            if self.obs_dtype == torch.bfloat16:
+                raise ValueError("observation normalisers and bf16 observation rows are not served together: the normaliser kernels read "
+                                 "and write f32 rows")
+            self._init_normalizers(obs_normalizer, critic_obs_normalizer)
+
+    def _init_normalizers(self, actor_norm, critic_norm) -> None:
+        env, st = self.env, self.alg.storage
+        n, dims = env.num_envs, (st.observations.shape[-1], st.privileged_observations.shape[-1])
+        for nm, d in zip((actor_norm, critic_norm), dims):
+            bufs = (nm._mean, nm._var, nm._std)
+            if any(b.shape != (1, d) or b.dtype != torch.float32 or b.device != st.observations.device or not b.is_contiguous() for b in bufs):
+                raise ValueError(f"normaliser buffers must be contiguous f32 [1, {d}] tensors on {st.observations.device}")
+            if nm.count.dtype != torch.int64 or nm.count.device != st.observations.device:
+                raise ValueError("normaliser count must be an int64 scalar on the rollout's device")
+        if float(actor_norm.eps) != float(critic_norm.eps) or actor_norm.until != critic_norm.until:
+            raise ValueError("both normalisers are served by the same launches: they must share eps and until")
+        self.normalizers = (actor_norm, critic_norm)
+        # rows the networks read: the normalised rows of the current slot (the slots themselves stay raw until normalize_storage())
+        self.norm_rows = (torch.zeros(n, dims[0], device=self.device), torch.zeros(n, dims[1], device=self.device))
+        # per-slot snapshots (mean, 1 / (std + eps)) of both networks, one row per slot: [T + 1][2 * Da + 2 * Dc]; slot 0 of a rollout
+        # takes the snapshot behind the last step of the one before (`_carry`), or the one of begin()
+        steps = st.observations.shape[0]
+        self._snaps = torch.zeros(steps + 1, 2 * (dims[0] + dims[1]), device=self.device)
+        self._carry = torch.zeros(2 * (dims[0] + dims[1]), device=self.device)
+        self._snap_off = (0, 2 * dims[0])
+        self._norm_ws = []
+        import ctypes
+
+        for d in dims:
+            floats = ctypes.c_size_t()
+            _abi.call("lt_obs_norm_ws_floats", n, d, ctypes.byref(floats))
+            self._norm_ws.append(torch.zeros(floats.value, device=self.device))  # zeroed: it carries the recurrence's f64 state
+        self._primed = False
+
+    def snapshots(self, which: int) -> torch.Tensor:
+        """[T + 1, 2, D] view of the per-slot snapshots (mean, 1 / (std + eps)) of network `which` (0 policy, 1 critic)."""
+        d = self.norm_rows[which].shape[1]
+        return self._snaps[:, self._snap_off[which]:self._snap_off[which] + 2 * d].unflatten(1, (2, d))
+
+    def _normalize(self, rows, critic_rows, snap_row: torch.Tensor) -> None:
+        """Merge the raw rows of both networks into the running statistics (training mode only: normalizer.py `forward`), write the
+        snapshots into `snap_row` and the normalised rows into `norm_rows` - two launches, one in evaluation mode."""
+        a, c = self.normalizers
+        nets = []
+        for nm, x, off, out, ws in zip((a, c), (rows, critic_rows), self._snap_off, self.norm_rows, self._norm_ws):
+            nets += [x, x.shape[1], nm._mean, nm._var, nm._std, nm.count, snap_row[off:], out, ws]
+        _abi.call("lt_obs_norm_update", self.env.num_envs, int(a.training), -1 if a.until is None else int(a.until), float(a.eps), *nets,
+                  _abi.stream(self.device))
+
+    def begin(self) -> None:
+        """The start of a `learn()` call: the env's current rows are merged once and normalised (the runner's eager loop does the same
+        before its first step).  Later rollouts carry the rows and the snapshot behind their last step over; rollout() calls this
+        itself when nobody has - call it yourself before capturing a rollout into a graph, or the replays merge these rows again."""
+        if self.normalizers is not None:
+            with torch.inference_mode():
+                self._normalize(self.env.obs_policy, self.env.obs_critic, self._carry)
+            self._primed = True
+
+    @property
+    def last_critic_obs(self) -> torch.Tensor:
+        """The critic rows behind the last step as the critic sees them: what `compute_returns` bootstraps from."""
+        return self.env.obs_critic if self.normalizers is None else self.norm_rows[1]
+
+    def normalize_storage(self) -> None:
+        """Rewrite the storage's observation rows in place through the per-slot snapshots (one launch per network): every update
+        path then consumes normalised rows without knowing.  Once per rollout, after its last step; the next rollout refills slot 0
+        from the env's rows, which stay raw."""
+        if self.normalizers is None:
+            return
+        st = self.alg.storage
+        steps, n = st.step, self.env.num_envs
+        with torch.inference_mode():
+            for rows, off in zip((st.observations, st.privileged_observations), self._snap_off):
+                _abi.call("lt_obs_norm_apply", rows, steps * n, rows.shape[-1], self._snaps[0, off:], self._snaps.shape[1], n, rows,
+                          _abi.stream(self.device))
 
     def step(self, t: int, last: bool) -> None:
         if self.actor_mlp is not None:
@@ -91,11 +201,16 @@ class FusedRollout:
     @property
     def launches_per_step(self) -> int:
         """Kernel launches of one rollout step (the reference-shaped eager loop needs ~30)."""
-        return 2 if self.actor_mlp is not None else 11  # policy + value, env step (the population pass rides in the next step's launch)
+        base = 2 if self.actor_mlp is not None else 11  # policy + value, env step (the population pass rides in the next step's launch)
+        if self.normalizers is None:
+            return base
+        return base + (2 if self.normalizers[0].training else 1)  # column statistics, merge + snapshot + normalise
 
     def policy_value_launch(self, t: int) -> None:
         """The MLP launch of step t alone (bench.py times it for the MFMA roofline entry)."""
         obs, cobs, _, _ = self._rows(t, False)
+        if self.normalizers is not None:
+            obs, cobs = self.norm_rows
         self._policy_value(t, obs, cobs)
 
     def _policy_value(self, t: int, obs, cobs) -> None:
@@ -112,10 +227,24 @@ class FusedRollout:
         if not self.rows_in_storage:
             st.observations[t].copy_(obs)
             st.privileged_observations[t].copy_(cobs)
-        self._policy_value(t, obs, cobs)
+        if self.normalizers is None:
+            self._policy_value(t, obs, cobs)
+        else:
+            self._policy_value(t, *self.norm_rows)
         prev = (obs.data_ptr(), cobs.data_ptr()) if self.rows_in_storage else (0, 0)
         env.step_rollout_raw(self.actions.data_ptr(), prev[0], prev[1], nxt_p, nxt_c, st.values[t].data_ptr(), float(alg.gamma),
                              st.rewards[t].data_ptr(), st.dones[t].data_ptr())
+        self._normalize_next(t, last)
+
+    def _normalize_next(self, t: int, last: bool) -> None:
+        """The raw rows step t has just produced (slot t + 1, or the env's rows) -> statistics, snapshot t + 1, normalised rows."""
+        if self.normalizers is None:
+            return
+        st = self.alg.storage
+        if self.rows_in_storage and not last:
+            self._normalize(st.observations[t + 1], st.privileged_observations[t + 1], self._snaps[t + 1])
+        else:
+            self._normalize(self.env.obs_policy, self.env.obs_critic, self._snaps[t + 1])
 
     def _step_torch(self, t: int, last: bool) -> None:
         """torch modules for the networks (shapes outside lt_mlp's limits): GEMMs -> lt_rollout_act -> env step -> record,
@@ -126,27 +255,33 @@ class FusedRollout:
         stream = _abi.stream(self.device)
         n = env.num_envs
         obs, cobs, nxt_p, nxt_c = self._rows(t, last)
-        mu = ac.actor(obs)
+        seen, cseen = (obs, cobs) if self.normalizers is None else self.norm_rows  # what the networks read
+        mu = ac.actor(seen)
         rows = (None, None, None, None) if self.rows_in_storage else (obs, cobs, st.observations[t], st.privileged_observations[t])
         _abi.call("lt_rollout_act", n, env.num_obs, self._noise_seed, self._act_counter, mu, ac.std.data, None, *rows,
                   st.actions[t], st.mu[t], st.sigma[t], None, st.actions_log_prob[t], self.actions, stream)
         self.side.wait_stream(main)
         with torch.cuda.stream(self.side):
-            value = ac.critic(cobs)
+            value = ac.critic(cseen)
         prev = (obs.data_ptr(), cobs.data_ptr()) if self.rows_in_storage else (0, 0)
         env.step_rows_raw(self.actions.data_ptr(), prev[0], prev[1], nxt_p, nxt_c)
         main.wait_stream(self.side)
         value.record_stream(main)
         _abi.call("lt_rollout_record", n, float(alg.gamma), env.reward_buf, env.dones_buf, env.time_out_buf, value,
                   st.rewards[t], st.dones[t], st.values[t], self._act_counter, stream)
+        self._normalize_next(t, last)
 
     def rollout(self, num_steps: int) -> None:
         """`num_steps` consecutive steps into storage slots 0.. (inference mode, capturable)."""
         env, st = self.env, self.alg.storage
+        if self.normalizers is not None and not self._primed:
+            self.begin()
         st.clear()
         main = torch.cuda.current_stream(self.device)
         with torch.inference_mode():
             self._act_counter.copy_(env.counters[:1])
+            if self.normalizers is not None:
+                self._snaps[0].copy_(self._carry)
             if self.actor_mlp is not None:  # the optimizer has stepped since the last rollout
                 self.actor_mlp.pack()
                 self.critic_mlp.pack()
@@ -167,6 +302,8 @@ class FusedRollout:
                 if chain:
                     env.gate_update()
                     env.defer_gate(0)
+                if self.normalizers is not None:
+                    self._carry.copy_(self._snaps[num_steps])
                 if self._tail_rows is not None:
                     env.set_row_format(torch.float32)
                     env.obs_policy.copy_(self._tail_rows[0])

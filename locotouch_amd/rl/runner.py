@@ -76,6 +76,8 @@ class OnPolicyRunner:
         self.train_mode()
         n = env.num_envs
         fused = self._make_fused()
+        if fused is not None:
+            fused.begin()  # with normalisers: the env's current rows are merged once and normalised, as `it == start` below does
         rew_acc = torch.zeros(n, device=self.device)
         len_acc = torch.zeros(n, device=self.device)
         rewbuffer, lenbuffer = deque(maxlen=100), deque(maxlen=100)
@@ -86,8 +88,9 @@ class OnPolicyRunner:
             if fused is not None:
                 # GPU path: GEMMs + fused kernels, episode statistics from the env's device-side accumulators
                 fused.rollout(self.num_steps_per_env)
+                fused.normalize_storage()  # (nothing without normalisers) the slots hold raw rows until here
                 with torch.inference_mode():
-                    alg.compute_returns(env.obs_critic)
+                    alg.compute_returns(fused.last_critic_obs)
             else:
               with torch.inference_mode():
                 if it == start:
@@ -169,9 +172,14 @@ class OnPolicyRunner:
             return None
         if getattr(self.alg.actor_critic, "noise_std_type", "scalar") != "scalar" or type(self.alg.actor_critic) is not ActorCritic:
             return None  # the fused rollout packs the plain feed-forward actor / critic MLPs
-        if self.empirical_normalization:  # the fused rollout feeds raw observation rows to the MLP kernel
+        if not self.empirical_normalization:
+            return FusedRollout(target, self.alg)
+        # The device normaliser (csrc/lt_obs_norm.hip) reads and writes f32 rows, and it keeps per-process statistics: ranks cannot
+        # all-reduce them per step inside a captured rollout, and one sync per iteration would change what the policy sees.  bf16
+        # observation rows and multi-rank runs therefore keep the eager loop below.
+        if self.alg.storage.observations.dtype != torch.float32 or self.dist.world_size > 1:
             return None
-        return FusedRollout(target, self.alg)
+        return FusedRollout(target, self.alg, obs_normalizer=self.obs_normalizer, critic_obs_normalizer=self.critic_obs_normalizer)
 
     # ---- checkpoints (reference on_policy_runner.py:369-422) -------------------------------------------
     def save(self, path: str, infos=None) -> None:
