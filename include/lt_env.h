@@ -685,6 +685,8 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_n
 /* ---- running observation normaliser of the trainer (reference loco_rl/loco_rl/modules/normalizer.py:14-76): lt_obs_norm_ws_floats,
  * lt_obs_norm_update, lt_obs_norm_apply - declared in a header of their own, part of this ABI. */
 #include "lt_obs_norm.h"
+/* ---- one fused inference step of the deployed student policy: lt_student_* - declared in a header of their own, part of this ABI. */
+#include "lt_student.h"
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(_HERE)
 HEADER = os.path.join(REPO, "include", "lt_env.h")
 OBS_NORM_HEADER = os.path.join(REPO, "include", "lt_obs_norm.h")  # included by lt_env.h: the observation normaliser's entry points
+STUDENT_HEADER = os.path.join(REPO, "include", "lt_student.h")  # included by lt_env.h: the fused student inference step
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -134,6 +135,17 @@ VALUE_QUERIES = frozenset({
 if not VALUE_QUERIES <= set(EXPORTS) or any(SIGNATURES[n][0] is not ctypes.c_int for n in set(EXPORTS) - VALUE_QUERIES):
     raise ImportError("_abi.VALUE_QUERIES does not match include/lt_env.h: a query it names is gone, or a new entry point returns no status")
 
+# include/lt_student.h: constants and structures of its own (CONSTS / STRUCTS stay those of lt_env.h); STUDENT_VALUE_QUERIES is to
+# this header what VALUE_QUERIES is to lt_env.h
+STUDENT_CONSTS, _student_structs, STUDENT_SIGNATURES = parse_header(open(STUDENT_HEADER).read(), structs=STRUCTS)
+globals().update(STUDENT_CONSTS)
+LtStudentDesc, LtStudentParams = _student_structs["lt_student_desc"], _student_structs["lt_student_params"]
+STUDENT_VALUE_QUERIES = frozenset({"lt_student_step_launches"})
+if (not STUDENT_VALUE_QUERIES <= set(STUDENT_SIGNATURES) or any(r is not ctypes.c_int for r, _ in STUDENT_SIGNATURES.values())
+        or set(STUDENT_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES))):
+    raise ImportError("_abi.STUDENT_VALUE_QUERIES does not match include/lt_student.h, or an entry point there returns no int or repeats "
+                      "one of another header")
+
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
@@ -147,10 +159,10 @@ def load() -> ctypes.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
-        if name not in VALUE_QUERIES:
+        if name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES:
             _calls[name] = (fn, [ptr if t is ctypes.c_void_p else _ref if issubclass(t, ctypes._Pointer) and issubclass(t._type_, ctypes.Structure)
                                  else None for t in argtypes])
     if lib.lt_cfg_sizeof() != ctypes.sizeof(LtCfg):
@@ -191,7 +203,7 @@ def call(name: str, *args) -> None:
     try:
         fn, conv = _calls[name]
     except KeyError:
-        if name in VALUE_QUERIES:
+        if name in VALUE_QUERIES or name in STUDENT_VALUE_QUERIES:
             raise TypeError(f"{name} returns a value, not a status: call load().{name}(...)") from None
         if _lib is not None:
             raise

@@ -24,6 +24,17 @@ __device__ __forceinline__ float frsqrt(float x) { return __builtin_amdgcn_rsqf(
 __device__ __forceinline__ float fsin(float x) { return __sinf(x); }
 __device__ __forceinline__ float fcos(float x) { return __cosf(x); }
 
+// a wave-uniform integer as the compiler can see it (v_readfirstlane): what is indexed by it alone is fetched by scalar loads
+__device__ __forceinline__ int wave_uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+// v_mfma_f32_16x16x4_f32: D[m][n] += sum_k A[m][k] B[k][n] on a 16 x 16 tile, k < 4.  Lane (i = l % 16, q = l / 16) supplies A[i][q] and
+// B[q][i]; acc[v] of lane (i, q) is D[4 q + v][i].  Exact f32 products, f32 accumulation.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
+
+// nothing is scheduled across this point: loads issued above it stay above the arithmetic below it
+__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
+
 // a value the optimiser cannot tie to its source: what is recomputed from it is recomputed, not kept live in registers
 __device__ __forceinline__ float opaque(float x) { asm volatile("" : "+v"(x)); return x; }
 

@@ -24,7 +24,10 @@ from .tactile_recorder import TactileRecorder
 
 class Distillation:
     def __init__(self, env, cfg: DistillationCfg, teacher_policy=None, teacher_encoder=None, teacher_backbone_weights=None,
-                 training: bool = True, log_dir: str | None = None, checkpoint: str | None = None, verbose: bool = True):
+                 training: bool = True, log_dir: str | None = None, checkpoint: str | None = None, verbose: bool = True,
+                 fused_student_inference: bool = False):
+        """`fused_student_inference`: the student's env steps (DAgger collection, evaluation, play) run through
+        `FusedStudent` - one `lt_student_step` per step instead of `Student.forward`; training is unchanged."""
         self.env, self.cfg, self.training = env, cfg, training
         obs, extras = env.get_observations()
         groups = extras["observations"]
@@ -73,6 +76,14 @@ class Distillation:
                 if verbose:
                     print(f"[INFO] Loading student policy checkpoint from: {checkpoint}")
         self.history: list[dict] = []
+        self.fused_student = None
+        if fused_student_inference:
+            from .fused_student import FusedStudent
+
+            self.fused_student = FusedStudent.for_student(self.student)  # ValueError for an architecture the kernels do not serve
+
+    def _acting_student(self):
+        return self.student if self.fused_student is None else self.fused_student
 
     def run(self):
         return self.train() if self.training else self.play()
@@ -82,15 +93,17 @@ class Distillation:
         for it in range(c.num_iterations):
             print("-" * 100)
             rewards, lengths = self.replay_buffer.collect_data(
-                teacher_policy=self.teacher_policy_inference, student_policy=self.student if it else None,
+                teacher_policy=self.teacher_policy_inference, student_policy=self._acting_student() if it else None,
                 num_steps=c.dagger_data_steps if it else c.bc_data_steps)
             rec = self.log_trajectory_rewards_and_lengths(rewards, lengths, it)
             self.student.train_on_data(self.replay_buffer, it)
+            if self.fused_student is not None:
+                self.fused_student.refresh()
             rec.update({"iter": it, **{f"train/{k}": v for k, v in self.student.last_stats.items()}})
             self.history.append(rec)
             if it == c.num_iterations - 1:
                 self.replay_buffer.clear_buffer()
-                rewards, lengths = self.replay_buffer.evaluate(self.student, c.evaluation_trajs_num)
+                rewards, lengths = self.replay_buffer.evaluate(self._acting_student(), c.evaluation_trajs_num)
                 self.history.append({"iter": "eval", **self.log_trajectory_rewards_and_lengths(rewards, lengths, it + 1)})
                 print("Log dir: ", self.student.log_dir)
         if self.logger is not None:
@@ -121,6 +134,7 @@ class Distillation:
     def play(self, num_steps: int | None = None):
         """distillation.py:172-212: the student drives the env on DELAYED tactile rows; returns the actions of the last step."""
         self.student.eval()
+        student = self._acting_student()
         obs, extras = self.env.get_observations()
         groups = dict(extras["observations"])
         action, t = None, 0
@@ -128,11 +142,11 @@ class Distillation:
             while num_steps is None or t < num_steps:
                 self.tactile_recorder.record_new_tactile_signals(groups["tactile"])
                 groups["tactile"] = self.tactile_recorder.get_tactile_signals().clone()
-                action = self.student.extract_input_and_forward(groups)
+                action = student.extract_input_and_forward(groups)
                 obs, _, dones, extras = self.env.step(action)
                 groups = dict(extras["observations"])
                 done_mask = dones != 0
                 self.tactile_recorder.reset(done_mask)
-                self.student.reset(done_mask)
+                student.reset(done_mask)
                 t += 1
         return action

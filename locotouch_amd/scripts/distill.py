@@ -33,6 +33,8 @@ def main() -> None:
     ap.add_argument("--distill_lr", type=float, default=None)
     ap.add_argument("--logger", default=None, choices=["wandb", "tensorboard"])
     ap.add_argument("--play_steps", type=int, default=None, help="play mode: stop after this many env steps (default: run until interrupted)")
+    ap.add_argument("--fused_student", action="store_true",
+                    help="run the student's env steps (DAgger collection, evaluation, play) through the fused HIP step (lt_student_step)")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -78,11 +80,12 @@ def _run(args, cfg, agent, env, distill_root) -> None:
         mono = cfg.distillation_type == "Monolithic"
         d = Distillation(env, cfg, teacher_policy=runner.get_inference_policy(device=args.device),
                          teacher_encoder=None if mono else runner.get_inference_encoder(device=args.device),
-                         teacher_backbone_weights=None if mono else runner.get_backbone_weights(), training=True)
+                         teacher_backbone_weights=None if mono else runner.get_backbone_weights(), training=True,
+                         fused_student_inference=args.fused_student)
         d.train()
     else:
         ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or ".*", args.checkpoint_distill or "model_.*.pt")
-        d = Distillation(env, cfg, training=False, checkpoint=ckpt)
+        d = Distillation(env, cfg, training=False, checkpoint=ckpt, fused_student_inference=args.fused_student)
         d.play(num_steps=args.play_steps)
 
 
