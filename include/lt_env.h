@@ -687,6 +687,9 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_n
 #include "lt_obs_norm.h"
 /* ---- one fused inference step of the deployed student policy: lt_student_* - declared in a header of their own, part of this ABI. */
 #include "lt_student.h"
+/* ---- the tactile delay line and the per-step recording of the student-driven collection loop: lt_delay_*, lt_collect_after_step -
+ * declared in a header of their own, part of this ABI. */
+#include "lt_collect.h"
 
 #ifdef __cplusplus
 }

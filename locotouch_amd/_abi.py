@@ -17,6 +17,7 @@ REPO = os.path.dirname(_HERE)
 HEADER = os.path.join(REPO, "include", "lt_env.h")
 OBS_NORM_HEADER = os.path.join(REPO, "include", "lt_obs_norm.h")  # included by lt_env.h: the observation normaliser's entry points
 STUDENT_HEADER = os.path.join(REPO, "include", "lt_student.h")  # included by lt_env.h: the fused student inference step
+COLLECT_HEADER = os.path.join(REPO, "include", "lt_collect.h")  # included by lt_env.h: the tactile delay line and the step recording
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -146,6 +147,12 @@ if (not STUDENT_VALUE_QUERIES <= set(STUDENT_SIGNATURES) or any(r is not ctypes.
     raise ImportError("_abi.STUDENT_VALUE_QUERIES does not match include/lt_student.h, or an entry point there returns no int or repeats "
                       "one of another header")
 
+# include/lt_collect.h: all status-returning, launched (or, for the size query, called) through `call`
+COLLECT_SIGNATURES = parse_header(open(COLLECT_HEADER).read())[2]
+if (any(r is not ctypes.c_int for r, _ in COLLECT_SIGNATURES.values())
+        or set(COLLECT_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES))):
+    raise ImportError("include/lt_collect.h: every entry point returns a status and none repeats one of another header")
+
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
@@ -159,7 +166,7 @@ def load() -> ctypes.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
         if name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES:

@@ -25,9 +25,11 @@ from .tactile_recorder import TactileRecorder
 class Distillation:
     def __init__(self, env, cfg: DistillationCfg, teacher_policy=None, teacher_encoder=None, teacher_backbone_weights=None,
                  training: bool = True, log_dir: str | None = None, checkpoint: str | None = None, verbose: bool = True,
-                 fused_student_inference: bool = False):
+                 fused_student_inference: bool = False, fused_collection: bool = False):
         """`fused_student_inference`: the student's env steps (DAgger collection, evaluation, play) run through
-        `FusedStudent` - one `lt_student_step` per step instead of `Student.forward`; training is unchanged."""
+        `FusedStudent` - one `lt_student_step` per step instead of `Student.forward`; training is unchanged.
+        `fused_collection`: the tactile delay line and the per-step recording of `collect_data` / `play` run through
+        `DeviceTactileRecorder` (two HIP launches per step, same bits); needs a CUDA env, composes with the other switch."""
         self.env, self.cfg, self.training = env, cfg, training
         obs, extras = env.get_observations()
         groups = extras["observations"]
@@ -37,7 +39,12 @@ class Distillation:
         self.tactile_signal_dim = groups["tactile"].shape[-1]
         if verbose:
             print(f"[INFO] Tactile signal dim: {self.tactile_signal_dim}, Proprioception dim: {self.proprioception_dim}")
-        self.tactile_recorder = TactileRecorder(env.device, env.num_envs, self.tactile_signal_dim, cfg.min_delay, cfg.max_delay)
+        if fused_collection:
+            from .device_recorder import DeviceTactileRecorder  # ValueError for a non-CUDA env: no fall-back
+
+            self.tactile_recorder = DeviceTactileRecorder(env.device, env.num_envs, self.tactile_signal_dim, cfg.min_delay, cfg.max_delay)
+        else:
+            self.tactile_recorder = TactileRecorder(env.device, env.num_envs, self.tactile_signal_dim, cfg.min_delay, cfg.max_delay)
         cfg.device = str(env.device)
         self.logger = None
         if training:
@@ -138,10 +145,16 @@ class Distillation:
         obs, extras = self.env.get_observations()
         groups = dict(extras["observations"])
         action, t = None, 0
+        rec = self.tactile_recorder
+        fused = not isinstance(rec, TactileRecorder)
         with torch.inference_mode():
+            delayed = torch.empty_like(groups["tactile"], memory_format=torch.contiguous_format) if fused else None  # one reused buffer
             while num_steps is None or t < num_steps:
-                self.tactile_recorder.record_new_tactile_signals(groups["tactile"])
-                groups["tactile"] = self.tactile_recorder.get_tactile_signals().clone()
+                if fused:
+                    groups["tactile"] = rec.push(groups["tactile"], delayed)
+                else:
+                    rec.record_new_tactile_signals(groups["tactile"])
+                    groups["tactile"] = rec.get_tactile_signals().clone()
                 action = student.extract_input_and_forward(groups)
                 obs, _, dones, extras = self.env.step(action)
                 groups = dict(extras["observations"])

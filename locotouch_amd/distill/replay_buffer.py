@@ -14,12 +14,17 @@ What is different is where the data lives and when the host looks at it:
     overshoots the reference's stopping step by at most `check_every - 1` env steps; those steps are discarded, so the kept
     trajectories, their order, and the returned rewards / lengths are what the reference's per-step bookkeeping gives;
   * a padded batch is ONE gather per field (row index grid built on the device) instead of a Python loop over trajectories.
+
+Handed a `DeviceTactileRecorder` (opt-in, `Distillation(..., fused_collection=True)`), `collect_data` does its per-step recording in
+two HIP launches - `push` in front of the env step (delay line + the delayed rows and the policy rows into their store slots),
+`after_step` behind it (reward, done mask, delay-line reset) - and stores the same bits.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from .device_recorder import DeviceTactileRecorder
 from .tactile_recorder import TactileRecorder
 
 
@@ -71,6 +76,7 @@ class ReplayBuffer:
 
     def collect_data(self, teacher_policy, student_policy, num_steps: int):
         env, n, rec = self._env, self._num_envs, self._tactile_recorder
+        fused = isinstance(rec, DeviceTactileRecorder)
         if student_policy is not None:
             env.reset()          # replay_buffer.py:22-23
             student_policy.reset()  # (the reference carries the previous collection's hidden state into the fresh episodes)
@@ -117,17 +123,26 @@ class ReplayBuffer:
             while stop_t is None:
                 proprio = obs[:, :self._proprioception_dim]
                 action = teacher_policy(obs) if student_policy is None else student_policy(proprio, tactile)
-                blk.row("policy", t).copy_(obs)          # before the step overwrites the env's rows
-                rec.record_new_tactile_signals(tactile)
-                blk.row("tactile", t).copy_(rec.get_tactile_signals())
-                obs, reward, dones, extras = env.step(action)
-                tactile = extras["observations"]["tactile"]
-                blk.row("reward", t).copy_(reward)
-                done_mask = dones != 0
-                blk.row("dones", t).copy_(done_mask)
-                if student_policy is not None:
-                    student_policy.reset(done_mask)
-                rec.reset(done_mask)
+                if fused:  # one launch in front of the step, one behind it (include/lt_collect.h)
+                    rec.push(tactile, blk.row("tactile", t), copy=(obs, blk.row("policy", t)))
+                    obs, reward, dones, extras = env.step(action)
+                    tactile = extras["observations"]["tactile"]
+                    done_mask = blk.row("dones", t)
+                    rec.after_step(reward, dones, blk.row("reward", t), done_mask)
+                    if student_policy is not None:
+                        student_policy.reset(done_mask)  # (FusedStudent stores the store's row as its pending mask: no launch)
+                else:
+                    blk.row("policy", t).copy_(obs)          # before the step overwrites the env's rows
+                    rec.record_new_tactile_signals(tactile)
+                    blk.row("tactile", t).copy_(rec.get_tactile_signals())
+                    obs, reward, dones, extras = env.step(action)
+                    tactile = extras["observations"]["tactile"]
+                    blk.row("reward", t).copy_(reward)
+                    done_mask = dones != 0
+                    blk.row("dones", t).copy_(done_mask)
+                    if student_policy is not None:
+                        student_policy.reset(done_mask)
+                    rec.reset(done_mask)
                 t += 1
                 if t % self._check_every == 0:
                     bookkeeping(t)
