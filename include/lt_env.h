@@ -690,6 +690,9 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_n
 /* ---- the tactile delay line and the per-step recording of the student-driven collection loop: lt_delay_*, lt_collect_after_step -
  * declared in a header of their own, part of this ABI. */
 #include "lt_collect.h"
+/* ---- the episode ledger of DAgger collection and evaluation (the trajectory bookkeeping behind each env step): lt_ledger_* - declared
+ * in a header of their own, part of this ABI. */
+#include "lt_ledger.h"
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,7 @@ HEADER = os.path.join(REPO, "include", "lt_env.h")
 OBS_NORM_HEADER = os.path.join(REPO, "include", "lt_obs_norm.h")  # included by lt_env.h: the observation normaliser's entry points
 STUDENT_HEADER = os.path.join(REPO, "include", "lt_student.h")  # included by lt_env.h: the fused student inference step
 COLLECT_HEADER = os.path.join(REPO, "include", "lt_collect.h")  # included by lt_env.h: the tactile delay line and the step recording
+LEDGER_HEADER = os.path.join(REPO, "include", "lt_ledger.h")  # included by lt_env.h: the episode ledger of collection and evaluation
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -153,6 +154,12 @@ if (any(r is not ctypes.c_int for r, _ in COLLECT_SIGNATURES.values())
         or set(COLLECT_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES))):
     raise ImportError("include/lt_collect.h: every entry point returns a status and none repeats one of another header")
 
+# include/lt_ledger.h: all status-returning, launched (or, for the size query, called) through `call`; LEDGER_CONSTS: the head's field indices
+LEDGER_CONSTS, _, LEDGER_SIGNATURES = parse_header(open(LEDGER_HEADER).read())
+if (any(r is not ctypes.c_int for r, _ in LEDGER_SIGNATURES.values())
+        or set(LEDGER_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES))):
+    raise ImportError("include/lt_ledger.h: every entry point returns a status and none repeats one of another header")
+
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
@@ -166,7 +173,7 @@ def load() -> ctypes.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES, **LEDGER_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
         if name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES:

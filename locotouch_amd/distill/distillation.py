@@ -25,11 +25,15 @@ from .tactile_recorder import TactileRecorder
 class Distillation:
     def __init__(self, env, cfg: DistillationCfg, teacher_policy=None, teacher_encoder=None, teacher_backbone_weights=None,
                  training: bool = True, log_dir: str | None = None, checkpoint: str | None = None, verbose: bool = True,
-                 fused_student_inference: bool = False, fused_collection: bool = False):
+                 fused_student_inference: bool = False, fused_collection: bool = False,
+                 device_ledger: bool = False):
         """`fused_student_inference`: the student's env steps (DAgger collection, evaluation, play) run through
         `FusedStudent` - one `lt_student_step` per step instead of `Student.forward`; training is unchanged.
         `fused_collection`: the tactile delay line and the per-step recording of `collect_data` / `play` run through
-        `DeviceTactileRecorder` (two HIP launches per step, same bits); needs a CUDA env, composes with the other switch."""
+        `DeviceTactileRecorder` (two HIP launches per step, same bits); needs a CUDA env, composes with the other switch.
+        `device_ledger`: the trajectory bookkeeping of `collect_data` / `evaluate` runs in `DeviceEpisodeLedger` (one HIP launch behind
+        each env step, a non-blocking poll instead of the blocking copy every `check_every` steps; same bits, the loop may run up to
+        `2 * check_every - 1` discarded steps past the stopping step); needs a CUDA env, composes with the other two."""
         self.env, self.cfg, self.training = env, cfg, training
         obs, extras = env.get_observations()
         groups = extras["observations"]
@@ -75,8 +79,10 @@ class Distillation:
                                    teacher_policy_inference=teacher_policy,
                                    teacher_encoder_inference=None if mono else teacher_encoder,
                                    teacher_backbone_weights=None if mono else teacher_backbone_weights, logger=self.logger, verbose=verbose)
-            self.replay_buffer = ReplayBuffer(env, self.tactile_recorder, self.proprioception_dim)
+            self.replay_buffer = ReplayBuffer(env, self.tactile_recorder, self.proprioception_dim, device_ledger=device_ledger)
         else:
+            if device_ledger and torch.device(env.device).type != "cuda":  # (play keeps no books, but the switch never passes quietly)
+                raise ValueError("Distillation: device_ledger needs a CUDA env")
             self.student = Student(cfg, self.proprioception_dim, self.tactile_signal_dim, env.num_actions, verbose=verbose)
             if checkpoint is not None:
                 self.student.load_checkpoint(checkpoint)

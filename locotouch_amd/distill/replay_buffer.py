@@ -18,12 +18,22 @@ What is different is where the data lives and when the host looks at it:
 Handed a `DeviceTactileRecorder` (opt-in, `Distillation(..., fused_collection=True)`), `collect_data` does its per-step recording in
 two HIP launches - `push` in front of the env step (delay line + the delayed rows and the policy rows into their store slots),
 `after_step` behind it (reward, done mask, delay-line reset) - and stores the same bits.
+
+With `device_ledger=True` (opt-in, `Distillation(..., device_ledger=True)`) the trajectory bookkeeping of `collect_data` and `evaluate`
+runs on the device too (`DeviceEpisodeLedger`, include/lt_ledger.h): one launch behind each env step applies the same rules to the
+reward and done-mask rows the loop stores anyway, and stops ITSELF on the step the host rules stop on.  Every `check_every` steps the
+loop polls the ledger's 64-byte head without blocking and sees the head of the poll before, so it learns of the stop up to two poll
+intervals late: it overshoots the stopping step by at most `2 * check_every - 1` env steps (without the ledger: `check_every - 1`).
+Those steps are discarded exactly as the shorter overshoot is - the ledger ignores them, the store is cut at the stopping step - so the
+kept trajectories, their order, the returned rewards / lengths and the carried reward sums are the same bits.  The only blocking copy
+is the one that reads the lists once the loop has learnt that the ledger stopped.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from .device_ledger import DeviceEpisodeLedger
 from .device_recorder import DeviceTactileRecorder
 from .tactile_recorder import TactileRecorder
 
@@ -49,7 +59,7 @@ class _Block:
 
 
 class ReplayBuffer:
-    def __init__(self, env, tactile_recorder: TactileRecorder, proprioception_dim: int, check_every: int = 16):
+    def __init__(self, env, tactile_recorder: TactileRecorder, proprioception_dim: int, check_every: int = 16, device_ledger: bool = False):
         self._env = env
         self._num_envs = env.num_envs
         self._device = env.device
@@ -67,6 +77,8 @@ class ReplayBuffer:
         self._traj_len: list[int] = []
         self._flat = None                  # (policy rows, tactile rows) concatenated over blocks, built lazily
         self._traj_dev = None
+        # the ledger's lists hold four poll intervals: by the time they could be half full the loop has seen a head that says so
+        self._ledger = DeviceEpisodeLedger(self._device, self._num_envs, 4 * self._check_every) if device_ledger else None  # ValueError off CUDA
 
     # ------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -85,6 +97,8 @@ class ReplayBuffer:
         dims = {"policy": (obs.shape[1], torch.float32), "tactile": (tactile.shape[1], torch.float32),
                 "reward": (0, torch.float32), "dones": (0, torch.bool)}
         blk = _Block(n, dims, self._device)
+        if self._ledger is not None:
+            return self._collect_with_ledger(teacher_policy, student_policy, num_steps, obs, tactile, blk)
         start_idx = np.zeros(n, dtype=np.int64)
         start_count = self._steps_count
         rewards_out, lengths_out, trajs = [], [], []   # trajs: (env, start, end) of this block
@@ -147,6 +161,49 @@ class ReplayBuffer:
                 if t % self._check_every == 0:
                     bookkeeping(t)
         self._reward_sums.copy_(torch.from_numpy(reward_sums.astype(np.float32)))
+        return self._keep_block(blk, stop_t, trajs, rewards_out, lengths_out)
+
+    def _collect_with_ledger(self, teacher_policy, student_policy, num_steps: int, obs, tactile, blk: _Block):
+        """`collect_data`'s loop with the bookkeeping in the device ledger: the same env steps and recording, `ledger.step` behind each
+        step on the rows just stored, a non-blocking poll every `check_every` steps (module text: the overshoot)."""
+        rec, led = self._tactile_recorder, self._ledger
+        fused = isinstance(rec, DeviceTactileRecorder)
+        led.begin(self._reward_sums, keep_target=num_steps)
+        t, head = 0, None
+        with torch.no_grad():
+            while head is None or not head.stopped_at:
+                proprio = obs[:, :self._proprioception_dim]
+                action = teacher_policy(obs) if student_policy is None else student_policy(proprio, tactile)
+                done_mask = blk.row("dones", t)
+                if fused:
+                    rec.push(tactile, blk.row("tactile", t), copy=(obs, blk.row("policy", t)))
+                    obs, reward, dones, extras = self._env.step(action)
+                    tactile = extras["observations"]["tactile"]
+                    rec.after_step(reward, dones, blk.row("reward", t), done_mask)
+                    if student_policy is not None:
+                        student_policy.reset(done_mask)
+                else:
+                    blk.row("policy", t).copy_(obs)
+                    rec.record_new_tactile_signals(tactile)
+                    blk.row("tactile", t).copy_(rec.get_tactile_signals())
+                    obs, reward, dones, extras = self._env.step(action)
+                    tactile = extras["observations"]["tactile"]
+                    blk.row("reward", t).copy_(reward)
+                    done_mask.copy_(dones != 0)
+                    if student_policy is not None:
+                        student_policy.reset(done_mask)
+                    rec.reset(done_mask)
+                led.step(blk.row("reward", t), done_mask)
+                t += 1
+                if t % self._check_every == 0:
+                    head = led.poll()
+        rewards_out, lengths_out, trajs = led.drain(head)
+        led.end(self._reward_sums)
+        self._steps_count += head.kept_steps
+        return self._keep_block(blk, head.stopped_at, trajs, rewards_out, lengths_out)
+
+    def _keep_block(self, blk: _Block, stop_t: int, trajs, rewards_out, lengths_out):
+        n = self._num_envs
         # keep the block's rows up to the stopping step
         keep = stop_t
         base = self._rows_total
@@ -210,6 +267,8 @@ class ReplayBuffer:
     def evaluate(self, student_policy, num_trajs: int):
         """replay_buffer.py:131-151: roll the student until `num_trajs` episodes have finished (from the env's current state)."""
         env, n = self._env, self._num_envs
+        if self._ledger is not None:
+            return self._evaluate_with_ledger(student_policy, num_trajs)
         rewards, lengths = [], []
         reward_sums = self._reward_sums.cpu().numpy().astype(np.float64)
         env_steps = np.zeros(n, dtype=np.int64)
@@ -240,6 +299,31 @@ class ReplayBuffer:
                         break
         self._reward_sums.copy_(torch.from_numpy(reward_sums.astype(np.float32)))
         return rewards, lengths
+
+    def _evaluate_with_ledger(self, student_policy, num_trajs: int):
+        """`evaluate`'s loop with the bookkeeping in the device ledger (episode target; no trajectory list)."""
+        env, n, k, led = self._env, self._num_envs, self._check_every, self._ledger
+        if num_trajs <= 0:  # (the host loop does not step at all)
+            return [], []
+        rbuf = torch.zeros(k, n, device=self._device)
+        dbuf = torch.zeros(k, n, dtype=torch.bool, device=self._device)
+        led.begin(self._reward_sums, episode_target=num_trajs, with_trajs=False)
+        head = None
+        with torch.no_grad():
+            obs, tactile = self._split_obs(env.get_observations())
+            while head is None or not head.stopped_at:
+                for i in range(k):
+                    action = student_policy(obs[:, :self._proprioception_dim], tactile)
+                    obs, reward, dones, extras = env.step(action)
+                    tactile = extras["observations"]["tactile"]
+                    rbuf[i].copy_(reward)
+                    dbuf[i].copy_(dones != 0)
+                    student_policy.reset(dbuf[i])
+                    led.step(rbuf[i], dbuf[i])
+                head = led.poll()
+        rewards, lengths, _ = led.drain(head)
+        led.end(self._reward_sums)
+        return rewards, [float(x) for x in lengths]
 
     @property
     def num_trajs(self) -> int:
