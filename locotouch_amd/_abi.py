@@ -19,6 +19,7 @@ OBS_NORM_HEADER = os.path.join(REPO, "include", "lt_obs_norm.h")  # included by 
 STUDENT_HEADER = os.path.join(REPO, "include", "lt_student.h")  # included by lt_env.h: the fused student inference step
 COLLECT_HEADER = os.path.join(REPO, "include", "lt_collect.h")  # included by lt_env.h: the tactile delay line and the step recording
 LEDGER_HEADER = os.path.join(REPO, "include", "lt_ledger.h")  # included by lt_env.h: the episode ledger of collection and evaluation
+CNN_TRAIN_HEADER = os.path.join(REPO, "include", "lt_cnn_train.h")  # the training form of the student's tactile CNN head
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -160,6 +161,17 @@ if (any(r is not ctypes.c_int for r, _ in LEDGER_SIGNATURES.values())
         or set(LEDGER_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES))):
     raise ImportError("include/lt_ledger.h: every entry point returns a status and none repeats one of another header")
 
+# include/lt_cnn_train.h: constants and structures of its own; CNN_TRAIN_VALUE_QUERIES is to this header what VALUE_QUERIES is to lt_env.h
+CNN_TRAIN_CONSTS, _cnn_structs, CNN_TRAIN_SIGNATURES = parse_header(open(CNN_TRAIN_HEADER).read())
+globals().update(CNN_TRAIN_CONSTS)
+LtCnnDesc, LtCnnParams, LtCnnGrads = _cnn_structs["lt_cnn_desc"], _cnn_structs["lt_cnn_params"], _cnn_structs["lt_cnn_grads"]
+CNN_TRAIN_VALUE_QUERIES = frozenset({"lt_cnn_launches"})
+if (not CNN_TRAIN_VALUE_QUERIES <= set(CNN_TRAIN_SIGNATURES) or any(r is not ctypes.c_int for r, _ in CNN_TRAIN_SIGNATURES.values())
+        or set(CNN_TRAIN_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
+                                        | set(LEDGER_SIGNATURES))):
+    raise ImportError("_abi.CNN_TRAIN_VALUE_QUERIES does not match include/lt_cnn_train.h, or an entry point there returns no int or "
+                      "repeats one of another header")
+
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
@@ -173,10 +185,11 @@ def load() -> ctypes.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES, **LEDGER_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES, **LEDGER_SIGNATURES,
+                                      **CNN_TRAIN_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
-        if name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES:
+        if name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES and name not in CNN_TRAIN_VALUE_QUERIES:
             _calls[name] = (fn, [ptr if t is ctypes.c_void_p else _ref if issubclass(t, ctypes._Pointer) and issubclass(t._type_, ctypes.Structure)
                                  else None for t in argtypes])
     if lib.lt_cfg_sizeof() != ctypes.sizeof(LtCfg):
@@ -217,7 +230,7 @@ def call(name: str, *args) -> None:
     try:
         fn, conv = _calls[name]
     except KeyError:
-        if name in VALUE_QUERIES or name in STUDENT_VALUE_QUERIES:
+        if name in VALUE_QUERIES or name in STUDENT_VALUE_QUERIES or name in CNN_TRAIN_VALUE_QUERIES:
             raise TypeError(f"{name} returns a value, not a status: call load().{name}(...)") from None
         if _lib is not None:
             raise

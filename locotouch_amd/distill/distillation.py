@@ -26,14 +26,17 @@ class Distillation:
     def __init__(self, env, cfg: DistillationCfg, teacher_policy=None, teacher_encoder=None, teacher_backbone_weights=None,
                  training: bool = True, log_dir: str | None = None, checkpoint: str | None = None, verbose: bool = True,
                  fused_student_inference: bool = False, fused_collection: bool = False,
-                 device_ledger: bool = False):
+                 device_ledger: bool = False, fused_cnn_training: bool = False):
         """`fused_student_inference`: the student's env steps (DAgger collection, evaluation, play) run through
         `FusedStudent` - one `lt_student_step` per step instead of `Student.forward`; training is unchanged.
         `fused_collection`: the tactile delay line and the per-step recording of `collect_data` / `play` run through
         `DeviceTactileRecorder` (two HIP launches per step, same bits); needs a CUDA env, composes with the other switch.
         `device_ledger`: the trajectory bookkeeping of `collect_data` / `evaluate` runs in `DeviceEpisodeLedger` (one HIP launch behind
         each env step, a non-blocking poll instead of the blocking copy every `check_every` steps; same bits, the loop may run up to
-        `2 * check_every - 1` discarded steps past the stopping step); needs a CUDA env, composes with the other two."""
+        `2 * check_every - 1` discarded steps past the stopping step); needs a CUDA env, composes with the other two.
+        `fused_cnn_training`: the student's tactile CNN head trains through the HIP kernels of include/lt_cnn_train.h
+        (`CNN2dHead.enable_fused_training`: direct convolutions, a backward that recomputes the maps) instead of `Conv2dAsGemm` and
+        autograd's saved maps; needs a CUDA env and a served conv stack (ValueError otherwise), composes with the other three."""
         self.env, self.cfg, self.training = env, cfg, training
         obs, extras = env.get_observations()
         groups = extras["observations"]
@@ -49,6 +52,10 @@ class Distillation:
             self.tactile_recorder = DeviceTactileRecorder(env.device, env.num_envs, self.tactile_signal_dim, cfg.min_delay, cfg.max_delay)
         else:
             self.tactile_recorder = TactileRecorder(env.device, env.num_envs, self.tactile_signal_dim, cfg.min_delay, cfg.max_delay)
+        if fused_cnn_training and torch.device(env.device).type != "cuda":
+            raise ValueError("Distillation: fused_cnn_training needs a CUDA env")
+        if fused_cnn_training and not training:  # (play trains nothing, but the switch never passes quietly)
+            raise ValueError("Distillation: fused_cnn_training needs training=True")
         cfg.device = str(env.device)
         self.logger = None
         if training:
@@ -80,6 +87,10 @@ class Distillation:
                                    teacher_encoder_inference=None if mono else teacher_encoder,
                                    teacher_backbone_weights=None if mono else teacher_backbone_weights, logger=self.logger, verbose=verbose)
             self.replay_buffer = ReplayBuffer(env, self.tactile_recorder, self.proprioception_dim, device_ledger=device_ledger)
+            if fused_cnn_training:
+                if not hasattr(getattr(self.student, "pre_encoder", None), "enable_fused_training"):
+                    raise ValueError("Distillation: fused_cnn_training needs a CNN2dHead pre_encoder")
+                self.student.pre_encoder.enable_fused_training(self.student.tactile_signal_img_shape)
         else:
             if device_ledger and torch.device(env.device).type != "cuda":  # (play keeps no books, but the switch never passes quietly)
                 raise ValueError("Distillation: device_ledger needs a CUDA env")

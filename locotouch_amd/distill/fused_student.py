@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import _abi
+from ..rl.cnn_train import fill_conv_stack
 from ..rl.models import MLP, RNN, CNN2dHead
 
 _ACT = {nn.ELU: "LT_ACT_ELU", nn.ReLU: "LT_ACT_RELU", nn.Tanh: "LT_ACT_TANH"}
@@ -47,34 +48,7 @@ def describe(student):
         raise ValueError("FusedStudent: the fused step serves pre_encoder CNN2dHead -> student_encoder RNN -> student_backbone MLP")
     d = _abi.LtStudentDesc()
     d.img_channels, d.img_height, d.img_width = (int(v) for v in student.tactile_signal_img_shape)
-    mods = list(pre.conv.conv)
-    convs = [m for m in mods if isinstance(m, nn.Conv2d)]
-    pools = {}
-    if len(convs) > _abi.LT_STUDENT_MAX_CONVS:
-        raise ValueError("FusedStudent: pre_encoder: more than LT_STUDENT_MAX_CONVS convolutions")
-    d.num_convs = len(convs)
-    ci = -1
-    for m in mods:
-        if isinstance(m, nn.Conv2d):
-            ci += 1
-        elif isinstance(m, nn.MaxPool2d):
-            pools[ci] = int(m.kernel_size if isinstance(m.kernel_size, int) else m.kernel_size[0])
-        elif isinstance(m, nn.ReLU):
-            d.conv_activation = _abi.CONSTS["LT_ACT_RELU"]
-        else:  # another activation, a norm layer, anything else: not served, and said by name
-            raise ValueError(f"FusedStudent: pre_encoder: {type(m).__name__} in the conv stack is not served (Conv2d, ReLU and MaxPool2d are)")
-    d.use_maxpool = int(bool(pools))
-    for i, c in enumerate(convs):
-        if c.kernel_size[0] != c.kernel_size[1] or c.stride[0] != c.stride[1] or c.padding[0] != c.padding[1] or c.dilation != (1, 1) or c.groups != 1:
-            raise ValueError("FusedStudent: pre_encoder: square kernels, equal strides / paddings, no dilation and no groups are served")
-        if pools and c.stride[0] != 1:
-            raise ValueError("FusedStudent: pre_encoder: a strided convolution beside max-pools is not served")
-        d.conv_channels[i], d.conv_kernel[i], d.conv_padding[i] = c.out_channels, c.kernel_size[0], c.padding[0]
-        d.conv_stride[i] = pools.get(i, 1) if pools else c.stride[0]
-    if not isinstance(pre.head, MLP) or len([m for m in pre.head.model if isinstance(m, nn.Linear)]) != 1:
-        raise ValueError("FusedStudent: pre_encoder.head: one Linear layer is served")
-    head = pre.head.model[0]
-    d.head_out = head.out_features
+    convs, head = fill_conv_stack(d, pre, "FusedStudent: pre_encoder")
     rnn = enc.memory.rnn
     d.rnn_type = _abi.LT_STUDENT_RNN_GRU if isinstance(rnn, nn.GRU) else _abi.LT_STUDENT_RNN_LSTM
     d.rnn_layers, d.rnn_hidden = rnn.num_layers, rnn.hidden_size

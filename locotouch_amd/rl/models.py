@@ -192,6 +192,7 @@ class CNN2dHead(nn.Module):
         self.conv = CNN2d(in_channels=c, channels=channels, kernel_sizes=kernel_sizes, strides=strides, paddings=paddings,
                           nonlinearity=nonlinearity, use_maxpool=use_maxpool, normlayer=normlayer)
         flat = self.conv.conv_out_size(h, w)
+        self._fused_cnn = None  # the validated lt_cnn_desc once enable_fused_training has run
         if hidden_sizes or output_size:
             self.head = MLP(flat, hidden_sizes, output_size, activation=nonlinearity)
             self._output_size = output_size if output_size is not None else (hidden_sizes if isinstance(hidden_sizes, int) else hidden_sizes[-1])
@@ -200,7 +201,19 @@ class CNN2dHead(nn.Module):
             self._output_size = flat
 
     def forward(self, x):
+        if self._fused_cnn is not None and x.is_cuda and torch.is_grad_enabled():
+            from . import cnn_train
+
+            return cnn_train.forward(self, x)
         return self.head(self.conv(x).reshape(x.shape[0], -1))
+
+    def enable_fused_training(self, img_shape):
+        """Opt in: CUDA forwards with grad enabled ([N, C, H, W] or [N, C H W]) run through the HIP kernels of include/lt_cnn_train.h,
+        whose backward recomputes the maps (rl/cnn_train.py).  `torch.no_grad()` and CPU inputs keep the module path.  ValueError with
+        the validator's message for a stack the kernels do not serve and for non-CUDA / non-float32 parameters: no fall-back."""
+        from . import cnn_train
+
+        cnn_train.enable(self, img_shape)
 
     @property
     def output_size(self):

@@ -39,6 +39,8 @@ def main() -> None:
                     help="run the tactile delay line and the per-step recording of collection / play in HIP kernels (lt_delay_push, lt_collect_after_step)")
     ap.add_argument("--device_ledger", action="store_true",
                     help="keep the trajectory bookkeeping of collection / evaluation on the device (lt_ledger_step behind each env step)")
+    ap.add_argument("--fused_cnn_train", action="store_true",
+                    help="train the student's tactile CNN head through the HIP kernels of lt_cnn_train.h (lt_cnn_forward, lt_cnn_backward)")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -85,7 +87,8 @@ def _run(args, cfg, agent, env, distill_root) -> None:
         d = Distillation(env, cfg, teacher_policy=runner.get_inference_policy(device=args.device),
                          teacher_encoder=None if mono else runner.get_inference_encoder(device=args.device),
                          teacher_backbone_weights=None if mono else runner.get_backbone_weights(), training=True,
-                         fused_student_inference=args.fused_student, fused_collection=args.fused_collect, device_ledger=args.device_ledger)
+                         fused_student_inference=args.fused_student, fused_collection=args.fused_collect, device_ledger=args.device_ledger,
+                         fused_cnn_training=args.fused_cnn_train)
         d.train()
     else:
         ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or ".*", args.checkpoint_distill or "model_.*.pt")
