@@ -693,6 +693,9 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_n
 /* ---- the episode ledger of DAgger collection and evaluation (the trajectory bookkeeping behind each env step): lt_ledger_* - declared
  * in a header of their own, part of this ABI. */
 #include "lt_ledger.h"
+/* ---- the two ends of the student's behaviour-cloning step (batch assembly, the masked loss and its statistics, the AdamW update):
+ * lt_bc_*, lt_adamw_step - declared in a header of their own, part of this ABI. */
+#include "lt_bc.h"
 
 #ifdef __cplusplus
 }

@@ -26,7 +26,7 @@ class Distillation:
     def __init__(self, env, cfg: DistillationCfg, teacher_policy=None, teacher_encoder=None, teacher_backbone_weights=None,
                  training: bool = True, log_dir: str | None = None, checkpoint: str | None = None, verbose: bool = True,
                  fused_student_inference: bool = False, fused_collection: bool = False,
-                 device_ledger: bool = False, fused_cnn_training: bool = False):
+                 device_ledger: bool = False, fused_cnn_training: bool = False, fused_bc_step: bool = False):
         """`fused_student_inference`: the student's env steps (DAgger collection, evaluation, play) run through
         `FusedStudent` - one `lt_student_step` per step instead of `Student.forward`; training is unchanged.
         `fused_collection`: the tactile delay line and the per-step recording of `collect_data` / `play` run through
@@ -36,7 +36,11 @@ class Distillation:
         `2 * check_every - 1` discarded steps past the stopping step); needs a CUDA env, composes with the other two.
         `fused_cnn_training`: the student's tactile CNN head trains through the HIP kernels of include/lt_cnn_train.h
         (`CNN2dHead.enable_fused_training`: direct convolutions, a backward that recomputes the maps) instead of `Conv2dAsGemm` and
-        autograd's saved maps; needs a CUDA env and a served conv stack (ValueError otherwise), composes with the other three."""
+        autograd's saved maps; needs a CUDA env and a served conv stack (ValueError otherwise), composes with the other three.
+        `fused_bc_step`: the two ends of the student's training step run through the HIP kernels of include/lt_bc.h - padded batches are
+        assembled by one launch (`ReplayBuffer(..., fused_batches=True)`), the masked loss with its statistics takes two launches forward
+        and one backward and AdamW one (`Student.enable_fused_bc_step`); needs a CUDA env and `training=True` (ValueError otherwise),
+        composes with the other four."""
         self.env, self.cfg, self.training = env, cfg, training
         obs, extras = env.get_observations()
         groups = extras["observations"]
@@ -56,6 +60,10 @@ class Distillation:
             raise ValueError("Distillation: fused_cnn_training needs a CUDA env")
         if fused_cnn_training and not training:  # (play trains nothing, but the switch never passes quietly)
             raise ValueError("Distillation: fused_cnn_training needs training=True")
+        if fused_bc_step and torch.device(env.device).type != "cuda":
+            raise ValueError("Distillation: fused_bc_step needs a CUDA env")
+        if fused_bc_step and not training:  # (play trains nothing, but the switch never passes quietly)
+            raise ValueError("Distillation: fused_bc_step needs training=True")
         cfg.device = str(env.device)
         self.logger = None
         if training:
@@ -86,7 +94,10 @@ class Distillation:
                                    teacher_policy_inference=teacher_policy,
                                    teacher_encoder_inference=None if mono else teacher_encoder,
                                    teacher_backbone_weights=None if mono else teacher_backbone_weights, logger=self.logger, verbose=verbose)
-            self.replay_buffer = ReplayBuffer(env, self.tactile_recorder, self.proprioception_dim, device_ledger=device_ledger)
+            self.replay_buffer = ReplayBuffer(env, self.tactile_recorder, self.proprioception_dim, device_ledger=device_ledger,
+                                              fused_batches=fused_bc_step)
+            if fused_bc_step:
+                self.student.enable_fused_bc_step()
             if fused_cnn_training:
                 if not hasattr(getattr(self.student, "pre_encoder", None), "enable_fused_training"):
                     raise ValueError("Distillation: fused_cnn_training needs a CNN2dHead pre_encoder")

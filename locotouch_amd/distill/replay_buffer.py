@@ -27,12 +27,18 @@ intervals late: it overshoots the stopping step by at most `2 * check_every - 1`
 Those steps are discarded exactly as the shorter overshoot is - the ledger ignores them, the store is cut at the stopping step - so the
 kept trajectories, their order, the returned rewards / lengths and the carried reward sums are the same bits.  The only blocking copy
 is the one that reads the lists once the loop has learnt that the ledger stopped.
+
+With `fused_batches=True` (opt-in, `Distillation(..., fused_bc_step=True)`) a padded batch is assembled by ONE HIP launch
+(`lt_bc_gather`, include/lt_bc.h) behind one upload of the batch's trajectory indices: every row of the batch is written once, copied
+from the store or as zeros, instead of gathered and then multiplied by the mask.  Only rows move, so the dictionary is `torch.equal` to
+the default path's; the permutation of `to_recurrent_generator` is untouched, so one seed yields the same batches either way.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from .. import _abi
 from .device_ledger import DeviceEpisodeLedger
 from .device_recorder import DeviceTactileRecorder
 from .tactile_recorder import TactileRecorder
@@ -59,7 +65,11 @@ class _Block:
 
 
 class ReplayBuffer:
-    def __init__(self, env, tactile_recorder: TactileRecorder, proprioception_dim: int, check_every: int = 16, device_ledger: bool = False):
+    def __init__(self, env, tactile_recorder: TactileRecorder, proprioception_dim: int, check_every: int = 16, device_ledger: bool = False,
+                 fused_batches: bool = False):
+        if fused_batches and torch.device(env.device).type != "cuda":
+            raise ValueError("ReplayBuffer: fused_batches needs a CUDA device (there is no fall-back)")
+        self._fused_batches = bool(fused_batches)
         self._env = env
         self._num_envs = env.num_envs
         self._device = env.device
@@ -237,7 +247,29 @@ class ReplayBuffer:
         for s in range(0, num_trajs, batch_size):
             yield self._prepare_padded_sequence(order[s:min(s + batch_size, num_trajs)], pad_to=pad)
 
+    def _gather_padded_sequence(self, traj_indices, pad_to=None):
+        """`_prepare_padded_sequence` as one upload of the indices and one `lt_bc_gather` launch; fresh outputs, every element written."""
+        (policy, tactile), (first, length) = self._materialise()
+        nb = len(traj_indices)
+        L = int(max(self._traj_len[i] for i in traj_indices))
+        B = nb
+        if pad_to is not None:
+            L, B = max(L, int(pad_to[0])), max(nb, int(pad_to[1]))
+        if policy.dtype != torch.float32 or tactile.dtype != torch.float32 or not policy.is_contiguous() or not tactile.is_contiguous():
+            raise ValueError("ReplayBuffer (fused_batches): the stored rows must be contiguous float32")
+        idx = torch.from_numpy(np.ascontiguousarray(traj_indices, dtype=np.int64)).to(self._device)
+        pe, td = policy.shape[1], tactile.shape[1]
+        pol = torch.empty(L, B, pe, device=self._device)
+        tac = torch.empty(L, B, td, device=self._device)
+        masks = torch.empty(L, B, dtype=torch.bool, device=self._device)
+        _abi.call("lt_bc_gather", policy, tactile, policy.shape[0], pe, td, first, length, first.numel(), idx, nb, self._num_envs, L, B,
+                  pol, tac, masks, _abi.stream(self._device))
+        return dict(proprioceptions=pol[..., :self._proprioception_dim], teacher_encoder_obses=pol[..., self._proprioception_dim:],
+                    tactile_signals=tac, masks=masks)
+
     def _prepare_padded_sequence(self, traj_indices, pad_to=None):
+        if self._fused_batches:
+            return self._gather_padded_sequence(traj_indices, pad_to)
         (policy, tactile), (first, length) = self._materialise()
         idx = torch.as_tensor(np.asarray(traj_indices), dtype=torch.int64, device=self._device)
         f, ln = first[idx], length[idx]

@@ -58,6 +58,7 @@ class Student(nn.Module):
         self.clip_actions, self.clip_range = cfg.clip_actions, cfg.clip_range
         self.action_scale_within_env = cfg.action_scale_within_env
         self.last_stats: dict = {}
+        self._flat_adamw = None  # the FlatAdamW around `_optimizer` once enable_fused_bc_step has run
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def encoder_forward(self, tactile_signal, hidden_states=None):
@@ -125,11 +126,55 @@ class Student(nn.Module):
         self._optimizer.step()
         return loss.detach(), mse, mae
 
+    def enable_fused_bc_step(self) -> None:
+        """Opt-in: `training_step` computes the masked loss and its statistics with `bc_loss` (include/lt_bc.h: two launches forward,
+        one backward) and steps through `FlatAdamW` (one `lt_adamw_step` launch; only the parameters with `requires_grad` are adopted,
+        so RMA's frozen backbone stays out).  `batch_loss` and `_eager_step` stay the definition.  Composes with the CNN head's
+        `enable_fused_training`.  ValueError for a student that is not on a CUDA device: nothing falls back."""
+        from ..rl.flat_adamw import FlatAdamW
+
+        if torch.device(self.device).type != "cuda":
+            raise ValueError("Student.enable_fused_bc_step needs a CUDA device")
+        if self._flat_adamw is None:
+            self._flat_adamw = FlatAdamW(self._optimizer)
+
+    def _teacher_obs(self, prop, enc_obs):
+        """`cat((prop, enc_obs), -1)`, or the tensor both are column slices of (`ReplayBuffer` hands out such views): no copy then."""
+        base = prop._base
+        if (base is not None and base is enc_obs._base and base.is_contiguous() and base.shape[:-1] == prop.shape[:-1]
+                and base.shape[-1] == prop.shape[-1] + enc_obs.shape[-1] and prop.stride() == base.stride() and enc_obs.stride() == base.stride()
+                and prop.data_ptr() == base.data_ptr() and enc_obs.data_ptr() == base.data_ptr() + prop.shape[-1] * base.element_size()):
+            return base
+        return torch.cat((prop, enc_obs), dim=-1)
+
+    def _fused_step(self, batch):
+        """`_eager_step` with the loss and its statistics from `bc_loss` and the update from `FlatAdamW` (same arithmetic: `batch_loss`)."""
+        from .bc_loss import bc_loss
+
+        prop, enc_obs, tac, masks = batch["proprioceptions"], batch["teacher_encoder_obses"], batch["tactile_signals"], batch["masks"]
+        opt = self._flat_adamw
+        opt.zero_grad()
+        clip = self.clip_range if self.clip_actions else 0.0
+        with torch.no_grad():
+            teacher_actions = self.teacher_policy_inference(self._teacher_obs(prop, enc_obs))
+        if self.MonolithicDistillation:
+            loss, mse, mae = bc_loss(self.forward(prop, tac), teacher_actions, masks, clip_range=clip, action_scale=self.action_scale_within_env)
+        else:
+            emb = self.encoder_forward(tac)
+            with torch.no_grad():
+                target = self.teacher_encoder_inference(enc_obs) if self.teacher_encoder_inference is not None else enc_obs
+                student_actions = self.backbone_forward(prop, emb)
+            loss, mse, mae = bc_loss(emb, target, masks, student_actions, teacher_actions, clip_range=clip,
+                                     action_scale=self.action_scale_within_env)
+        loss.backward()
+        opt.step()
+        return loss.detach(), mse, mae
+
     def training_step(self, batch):
         """One optimizer step on a padded batch; (loss, action_mse | None, action_mae) as device scalars.
         (A hipGraph replay of this step was tried: +6 %, and capture of the ~3 k-launch step segfaulted in `capture_end` on
         this stack once the GRU's HIP time loop was inside - removed.)"""
-        return self._eager_step(batch)
+        return self._eager_step(batch) if self._flat_adamw is None else self._fused_step(batch)
 
     def num_epoches(self, num_iter: int) -> int:
         n = self.initial_epoches + self.incremental_epoches * num_iter

@@ -41,6 +41,9 @@ def main() -> None:
                     help="keep the trajectory bookkeeping of collection / evaluation on the device (lt_ledger_step behind each env step)")
     ap.add_argument("--fused_cnn_train", action="store_true",
                     help="train the student's tactile CNN head through the HIP kernels of lt_cnn_train.h (lt_cnn_forward, lt_cnn_backward)")
+    ap.add_argument("--fused_bc_step", action="store_true",
+                    help="assemble batches, compute the masked BC loss and step AdamW through the HIP kernels of lt_bc.h (lt_bc_gather, "
+                         "lt_bc_loss_forward / _backward, lt_adamw_step)")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -88,7 +91,7 @@ def _run(args, cfg, agent, env, distill_root) -> None:
                          teacher_encoder=None if mono else runner.get_inference_encoder(device=args.device),
                          teacher_backbone_weights=None if mono else runner.get_backbone_weights(), training=True,
                          fused_student_inference=args.fused_student, fused_collection=args.fused_collect, device_ledger=args.device_ledger,
-                         fused_cnn_training=args.fused_cnn_train)
+                         fused_cnn_training=args.fused_cnn_train, fused_bc_step=args.fused_bc_step)
         d.train()
     else:
         ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or ".*", args.checkpoint_distill or "model_.*.pt")
