@@ -696,6 +696,9 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_n
 /* ---- the two ends of the student's behaviour-cloning step (batch assembly, the masked loss and its statistics, the AdamW update):
  * lt_bc_*, lt_adamw_step - declared in a header of their own, part of this ABI. */
 #include "lt_bc.h"
+/* ---- the LSTM recurrence of `Memory` / `PolicyMemory` over whole trajectories (the LSTM counterpart of lt_gru_*): lt_lstm_* - declared
+ * in a header of their own, part of this ABI. */
+#include "lt_lstm.h"
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from . import lstm as _lstm
 from .gru import gru_sequence
 from .linear import Linear
 
@@ -64,6 +65,9 @@ class Memory(nn.Module):
             if input.is_cuda and isinstance(self.rnn, nn.GRU) and self.rnn.num_layers == 1 and not self.use_miopen_sequence:
                 out, _ = gru_sequence(self.rnn, input, hidden_states)  # rl/gru.py: ~15x MIOpen's RNN path at L ~ 500, B ~ 47
                 return out
+            if not self.use_miopen_sequence and _lstm.serves(self.rnn, input):
+                out, _ = _lstm.lstm_sequence(self.rnn, input, hidden_states)  # rl/lstm.py: the recurrence in csrc/lt_lstm.hip
+                return out
             out, _ = self.rnn(input, hidden_states)
             return out
         if isinstance(self.rnn, nn.GRU) and self.rnn.num_layers == 1:
@@ -73,6 +77,10 @@ class Memory(nn.Module):
             h = torch.gru_cell(input, h, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
             self.hidden_states = h.unsqueeze(0)
             return h
+        if _lstm.serves(self.rnn, input):
+            # one env step: a length-1 sequence of the same kernels, (h, c) carried as the tuple `reset()` handles
+            out, self.hidden_states = _lstm.lstm_sequence(self.rnn, input.unsqueeze(0), self.hidden_states)
+            return out.squeeze(0)
         out, self.hidden_states = self.rnn(input.unsqueeze(0), self.hidden_states)
         return out.squeeze(0)
 

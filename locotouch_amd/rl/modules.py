@@ -115,13 +115,20 @@ class PolicyMemory(nn.Module):
         self.hidden_states = None
 
     def forward(self, input, masks=None, hidden_states=None):
+        from . import lstm as _lstm
         from .trajectories import unpad_trajectories
 
         if masks is not None:
             if hidden_states is None:
                 raise ValueError("Hidden states not passed to memory module during policy update")
+            if _lstm.serves(self.rnn, input):
+                out, _ = _lstm.lstm_sequence(self.rnn, input, hidden_states)  # rl/lstm.py: the recurrence in csrc/lt_lstm.hip
+                return unpad_trajectories(out, masks)
             out, _ = self.rnn(input, hidden_states)
             return unpad_trajectories(out, masks)
+        if _lstm.serves(self.rnn, input):
+            out, self.hidden_states = _lstm.lstm_sequence(self.rnn, input.unsqueeze(0), self.hidden_states)
+            return out
         out, self.hidden_states = self.rnn(input.unsqueeze(0), self.hidden_states)
         return out
 
