@@ -699,6 +699,9 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_n
 /* ---- the LSTM recurrence of `Memory` / `PolicyMemory` over whole trajectories (the LSTM counterpart of lt_gru_*): lt_lstm_* - declared
  * in a header of their own, part of this ABI. */
 #include "lt_lstm.h"
+/* ---- one rollout step of the two LSTM memories of a recurrent policy in one launch: lt_memory_* - declared in a header of their own,
+ * part of this ABI. */
+#include "lt_memory.h"
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ LEDGER_HEADER = os.path.join(REPO, "include", "lt_ledger.h")  # included by lt_e
 CNN_TRAIN_HEADER = os.path.join(REPO, "include", "lt_cnn_train.h")  # the training form of the student's tactile CNN head
 BC_HEADER = os.path.join(REPO, "include", "lt_bc.h")  # included by lt_env.h: batch assembly, masked loss and AdamW of the student's BC step
 LSTM_HEADER = os.path.join(REPO, "include", "lt_lstm.h")  # included by lt_env.h: the LSTM recurrence over whole trajectories
+MEMORY_HEADER = os.path.join(REPO, "include", "lt_memory.h")  # included by lt_env.h: one rollout step of a recurrent policy's two LSTM memories
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -188,6 +189,14 @@ if (any(r is not ctypes.c_int for r, _ in LSTM_SIGNATURES.values())
                                    | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES))):
     raise ImportError("include/lt_lstm.h: every entry point returns a status and none repeats one of another header")
 
+# include/lt_memory.h: a structure of its own (one memory's operands); all status-returning, launched through `call`
+_, _memory_structs, MEMORY_SIGNATURES = parse_header(open(MEMORY_HEADER).read())
+LtMemoryNet = _memory_structs["lt_memory_net"]
+if (any(r is not ctypes.c_int for r, _ in MEMORY_SIGNATURES.values())
+        or set(MEMORY_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
+                                     | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES))):
+    raise ImportError("include/lt_memory.h: every entry point returns a status and none repeats one of another header")
+
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
@@ -202,7 +211,7 @@ def load() -> ctypes.CDLL:
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES, **LEDGER_SIGNATURES,
-                                      **CNN_TRAIN_SIGNATURES, **BC_SIGNATURES, **LSTM_SIGNATURES}.items():
+                                      **CNN_TRAIN_SIGNATURES, **BC_SIGNATURES, **LSTM_SIGNATURES, **MEMORY_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
         if name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES and name not in CNN_TRAIN_VALUE_QUERIES:

@@ -20,6 +20,13 @@ Observation normalisation (the runner's `empirical_normalization`, rl/normalizer
     scratch buffers - two launches, one in evaluation mode]
 still on the one stream.  The storage slots stay RAW during the rollout (the step kernel shifts its observation history from slot t
 to slot t + 1), `normalize_storage()` rewrites them in place through the per-slot snapshots before the update reads them.
+
+Recurrent policies (`ActorCriticRecurrent` with single-layer LSTM memories; the runner's `fused_recurrent_rollout`): a step is
+    [lt_memory_step: both memories - reset mask of the previous step's dones, the pre-step state into the storage's
+     `saved_hidden_states` slot t, the LSTM cell on the observation rows of slot t, new raw (h, c) into a ping-pong buffer]
+ -> [policy + value on the two h buffers] -> [env step]
+and one `lt_memory_finish` launch behind the last step leaves where(dones[T-1], 0, state) in the modules' `hidden_states`
+(csrc/lt_memory.hip; DESIGN.md 4 "Recurrent rollout step").
 """
 from __future__ import annotations
 
@@ -27,6 +34,34 @@ from __future__ import annotations
 import torch
 
 from .. import _abi
+
+MEMORY_MIN_HIDDEN, MEMORY_MAX_HIDDEN, MEMORY_MAX_K = 64, 512, 1248  # include/lt_memory.h
+
+
+def recurrent_unsupported(ac, storage) -> str | None:
+    """Why the fused rollout does not serve this recurrent policy (None: it does): include/lt_memory.h covers two single-layer f32 LSTM
+    memories with biases of one hidden size, a multiple of 64 in [64, 512], on f32 observation rows."""
+    mems = (getattr(ac, "memory_a", None), getattr(ac, "memory_c", None))
+    if any(m is None for m in mems):
+        return "the policy has no memory_a / memory_c"
+    for name, m in zip(("memory_a", "memory_c"), mems):
+        rnn = m.rnn
+        if not isinstance(rnn, torch.nn.LSTM):
+            return f"{name} is a {type(rnn).__name__}: only LSTM memories are served"
+        if rnn.num_layers != 1 or rnn.bidirectional or rnn.batch_first or not rnn.bias or rnn.proj_size != 0:
+            return f"{name} must be a single-layer, unidirectional, time-major LSTM with biases and without projection"
+        h = rnn.hidden_size
+        if h % 64 or not MEMORY_MIN_HIDDEN <= h <= MEMORY_MAX_HIDDEN:
+            return f"{name}: hidden size {h} is not a multiple of 64 in [{MEMORY_MIN_HIDDEN}, {MEMORY_MAX_HIDDEN}]"
+        if rnn.input_size + h > MEMORY_MAX_K:
+            return f"{name}: input size + hidden size exceeds {MEMORY_MAX_K}"
+        if rnn.weight_ih_l0.dtype != torch.float32:
+            return f"{name} is not f32"
+    if mems[0].rnn.hidden_size != mems[1].rnn.hidden_size:
+        return "the two memories differ in hidden size"
+    if storage.observations.dtype != torch.float32:
+        return "bf16 observation rows: the memory step reads f32 rows"
+    return None
 
 
 def normalize_rows(normalizer, rows: torch.Tensor, out: torch.Tensor | None = None, snapshot: torch.Tensor | None = None) -> torch.Tensor:
@@ -66,6 +101,16 @@ class FusedRollout:
         ac = alg.actor_critic
         if getattr(ac, "noise_std_type", "scalar") != "scalar":
             raise ValueError("FusedRollout supports the 'scalar' noise_std_type of the LocoTouch agent configs")
+        # recurrent policy: the two LSTM memories run in one launch in front of the MLPs (csrc/lt_memory.hip)
+        self.recurrent = bool(getattr(ac, "is_recurrent", False))
+        if not self.recurrent and type(ac).__name__ == "ActorCriticEncoder":
+            raise ValueError("FusedRollout does not serve ActorCriticEncoder: its encoders are not part of the fused step")
+        if self.recurrent:
+            why = recurrent_unsupported(ac, alg.storage)
+            if why is None and obs_normalizer is not None:
+                why = "observation normalisers are not served together with a recurrent policy"
+            if why is not None:
+                raise ValueError(f"FusedRollout does not serve this recurrent policy: {why}")
         self.env, self.alg = env, alg
         self.device = env.device
         self.actions = torch.zeros(env.num_envs, 12, device=self.device)
@@ -106,6 +151,69 @@ class FusedRollout:
                 raise ValueError("observation normalisers and bf16 observation rows are not served together: the normaliser kernels read "
                                  "and write f32 rows")
             self._init_normalizers(obs_normalizer, critic_obs_normalizer)
+
+        if self.recurrent:
+            self._init_memory()
+
+    def _init_memory(self) -> None:
+        """Ping-pong buffers of the raw (h, c) of both memories, and the storage's `saved_hidden_states` slots."""
+        st, ac, n = self.alg.storage, self.alg.actor_critic, self.env.num_envs
+        hid = ac.memory_a.rnn.hidden_size
+        steps = st.observations.shape[0]
+        rows = n + (-n) % 64  # (the MLP launch reads whole row tiles)
+        # _hc[parity][network] = (h, c): step t reads parity (t - 1) & 1 - at t = 0 the modules' own state - and writes parity t & 1
+        self._hc = [[tuple(torch.zeros(rows, hid, device=self.device) for _ in range(2)) for _ in range(2)] for _ in range(2)]
+        for name in ("saved_hidden_states_a", "saved_hidden_states_c"):
+            saved = getattr(st, name)
+            if saved is None:
+                setattr(st, name, [torch.zeros(steps, 1, n, hid, device=self.device) for _ in range(2)])
+            elif len(saved) != 2 or any(s.shape != (steps, 1, n, hid) or s.dtype != torch.float32 or not s.is_contiguous() for s in saved):
+                raise ValueError(f"storage.{name} must be [h, c] of contiguous f32 ({steps}, 1, {n}, {hid}) tensors")
+        self._state = None  # the modules' (h, c) tensors of both memories, adopted by begin() / rollout()
+
+    def _adopt_state(self) -> None:
+        """The modules' `hidden_states` become the rollout's state tensors (zeros when a memory has none yet): step 0 reads them,
+        `lt_memory_finish` writes them."""
+        ac, n = self.alg.actor_critic, self.env.num_envs
+        state = []
+        for name, mem in (("memory_a", ac.memory_a), ("memory_c", ac.memory_c)):
+            hid = mem.rnn.hidden_size
+            if mem.hidden_states is None:
+                mem.hidden_states = (torch.zeros(1, n, hid, device=self.device), torch.zeros(1, n, hid, device=self.device))
+            hc = mem.hidden_states
+            if (not isinstance(hc, tuple) or len(hc) != 2
+                    or any(not torch.is_tensor(x) or x.shape != (1, n, hid) or x.dtype != torch.float32 or x.device != self._hc[0][0][0].device
+                           for x in hc)):
+                raise ValueError(f"{name}.hidden_states must be (h, c) of f32 [1, {n}, {hid}] tensors on {self.device}")
+            if not all(x.is_contiguous() for x in hc):
+                mem.hidden_states = hc = tuple(x.contiguous() for x in hc)
+            state.append(hc)
+        self._state = state
+
+    def _memory_step(self, t: int, obs, cobs) -> None:
+        """Step t of both memories in one launch; the h buffers of parity t & 1 are then the input rows of the MLPs."""
+        ac, st = self.alg.actor_critic, self.alg.storage
+        src = self._state if t == 0 else self._hc[(t - 1) & 1]
+        dst = self._hc[t & 1]
+        nets = []
+        for k, (mem, x, saved) in enumerate(((ac.memory_a, obs, st.saved_hidden_states_a), (ac.memory_c, cobs, st.saved_hidden_states_c))):
+            rnn = mem.rnn
+            nets.append(_abi.LtMemoryNet(x.data_ptr(), x.shape[1], rnn.weight_ih_l0.data_ptr(), rnn.weight_hh_l0.data_ptr(),
+                                         rnn.bias_ih_l0.data_ptr(), rnn.bias_hh_l0.data_ptr(), src[k][0].data_ptr(), src[k][1].data_ptr(),
+                                         dst[k][0].data_ptr(), dst[k][1].data_ptr(), saved[0][t].data_ptr(), saved[1][t].data_ptr()))
+        _abi.call("lt_memory_step", nets[0], nets[1], st.dones[t - 1] if t > 0 else None, self.env.num_envs, ac.memory_a.rnn.hidden_size,
+                  _abi.stream(self.device))
+
+    def _memory_rows(self, t: int):
+        """The rows the MLPs of step t read: the new h of both memories."""
+        n = self.env.num_envs
+        return self._hc[t & 1][0][0][:n], self._hc[t & 1][1][0][:n]
+
+    def _memory_finish(self, num_steps: int) -> None:
+        raw, st = self._hc[(num_steps - 1) & 1], self.alg.storage
+        (ha, ca), (hc, cc) = self._state
+        _abi.call("lt_memory_finish", raw[0][0], raw[0][1], raw[1][0], raw[1][1], st.dones[num_steps - 1], self.env.num_envs,
+                  self.alg.actor_critic.memory_a.rnn.hidden_size, ha, ca, hc, cc, _abi.stream(self.device))
 
     def _init_normalizers(self, actor_norm, critic_norm) -> None:
         env, st = self.env, self.alg.storage
@@ -155,6 +263,8 @@ class FusedRollout:
         """The start of a `learn()` call: the env's current rows are merged once and normalised (the runner's eager loop does the same
         before its first step).  Later rollouts carry the rows and the snapshot behind their last step over; rollout() calls this
         itself when nobody has - call it yourself before capturing a rollout into a graph, or the replays merge these rows again."""
+        if self.recurrent:
+            self._adopt_state()
         if self.normalizers is not None:
             with torch.inference_mode():
                 self._normalize(self.env.obs_policy, self.env.obs_critic, self._carry)
@@ -202,6 +312,8 @@ class FusedRollout:
     def launches_per_step(self) -> int:
         """Kernel launches of one rollout step (the reference-shaped eager loop needs ~30)."""
         base = 2 if self.actor_mlp is not None else 11  # policy + value, env step (the population pass rides in the next step's launch)
+        if self.recurrent:
+            return base + 1  # both memories: one launch in front of the MLPs
         if self.normalizers is None:
             return base
         return base + (2 if self.normalizers[0].training else 1)  # column statistics, merge + snapshot + normalise
@@ -227,7 +339,10 @@ class FusedRollout:
         if not self.rows_in_storage:
             st.observations[t].copy_(obs)
             st.privileged_observations[t].copy_(cobs)
-        if self.normalizers is None:
+        if self.recurrent:
+            self._memory_step(t, obs, cobs)
+            self._policy_value(t, *self._memory_rows(t))
+        elif self.normalizers is None:
             self._policy_value(t, obs, cobs)
         else:
             self._policy_value(t, *self.norm_rows)
@@ -256,6 +371,9 @@ class FusedRollout:
         n = env.num_envs
         obs, cobs, nxt_p, nxt_c = self._rows(t, last)
         seen, cseen = (obs, cobs) if self.normalizers is None else self.norm_rows  # what the networks read
+        if self.recurrent:
+            self._memory_step(t, obs, cobs)
+            seen, cseen = self._memory_rows(t)
         mu = ac.actor(seen)
         rows = (None, None, None, None) if self.rows_in_storage else (obs, cobs, st.observations[t], st.privileged_observations[t])
         _abi.call("lt_rollout_act", n, env.num_obs, self._noise_seed, self._act_counter, mu, ac.std.data, None, *rows,
@@ -276,6 +394,10 @@ class FusedRollout:
         env, st = self.env, self.alg.storage
         if self.normalizers is not None and not self._primed:
             self.begin()
+        if self.recurrent:
+            # the tensors the modules hold NOW: `compute_returns` advances the critic memory by one evaluate, which rebinds its state
+            # (a captured rollout keeps the addresses it was captured with: replay it only while the modules keep those tensors)
+            self._adopt_state()
         st.clear()
         main = torch.cuda.current_stream(self.device)
         with torch.inference_mode():
@@ -298,6 +420,8 @@ class FusedRollout:
             try:
                 for t in range(num_steps):
                     self.step(t, last=t == num_steps - 1)
+                if self.recurrent:
+                    self._memory_finish(num_steps)
             finally:
                 if chain:
                     env.gate_update()

@@ -17,7 +17,7 @@ from collections import deque
 import torch
 
 from .dist import Dist
-from .modules import ActorCritic
+from .modules import ActorCritic, ActorCriticRecurrent
 from .normalizer import EmpiricalNormalization
 from .ppo import PPO
 
@@ -159,7 +159,9 @@ class OnPolicyRunner:
                 self.writer.flush()
 
     def _make_fused(self):
-        """FusedRollout when the env is the HIP env on a GPU and the policy is the plain feed-forward ActorCritic."""
+        """FusedRollout when the env is the HIP env on a GPU and the policy is the plain feed-forward ActorCritic, or - behind the cfg
+        key `fused_recurrent_rollout` (default False: the fused path draws its exploration noise from the kernels' Philox stream, which
+        would change existing runs) - an ActorCriticRecurrent whose memories csrc/lt_memory.hip serves."""
         try:
             from ..env import LocoTouchVecEnv
             from .fused import FusedRollout
@@ -170,8 +172,19 @@ class OnPolicyRunner:
             target = getattr(self.env, "fused_target", lambda: None)()
         if not isinstance(target, LocoTouchVecEnv) or self.cfg.get("fused_rollout", True) is False:
             return None
-        if getattr(self.alg.actor_critic, "noise_std_type", "scalar") != "scalar" or type(self.alg.actor_critic) is not ActorCritic:
-            return None  # the fused rollout packs the plain feed-forward actor / critic MLPs
+        ac = self.alg.actor_critic
+        if getattr(ac, "noise_std_type", "scalar") != "scalar":
+            return None
+        if type(ac) is ActorCriticRecurrent:
+            from .fused import recurrent_unsupported
+
+            # single-layer f32 LSTM memories alone, without the normaliser (it would have to feed the memory step, not the MLPs)
+            if (not self.cfg.get("fused_recurrent_rollout", False) or self.empirical_normalization
+                    or recurrent_unsupported(ac, self.alg.storage) is not None):
+                return None
+            return FusedRollout(target, self.alg)
+        if type(ac) is not ActorCritic:
+            return None  # the fused rollout packs the actor / critic MLPs (ActorCriticEncoder keeps the eager loop)
         if not self.empirical_normalization:
             return FusedRollout(target, self.alg)
         # The device normaliser (csrc/lt_obs_norm.hip) reads and writes f32 rows, and it keeps per-process statistics: ranks cannot

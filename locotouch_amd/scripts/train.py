@@ -47,6 +47,9 @@ def main() -> None:
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--logger", default="tensorboard")
     ap.add_argument("--log_root", default="logs/rsl_rl")
+    ap.add_argument("--fused_recurrent_rollout", action="store_true",
+                    help="recurrent (LSTM) policies: collect on the fused rollout path (rl/fused.py); exploration noise then comes from "
+                         "the kernels' Philox stream instead of torch's generator")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -63,6 +66,8 @@ def main() -> None:
         cfg["seed"] = args.seed
     if args.max_iterations is not None:
         cfg["max_iterations"] = args.max_iterations
+    if args.fused_recurrent_rollout:
+        cfg["fused_recurrent_rollout"] = True
     device = f"cuda:{dist.local_rank}"
     torch.cuda.set_device(device)
     torch.manual_seed(cfg["seed"])
