@@ -31,6 +31,12 @@ class PPO:
         self.fused_loss = on_gpu and bool(unused.get("fused_loss", True))  # csrc/lt_ppo.hip: the loss chain and its backward in one launch
         self.packed_forward = on_gpu and bool(unused.get("packed_forward", True))  # csrc/lt_mlp.hip: both networks' training forward in one launch
         self.direct_update = on_gpu and bool(unused.get("direct_update", True))  # no autograd graph, no host read between minibatch steps (_direct_update)
+        # opt-in: recurrent (LSTM) policies update on whole rollouts of env blocks, without padding (_recurrent_update, rl/memory_seq.py)
+        self.fused_recurrent_update = bool(unused.get("fused_recurrent_update", False))
+        if self.fused_recurrent_update:
+            why = self._recurrent_update_unsupported()
+            if why is not None:
+                raise ValueError(f"fused_recurrent_update: {why}")
         self._pair = None
         if on_gpu and bool(unused.get("tuned_gemms", True)):
             from . import tuned_gemms
@@ -299,7 +305,93 @@ class PPO:
             group["lr"] = self.learning_rate
 
     def update(self):
+        if self.fused_recurrent_update:
+            return self._recurrent_update()
         return self._eager_update()
+
+    def _recurrent_update_unsupported(self) -> str | None:
+        """Why `_recurrent_update` does not serve this policy / storage (None: it does)."""
+        from .memory_seq import unsupported
+        from .modules import ActorCriticRecurrent
+
+        ac = self.actor_critic
+        if type(ac) is not ActorCriticRecurrent:
+            return f"the policy is a {type(ac).__name__}: only a plain ActorCriticRecurrent is served"
+        st = getattr(self, "storage", None)  # (None at construction: the observation rows' dtype is checked at the first update)
+        return unsupported(ac.memory_a, ac.memory_c, *((None, None) if st is None else (st.observations, st.privileged_observations)))
+
+    def _recurrent_update(self):
+        """The update of an `ActorCriticRecurrent` with LSTM memories on WHOLE ROLLOUTS of env blocks (rl/memory_seq.py: why this equals
+        the padded trajectories of `_eager_update`): no `split_and_pad_trajectories`, no `recurrent_mini_batches`, no boolean indexing.
+        Per optimizer step: the env block [e0, e1) of the reference's dealing (per = N // num_mini_batches, leftover envs dropped), both
+        memories over its T steps from the states saved at step 0 (`memory_rollout_sequence`; on the GPU csrc/lt_memory.hip), the two
+        MLPs on the [T, per, H] outputs, the loss (one launch, csrc/lt_ppo.hip, where its conditions hold; else the op chain of
+        `_eager_update`), the learning-rate rule, backward, clip + Adam.  The statistics stay on the device until the last step."""
+        why = self._recurrent_update_unsupported()
+        if why is not None:
+            raise ValueError(f"fused_recurrent_update: {why}")
+        from .memory_seq import memory_rollout_sequence
+
+        ac, st = self.actor_critic, self.storage
+        if st.saved_hidden_states_a is None or st.saved_hidden_states_c is None:
+            raise ValueError("fused_recurrent_update: the storage holds no saved hidden states (no rollout of a recurrent policy filled it)")
+        T, N = st.num_steps, st.num_envs
+        per = N // self.num_mini_batches
+        dones = st.dones.view(T, N)  # uint8 [T, N]
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        fused = (self.fused_loss and st.observations.is_cuda and getattr(ac, "noise_std_type", "scalar") == "scalar" and st.actions.shape[-1] <= 16)
+        if fused:
+            from .fused_loss import fused_ppo_loss
+        # the env blocks are the same in every epoch: their observation rows are laid out contiguously ONCE per update (what the weight
+        # gradient dW_ih = dgates^T X multiplies); everything else of a block is a view of the storage
+        blocks = []
+        for i in range(self.num_mini_batches):
+            sl = (slice(None), slice(i * per, (i + 1) * per))
+            blocks.append((sl, st.observations[sl].contiguous(), st.privileged_observations[sl].contiguous()))
+        stats = torch.zeros(3, device=st.observations.device, dtype=st.values.dtype)
+        for _ in range(self.num_learning_epochs):
+            for sl, obs, cobs in blocks:
+                hc_a = tuple(h[0][sl] for h in st.saved_hidden_states_a)
+                hc_c = tuple(h[0][sl] for h in st.saved_hidden_states_c)
+                out_a, out_c = memory_rollout_sequence(ac.memory_a, ac.memory_c, obs, cobs, dones[sl], hc_a, hc_c)
+                adv = st.advantages[sl]
+                if self.normalize_advantage_per_mini_batch:
+                    with torch.no_grad():
+                        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+                old_mu, old_sigma, old_values, returns = st.mu[sl], st.sigma[sl], st.values[sl], st.returns[sl]
+                if fused:
+                    f = lambda t: t.reshape(T * per, -1)  # noqa: E731  (row t * per + e, the order of the memories' outputs)
+                    loss, surrogate_loss, value_loss, ent, kl_mean = fused_ppo_loss(
+                        ac.actor(out_a.view(T * per, -1)), ac.std, ac.critic(out_c.view(T * per, -1)), f(st.actions[sl]),
+                        f(st.actions_log_prob[sl]), f(adv), f(returns), f(old_values), f(old_mu), f(old_sigma), self.clip_param,
+                        self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
+                    if adaptive:
+                        self._apply_kl(kl_mean)
+                    ent = ent.detach()
+                else:
+                    ac.update_distribution(out_a)
+                    log_prob = ac.get_actions_log_prob(st.actions[sl])
+                    value = ac.critic(out_c)
+                    mu, sigma, ent = ac.action_mean, ac.action_std, ac.entropy.mean()
+                    if adaptive:
+                        self._adapt_learning_rate(mu, sigma, old_mu, old_sigma)
+                    ratio = torch.exp(log_prob - torch.squeeze(st.actions_log_prob[sl]))
+                    a = torch.squeeze(adv)
+                    surrogate_loss = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
+                    if self.use_clipped_value_loss:
+                        clipped = old_values + (value - old_values).clamp(-self.clip_param, self.clip_param)
+                        value_loss = torch.max((value - returns).pow(2), (clipped - returns).pow(2)).mean()
+                    else:
+                        value_loss = (returns - value).pow(2).mean()
+                    loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * ent
+                self._zero_grad()
+                loss.backward()
+                self._optim_step()
+                stats = stats + torch.stack((value_loss.detach(), surrogate_loss.detach(), ent.detach())).to(stats.dtype)
+        n = self.num_learning_epochs * self.num_mini_batches
+        sv, ss, se = (stats / n).tolist()  # the statistics' only host read
+        st.clear()
+        return sv, ss, se, None, None
 
     def _eager_update(self):
         ac = self.actor_critic

@@ -38,6 +38,8 @@ class OnPolicyRunner:
             raise NotImplementedError(f"policy class {cls_name!r} is not implemented (ActorCritic, ActorCriticRecurrent, ActorCriticEncoder are)")
         self.alg_cfg.pop("class_name", None)
         ac = getattr(_m, cls_name)(num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
+        if "fused_recurrent_update" in self.cfg:  # opt-in (rl/ppo.py `_recurrent_update`); a refusal is PPO's ValueError
+            self.alg_cfg["fused_recurrent_update"] = bool(self.cfg["fused_recurrent_update"])
         self.alg = PPO(ac, device=device, dist=self.dist, **self.alg_cfg)
         self.num_steps_per_env = int(self.cfg["num_steps_per_env"])
         self.save_interval = int(self.cfg.get("save_interval", 50))

@@ -50,6 +50,8 @@ def main() -> None:
     ap.add_argument("--fused_recurrent_rollout", action="store_true",
                     help="recurrent (LSTM) policies: collect on the fused rollout path (rl/fused.py); exploration noise then comes from "
                          "the kernels' Philox stream instead of torch's generator")
+    ap.add_argument("--fused_recurrent_update", action="store_true",
+                    help="recurrent (LSTM) policies: update on whole rollouts of env blocks, without padding (rl/ppo.py `_recurrent_update`)")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -68,6 +70,8 @@ def main() -> None:
         cfg["max_iterations"] = args.max_iterations
     if args.fused_recurrent_rollout:
         cfg["fused_recurrent_rollout"] = True
+    if args.fused_recurrent_update:
+        cfg["fused_recurrent_update"] = True
     device = f"cuda:{dist.local_rank}"
     torch.cuda.set_device(device)
     torch.manual_seed(cfg["seed"])

@@ -1,0 +1,151 @@
+"""What the PPO update of a recurrent (LSTM) policy costs with `fused_recurrent_update` off and on: writes profiles/recurrent_update_<n>.json.
+
+Teacher task, `--envs` envs (4096), `ActorCriticRecurrent` with LSTM memories of H = 256, 24 steps per rollout, the recurrent runner cfg
+(the fused rollout in both legs, so that the legs differ in the update alone); one fresh process per leg, `--warmup` (3) iterations, then
+the median of `--rounds` (7) with [min, max]:
+  update_ms     `Perf/learning_time` of `runner.learn` (host wall clock of `alg.update()`, which ends in a host read)
+  iteration_ms  collection + learning time
+The tool uses the public runner / PPO interface alone, and a tree without the switch ignores the cfg key: THE BASELINE LEG IS THE PARENT
+COMMIT - run `--mode off` in a checkout of the parent and hand its RESULT line to `--off-result`; without it the off leg runs on this
+tree with the switch off (the same code path, `_eager_update`), and the file says which tree each leg ran on.
+The two new kernels' per-launch time comes from a `rocprofv3 --kernel-trace --stats` run of its own (`--mode trace` under the profiler,
+no counters in it).  A gain is claimed only where the legs' [min, max] intervals do not overlap.
+
+    python tools/recurrent_update_bench.py [--envs 4096] [--rounds 7] [--off-result FILE] [--out profiles/recurrent_update_4096.json]
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import glob
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+TASK = "Isaac-RandCylinderTransportTeacher-LocoTouch-v1"
+HIDDEN = 256
+KERNELS = ("lt_memory_step_kernel", "lt_memory_seq_bwd_kernel", "lt_memory_seq_bwd_open_kernel")
+
+
+def stats(xs: list[float]) -> dict:
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "rounds": len(xs)}
+
+
+def tree() -> str | None:
+    try:
+        return subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip() or None
+    except OSError:
+        return None
+
+
+def make_runner(envs: int, on: bool):
+    from locotouch_amd.agents import train_cfg
+    from locotouch_amd.env import make
+    from locotouch_amd.rl import OnPolicyRunner
+
+    cfg = dict(train_cfg(TASK), fused_recurrent_rollout=True, fused_recurrent_update=on)
+    cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=HIDDEN, rnn_num_layers=1)
+    return OnPolicyRunner(make(TASK, num_envs=envs, device="cuda:0", seed=1), cfg, log_dir=None, device="cuda:0")
+
+
+def measure(mode: str, envs: int, rounds: int, warmup: int) -> dict:
+    runner = make_runner(envs, mode != "off")
+    alg = runner.alg
+    out = {"mode": mode, "tree": tree(), "switch": bool(getattr(alg, "fused_recurrent_update", False)), "steps": runner.num_steps_per_env,
+           "num_mini_batches": alg.num_mini_batches, "num_learning_epochs": alg.num_learning_epochs}
+    if mode == "trace":
+        runner.learn(2)
+        return out
+    runner.learn(warmup + rounds)
+    recs = runner.history[warmup:]
+    out["update_ms"] = stats([1e3 * r["Perf/learning_time"] for r in recs])
+    out["iteration_ms"] = stats([1e3 * (r["Perf/collection time"] + r["Perf/learning_time"]) for r in recs])
+    return out
+
+
+def kernel_trace(envs: int) -> dict:
+    """Per-launch time of the sequence kernels: a `rocprofv3 --kernel-trace --stats` run of two iterations, nothing else traced."""
+    exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    if not os.path.exists(exe):
+        return {"error": "rocprofv3 not found"}
+    tmp = tempfile.mkdtemp(prefix="recurrent_update_trace_")
+    try:
+        p = subprocess.run([exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "trace", "--", sys.executable,
+                            os.path.abspath(__file__), "--mode", "trace", "--envs", str(envs)], capture_output=True, text=True, timeout=600)
+        if p.returncode != 0:
+            return {"error": f"rocprofv3 exit {p.returncode}: {p.stderr[-500:]}"}
+        rows = {}
+        for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
+            for row in csv.DictReader(open(path)):
+                if any(k in row.get("Name", "") for k in KERNELS):
+                    rows[row["Name"]] = {"calls": int(row["Calls"]), "average_us": float(row["AverageNs"]) / 1e3,
+                                         "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
+        return rows or {"error": "no sequence-kernel row in the kernel statistics"}
+    except (OSError, subprocess.TimeoutExpired, KeyError, ValueError) as exc:
+        return {"error": f"{type(exc).__name__}: {exc}"}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--commit", help="what to record as measured_on_commit (default: git rev-parse --short HEAD, null outside a checkout)")
+    ap.add_argument("--off-result", help="file holding the RESULT line of `--mode off` run in a checkout of the parent commit")
+    ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
+    ap.add_argument("--mode", choices=["off", "on", "trace"], help="(internal) measure one leg and print it")
+    args = ap.parse_args()
+    if args.rounds < 5:
+        sys.exit("--rounds must be at least 5")
+    if args.mode:
+        print("RESULT " + json.dumps(measure(args.mode, args.envs, args.rounds, args.warmup)))
+        return
+    legs = {}
+    if args.off_result:
+        line = [l for l in open(args.off_result).read().splitlines() if l.startswith("RESULT ")]
+        if not line:
+            sys.exit(f"{args.off_result}: no RESULT line")
+        legs["off"] = json.loads(line[-1][7:])
+    for mode in ("off", "on"):  # a fresh process each: no allocator state carried from one to the next
+        if mode in legs:
+            continue
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--envs", str(args.envs), "--rounds", str(args.rounds),
+                            "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=900)
+        line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            sys.exit(f"{mode}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+        legs[mode] = json.loads(line[-1][7:])
+    if legs["off"]["switch"] or not legs["on"]["switch"]:
+        sys.exit("the off leg ran with the switch on, or the on leg without it")
+
+    def faster(key):  # on is faster by MORE than the spread of either leg: the intervals [min, max] do not even touch
+        return legs["on"][key]["max"] < legs["off"][key]["min"]
+
+    res = {"task": TASK, "envs": args.envs, "hidden": HIDDEN, "measured_on_commit": args.commit or tree(),
+           "notes": {"off": "the parent commit's tree where `tree` differs from the on leg's; else this tree with the switch off",
+                     "update_ms": "runner wall clock of alg.update() (it ends in a host read)",
+                     "iteration_ms": "runner wall clock, collection + learning",
+                     "spread": "min and max over the rounds, beside the median"},
+           **legs, "kernels": None if args.no_trace else kernel_trace(args.envs),
+           "off_over_on_update": legs["off"]["update_ms"]["median"] / legs["on"]["update_ms"]["median"],
+           "off_over_on_iteration": legs["off"]["iteration_ms"]["median"] / legs["on"]["iteration_ms"]["median"],
+           "on_faster_than_the_spread": {"update": faster("update_ms"), "iteration": faster("iteration_ms")}}
+    out = args.out or os.path.join(REPO, "profiles", f"recurrent_update_{args.envs}.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
