@@ -26,7 +26,8 @@ Recurrent policies (`ActorCriticRecurrent` with single-layer LSTM memories; the 
      `saved_hidden_states` slot t, the LSTM cell on the observation rows of slot t, new raw (h, c) into a ping-pong buffer]
  -> [policy + value on the two h buffers] -> [env step]
 and one `lt_memory_finish` launch behind the last step leaves where(dones[T-1], 0, state) in the modules' `hidden_states`
-(csrc/lt_memory.hip; DESIGN.md 4 "Recurrent rollout step").
+(csrc/lt_memory.hip; DESIGN.md 4 "Recurrent rollout step").  With `fused_gru_memories=True` two GRU memories take the same path through
+`lt_memory_gru_step` / `lt_memory_gru_finish` (csrc/lt_memory_gru.hip): the state is one tensor per memory instead of (h, c).
 """
 from __future__ import annotations
 
@@ -38,18 +39,22 @@ from .. import _abi
 MEMORY_MIN_HIDDEN, MEMORY_MAX_HIDDEN, MEMORY_MAX_K = 64, 512, 1248  # include/lt_memory.h
 
 
-def recurrent_unsupported(ac, storage) -> str | None:
+def recurrent_unsupported(ac, storage, gru_memories: bool = False) -> str | None:
     """Why the fused rollout does not serve this recurrent policy (None: it does): include/lt_memory.h covers two single-layer f32 LSTM
-    memories with biases of one hidden size, a multiple of 64 in [64, 512], on f32 observation rows."""
+    memories with biases of one hidden size, a multiple of 64 in [64, 512], on f32 observation rows.  `gru_memories=True` (the opt-in
+    `fused_gru_memories`): two GRUs of the same description are served as well (include/lt_memory_gru.h), an LSTM beside a GRU is not."""
     mems = (getattr(ac, "memory_a", None), getattr(ac, "memory_c", None))
     if any(m is None for m in mems):
         return "the policy has no memory_a / memory_c"
+    kind = torch.nn.GRU if gru_memories and isinstance(mems[0].rnn, torch.nn.GRU) else torch.nn.LSTM
     for name, m in zip(("memory_a", "memory_c"), mems):
         rnn = m.rnn
-        if not isinstance(rnn, torch.nn.LSTM):
+        if not isinstance(rnn, kind):
+            if gru_memories and isinstance(rnn, (torch.nn.LSTM, torch.nn.GRU)):
+                return f"{name} is a {type(rnn).__name__} beside a {kind.__name__}: the two memories must be of one kind"
             return f"{name} is a {type(rnn).__name__}: only LSTM memories are served"
-        if rnn.num_layers != 1 or rnn.bidirectional or rnn.batch_first or not rnn.bias or rnn.proj_size != 0:
-            return f"{name} must be a single-layer, unidirectional, time-major LSTM with biases and without projection"
+        if rnn.num_layers != 1 or rnn.bidirectional or rnn.batch_first or not rnn.bias or getattr(rnn, "proj_size", 0) != 0:
+            return f"{name} must be a single-layer, unidirectional, time-major {kind.__name__} with biases and without projection"
         h = rnn.hidden_size
         if h % 64 or not MEMORY_MIN_HIDDEN <= h <= MEMORY_MAX_HIDDEN:
             return f"{name}: hidden size {h} is not a multiple of 64 in [{MEMORY_MIN_HIDDEN}, {MEMORY_MAX_HIDDEN}]"
@@ -93,7 +98,8 @@ class FusedRollout:
     The env writes observation rows straight into the storage slots (slot t+1 from slot t; the last step writes the arena
     rows), so nothing copies observations."""
 
-    def __init__(self, env, alg, use_packed_mlp: bool = True, obs_normalizer=None, critic_obs_normalizer=None):
+    def __init__(self, env, alg, use_packed_mlp: bool = True, obs_normalizer=None, critic_obs_normalizer=None,
+                 fused_gru_memories: bool = False):
         from ..env import LocoTouchVecEnv
 
         if not isinstance(env, LocoTouchVecEnv):
@@ -103,14 +109,16 @@ class FusedRollout:
             raise ValueError("FusedRollout supports the 'scalar' noise_std_type of the LocoTouch agent configs")
         # recurrent policy: the two LSTM memories run in one launch in front of the MLPs (csrc/lt_memory.hip)
         self.recurrent = bool(getattr(ac, "is_recurrent", False))
+        self.gru = False  # GRU memories (opt-in `fused_gru_memories`): one state tensor per memory, csrc/lt_memory_gru.hip
         if not self.recurrent and type(ac).__name__ == "ActorCriticEncoder":
             raise ValueError("FusedRollout does not serve ActorCriticEncoder: its encoders are not part of the fused step")
         if self.recurrent:
-            why = recurrent_unsupported(ac, alg.storage)
+            why = recurrent_unsupported(ac, alg.storage, gru_memories=fused_gru_memories)
             if why is None and obs_normalizer is not None:
                 why = "observation normalisers are not served together with a recurrent policy"
             if why is not None:
                 raise ValueError(f"FusedRollout does not serve this recurrent policy: {why}")
+            self.gru = isinstance(ac.memory_a.rnn, torch.nn.GRU)
         self.env, self.alg = env, alg
         self.device = env.device
         self.actions = torch.zeros(env.num_envs, 12, device=self.device)
@@ -156,19 +164,21 @@ class FusedRollout:
             self._init_memory()
 
     def _init_memory(self) -> None:
-        """Ping-pong buffers of the raw (h, c) of both memories, and the storage's `saved_hidden_states` slots."""
+        """Ping-pong buffers of the raw (h, c) of both memories - of h alone for GRU memories - and the storage's `saved_hidden_states`
+        slots."""
         st, ac, n = self.alg.storage, self.alg.actor_critic, self.env.num_envs
         hid = ac.memory_a.rnn.hidden_size
         steps = st.observations.shape[0]
         rows = n + (-n) % 64  # (the MLP launch reads whole row tiles)
-        # _hc[parity][network] = (h, c): step t reads parity (t - 1) & 1 - at t = 0 the modules' own state - and writes parity t & 1
-        self._hc = [[tuple(torch.zeros(rows, hid, device=self.device) for _ in range(2)) for _ in range(2)] for _ in range(2)]
+        ns = 1 if self.gru else 2  # state tensors per memory
+        # _hc[parity][network] = (h, c), or (h,): step t reads parity (t - 1) & 1 - at t = 0 the modules' own state - and writes parity t & 1
+        self._hc = [[tuple(torch.zeros(rows, hid, device=self.device) for _ in range(ns)) for _ in range(2)] for _ in range(2)]
         for name in ("saved_hidden_states_a", "saved_hidden_states_c"):
             saved = getattr(st, name)
             if saved is None:
-                setattr(st, name, [torch.zeros(steps, 1, n, hid, device=self.device) for _ in range(2)])
-            elif len(saved) != 2 or any(s.shape != (steps, 1, n, hid) or s.dtype != torch.float32 or not s.is_contiguous() for s in saved):
-                raise ValueError(f"storage.{name} must be [h, c] of contiguous f32 ({steps}, 1, {n}, {hid}) tensors")
+                setattr(st, name, [torch.zeros(steps, 1, n, hid, device=self.device) for _ in range(ns)])
+            elif len(saved) != ns or any(s.shape != (steps, 1, n, hid) or s.dtype != torch.float32 or not s.is_contiguous() for s in saved):
+                raise ValueError(f"storage.{name} must be {'[h]' if self.gru else '[h, c]'} of contiguous f32 ({steps}, 1, {n}, {hid}) tensors")
         self._state = None  # the modules' (h, c) tensors of both memories, adopted by begin() / rollout()
 
     def _adopt_state(self) -> None:
@@ -179,14 +189,17 @@ class FusedRollout:
         for name, mem in (("memory_a", ac.memory_a), ("memory_c", ac.memory_c)):
             hid = mem.rnn.hidden_size
             if mem.hidden_states is None:
-                mem.hidden_states = (torch.zeros(1, n, hid, device=self.device), torch.zeros(1, n, hid, device=self.device))
-            hc = mem.hidden_states
-            if (not isinstance(hc, tuple) or len(hc) != 2
+                zeros = tuple(torch.zeros(1, n, hid, device=self.device) for _ in self._hc[0][0])
+                mem.hidden_states = zeros[0] if self.gru else zeros
+            hc = (mem.hidden_states,) if self.gru else mem.hidden_states  # (an nn.GRU's state is the tensor itself)
+            if (not isinstance(hc, tuple) or len(hc) != len(self._hc[0][0])
                     or any(not torch.is_tensor(x) or x.shape != (1, n, hid) or x.dtype != torch.float32 or x.device != self._hc[0][0][0].device
                            for x in hc)):
-                raise ValueError(f"{name}.hidden_states must be (h, c) of f32 [1, {n}, {hid}] tensors on {self.device}")
+                raise ValueError(f"{name}.hidden_states must be {'h, an' if self.gru else '(h, c) of'} f32 [1, {n}, {hid}] "
+                                 f"tensor{'' if self.gru else 's'} on {self.device}")
             if not all(x.is_contiguous() for x in hc):
-                mem.hidden_states = hc = tuple(x.contiguous() for x in hc)
+                hc = tuple(x.contiguous() for x in hc)
+                mem.hidden_states = hc[0] if self.gru else hc
             state.append(hc)
         self._state = state
 
@@ -198,10 +211,15 @@ class FusedRollout:
         nets = []
         for k, (mem, x, saved) in enumerate(((ac.memory_a, obs, st.saved_hidden_states_a), (ac.memory_c, cobs, st.saved_hidden_states_c))):
             rnn = mem.rnn
+            if self.gru:
+                nets.append(_abi.LtMemoryGruNet(x.data_ptr(), x.shape[1], rnn.weight_ih_l0.data_ptr(), rnn.weight_hh_l0.data_ptr(),
+                                                rnn.bias_ih_l0.data_ptr(), rnn.bias_hh_l0.data_ptr(), src[k][0].data_ptr(),
+                                                dst[k][0].data_ptr(), saved[0][t].data_ptr()))
+                continue
             nets.append(_abi.LtMemoryNet(x.data_ptr(), x.shape[1], rnn.weight_ih_l0.data_ptr(), rnn.weight_hh_l0.data_ptr(),
                                          rnn.bias_ih_l0.data_ptr(), rnn.bias_hh_l0.data_ptr(), src[k][0].data_ptr(), src[k][1].data_ptr(),
                                          dst[k][0].data_ptr(), dst[k][1].data_ptr(), saved[0][t].data_ptr(), saved[1][t].data_ptr()))
-        _abi.call("lt_memory_step", nets[0], nets[1], st.dones[t - 1] if t > 0 else None, self.env.num_envs, ac.memory_a.rnn.hidden_size,
+        _abi.call("lt_memory_gru_step" if self.gru else "lt_memory_step", nets[0], nets[1], st.dones[t - 1] if t > 0 else None, self.env.num_envs, ac.memory_a.rnn.hidden_size,
                   _abi.stream(self.device))
 
     def _memory_rows(self, t: int):
@@ -211,6 +229,10 @@ class FusedRollout:
 
     def _memory_finish(self, num_steps: int) -> None:
         raw, st = self._hc[(num_steps - 1) & 1], self.alg.storage
+        if self.gru:
+            _abi.call("lt_memory_gru_finish", raw[0][0], raw[1][0], st.dones[num_steps - 1], self.env.num_envs,
+                      self.alg.actor_critic.memory_a.rnn.hidden_size, self._state[0][0], self._state[1][0], _abi.stream(self.device))
+            return
         (ha, ca), (hc, cc) = self._state
         _abi.call("lt_memory_finish", raw[0][0], raw[0][1], raw[1][0], raw[1][1], st.dones[num_steps - 1], self.env.num_envs,
                   self.alg.actor_critic.memory_a.rnn.hidden_size, ha, ca, hc, cc, _abi.stream(self.device))

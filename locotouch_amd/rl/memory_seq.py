@@ -15,6 +15,11 @@ unaffected), in two forms as rl/lstm.py:
     read in place) and `lt_memory_seq_backward` (T launches).  What is not sequential stays outside the loop, one call each:
     dW_hh = dgates^T h_prev and dW_ih = dgates^T X through rl/gru.py `_wgrad`, the bias gradients as column sums.
 The observations and the initial states carry no gradient: dX, dh0 and dc0 are not computed.
+
+GRU memories (`gru_memories=True`, the opt-in `fused_gru_memories` of rl/ppo.py) have the same two forms: the op loop `_gru_forward_ops`
+/ `_gru_backward_ops` and csrc/lt_memory_gru.hip (include/lt_memory_gru.h).  The state is one tensor, the forward record is (out, gates
+= r | z | n | hn, h_prev), and the backward pass leaves TWO gate-gradient arrays, dig = (dr, dz, dn) and dhg = (dr, dz, dn * r): dW_ih =
+dig^T X and db_ih come from the first, dW_hh = dhg^T h_prev and db_hh from the second, each as the kernel wrote it.
 """
 from __future__ import annotations
 
@@ -41,6 +46,14 @@ def _dones2d(dones, T, E):
         return None
     d = dones[..., 0] if dones.dim() == 3 else dones
     assert d.shape == (T, E), "dones must be [T, E] (or [T, E, 1])"
+    return d
+
+
+def _dones_bytes(d):
+    """dones [T, E] as the kernels read them: uint8, E contiguous bytes per step, any stride between steps."""
+    if d is not None:
+        d = d if d.dtype == torch.uint8 else (d != 0).to(torch.uint8)
+        d = d if d.stride(1) == 1 else d.contiguous()
     return d
 
 
@@ -194,18 +207,169 @@ class _MemorySeqHip(torch.autograd.Function):
         return (None,) * 7 + tuple(grads)
 
 
-def unsupported(memory_a, memory_c, obs=None, critic_obs=None, kernels: bool = True) -> str | None:
+# ---- GRU memories: the PyTorch-op form -------------------------------------------------------------------------------------------------
+def _gru_state(h0, E):
+    """h0 as [E, H] from a `saved_hidden_states[0][0][:, e0:e1]`-shaped ([1, E, H]) or [E, H] tensor, or a 1-tuple of one."""
+    if isinstance(h0, (tuple, list)):
+        (h0,) = h0
+    return h0.reshape(E, -1)
+
+
+def _gru_forward_ops(x, done_rows, h0, w_ih, w_hh, b_ih, b_hh):
+    """One network (PyTorch's gate order r, z, n).  Returns the forward record (out, gates [T, E, 4H] = r | z | n | hn, h_prev)."""
+    T, E, _ = x.shape
+    H = w_hh.shape[1]
+    ig = torch.addmm(b_ih, x.reshape(T * E, -1), w_ih.t()).view(T, E, 3 * H)
+    w_hh_t = w_hh.t().contiguous()
+    out, h_prev = x.new_empty(T, E, H), x.new_empty(T, E, H)
+    gates = x.new_empty(T, E, 4 * H)
+    h = h0
+    for t in range(T):
+        if t > 0 and done_rows is not None:
+            h = torch.where(done_rows[t - 1], torch.zeros_like(h), h)
+        h_prev[t] = h
+        hg = torch.addmm(b_hh, h, w_hh_t)  # b_hn stays inside r * (...)
+        r = torch.sigmoid(ig[t, :, :H] + hg[:, :H])
+        z = torch.sigmoid(ig[t, :, H:2 * H] + hg[:, H:2 * H])
+        hn = hg[:, 2 * H:]
+        n = torch.tanh(ig[t, :, 2 * H:] + r * hn)
+        h = (1 - z) * n + z * h
+        gates[t] = torch.cat([r, z, n, hn], dim=1)
+        out[t] = h
+    return out, gates, h_prev
+
+
+def _gru_backward_ops(dout, done_rows, w_hh, gates, h_prev):
+    """(dig, dhg), each [T, E, 3H], of one network from the forward record."""
+    T, E, H = h_prev.shape
+    dig, dhg = h_prev.new_empty(T, E, 3 * H), h_prev.new_empty(T, E, 3 * H)
+    back = None  # what step t + 1 hands to step t: dhg[t+1] W_hh + dh_{t+1} z_{t+1}
+    for t in range(T - 1, -1, -1):
+        dh = dout[t]
+        if back is not None:
+            if done_rows is not None:
+                back = torch.where(done_rows[t], torch.zeros_like(back), back)
+            dh = dh + back
+        r, z, n, hn = gates[t].split(H, dim=1)
+        dn = dh * (1 - z) * (1 - n * n)
+        dz = dh * (h_prev[t] - n) * z * (1 - z)
+        dr = dn * hn * r * (1 - r)
+        dig[t] = torch.cat([dr, dz, dn], dim=1)
+        dhg[t] = torch.cat([dr, dz, dn * r], dim=1)
+        back = dhg[t] @ w_hh + dh * z
+    return dig, dhg
+
+
+def _gru_finish(x, dig, dhg, h_prev):
+    """(dW_ih, dW_hh, db_ih, db_hh) of one network: everything of the backward pass that is not sequential, one call each."""
+    T, E, H = h_prev.shape
+    di2, dh2 = dig.view(T * E, 3 * H), dhg.view(T * E, 3 * H)
+    return _wgrad(di2, x.reshape(T * E, -1)), _wgrad(dh2, h_prev.view(T * E, H)), di2.sum(0), dh2.sum(0)
+
+
+class _GruMemorySeq(torch.autograd.Function):
+    """Both GRU memories, time loop in PyTorch ops."""
+
+    @staticmethod
+    def forward(ctx, x_a, x_c, dones, h0_a, h0_c, *params):
+        done_rows = None if dones is None else (dones != 0).unsqueeze(-1)
+        ra = _gru_forward_ops(x_a, done_rows, h0_a, *params[:4])
+        rc = _gru_forward_ops(x_c, done_rows, h0_c, *params[4:])
+        ctx.save_for_backward(x_a, x_c, done_rows, params[1], params[5], *ra[1:], *rc[1:])
+        ctx.set_materialize_grads(False)
+        return ra[0], rc[0]
+
+    @staticmethod
+    def backward(ctx, dout_a, dout_c):
+        x_a, x_c, done_rows, w_hh_a, w_hh_c, *rec = ctx.saved_tensors
+        grads = []
+        for x, dout, w_hh, (gates, h_prev) in ((x_a, dout_a, w_hh_a, rec[:2]), (x_c, dout_c, w_hh_c, rec[2:])):
+            if dout is None:
+                grads += [None] * 4
+                continue
+            grads += _gru_finish(x, *_gru_backward_ops(dout, done_rows, w_hh, gates, h_prev), h_prev)
+        return (None,) * 5 + tuple(grads)
+
+
+# ---- GRU memories: the HIP form --------------------------------------------------------------------------------------------------------
+def gru_hip_forward(x_a, x_c, dones, h0_a, h0_c, params):
+    """`lt_memory_gru_seq_forward`: T launches.  Arguments as `hip_forward` without the cell states; params: the eight GRU parameters.
+    Returns the two forward records {out, gates, h_prev}."""
+    from .. import _abi
+
+    T, E, _ = x_a.shape
+    H = params[1].shape[1]
+    recs, nets = [], []
+    for x, h0, (w_ih, w_hh, b_ih, b_hh) in ((x_a, h0_a, params[:4]), (x_c, h0_c, params[4:])):
+        x = _rows(x)
+        ops = [t.detach().contiguous() for t in (w_ih, w_hh, b_ih, b_hh, h0)]
+        rec = {k: x.new_empty(T, E, 4 * H if k == "gates" else H) for k in ("out", "gates", "h_prev")}
+        nets.append(_abi.LtMemoryGruSeqNet(x=x.data_ptr(), x_stride=x.stride(0), I=x.shape[2], w_ih=ops[0].data_ptr(), w_hh=ops[1].data_ptr(),
+                                           b_ih=ops[2].data_ptr(), b_hh=ops[3].data_ptr(), h0=ops[4].data_ptr(),
+                                           **{k: v.data_ptr() for k, v in rec.items()}))
+        recs.append(rec)
+    assert dones is None or (dones.dtype == torch.uint8 and dones.stride(1) == 1)
+    _abi.call("lt_memory_gru_seq_forward", nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H, _abi.stream(x_a.device))
+    return recs
+
+
+def gru_hip_backward(douts, dones, w_hhs, recs):
+    """`lt_memory_gru_seq_backward`: T launches.  Returns [(dig, dhg)] of the two networks, each [T, E, 3H]."""
+    from .. import _abi
+
+    T, E, H = recs[0]["out"].shape
+    nets, dgs = [], []
+    for dout, w_hh, rec in zip(douts, w_hhs, recs):
+        dout = torch.zeros_like(rec["out"]) if dout is None else dout.contiguous()
+        w = w_hh.detach().contiguous()
+        dig, dhg, carry = dout.new_empty(T, E, 3 * H), dout.new_empty(T, E, 3 * H), dout.new_empty(E, H)
+        nets.append(_abi.LtMemoryGruSeqGrad(dout=dout.data_ptr(), w_hh=w.data_ptr(), gates=rec["gates"].data_ptr(), h_prev=rec["h_prev"].data_ptr(),
+                                            dig=dig.data_ptr(), dhg=dhg.data_ptr(), dh_carry=carry.data_ptr()))
+        dgs.append((dig, dhg))
+    _abi.call("lt_memory_gru_seq_backward", nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H,
+              _abi.stream(dgs[0][0].device))
+    return dgs
+
+
+class _GruMemorySeqHip(torch.autograd.Function):
+    """Both GRU memories, time loops in csrc/lt_memory_gru.hip."""
+
+    @staticmethod
+    def forward(ctx, x_a, x_c, dones, h0_a, h0_c, *params):
+        ra, rc = gru_hip_forward(x_a, x_c, dones, h0_a, h0_c, params)
+        ctx.save_for_backward(x_a, x_c, dones, params[1], params[5], *(r[k] for r in (ra, rc) for k in ("out", "gates", "h_prev")))
+        ctx.set_materialize_grads(False)
+        return ra["out"], rc["out"]
+
+    @staticmethod
+    def backward(ctx, dout_a, dout_c):
+        x_a, x_c, dones, w_hh_a, w_hh_c, *rec = ctx.saved_tensors
+        keys = ("out", "gates", "h_prev")
+        recs = [dict(zip(keys, rec[:3])), dict(zip(keys, rec[3:]))]
+        dgs = gru_hip_backward((dout_a, dout_c), dones, (w_hh_a, w_hh_c), recs)
+        grads = []
+        for x, (dig, dhg), r in zip((x_a, x_c), dgs, recs):
+            grads += _gru_finish(x, dig, dhg, r["h_prev"])
+        return (None,) * 5 + tuple(grads)
+
+
+def unsupported(memory_a, memory_c, obs=None, critic_obs=None, kernels: bool = True, gru_memories: bool = False) -> str | None:
     """Why `PPO(fused_recurrent_update=True)` and `memory_rollout_sequence` refuse these memories / rows (None: they do not):
     include/lt_memory_seq.h covers two single-layer LSTMs with biases of one hidden size, a multiple of 64 in [64, 512], with
     I + H <= 1248, on observation rows - BOTH tensors - of the memories' dtype (the HIP form itself: f32 on a GPU, `serves`; the
     PyTorch-op form covers the same set on the CPU and in other dtypes).  `kernels=False`: what the PyTorch-op form refuses as well - all
-    of the above but the bounds on the sizes."""
+    of the above but the bounds on the sizes.  `gru_memories=True` (the opt-in `fused_gru_memories`): two GRUs of the same description
+    are served as well (include/lt_memory_gru.h), one LSTM beside one GRU is not."""
+    kind = type(getattr(memory_a, "rnn", None)) if gru_memories and _is_gru(memory_a) else torch.nn.LSTM
     for name, m in (("memory_a", memory_a), ("memory_c", memory_c)):
         rnn = getattr(m, "rnn", None)
-        if not isinstance(rnn, torch.nn.LSTM):
+        if not isinstance(rnn, kind):
+            if gru_memories and isinstance(rnn, (torch.nn.LSTM, torch.nn.GRU)):
+                return f"{name} is a {type(rnn).__name__} beside a {kind.__name__}: the two memories must be of one kind"
             return f"{name} is a {type(rnn).__name__}: only LSTM memories are served"
-        if rnn.num_layers != 1 or rnn.bidirectional or rnn.batch_first or not rnn.bias or rnn.proj_size != 0:
-            return f"{name} must be a single-layer, unidirectional, time-major LSTM with biases and without projection (it has {rnn.num_layers} layers)"
+        if rnn.num_layers != 1 or rnn.bidirectional or rnn.batch_first or not rnn.bias or getattr(rnn, "proj_size", 0) != 0:
+            return (f"{name} must be a single-layer, unidirectional, time-major {kind.__name__} with biases and without projection "
+                    f"(it has {rnn.num_layers} layers)")
         h = rnn.hidden_size
         if not kernels:
             continue
@@ -221,15 +385,19 @@ def unsupported(memory_a, memory_c, obs=None, critic_obs=None, kernels: bool = T
     return None
 
 
-def serves(memory_a, memory_c, obs: torch.Tensor, critic_obs: torch.Tensor | None = None) -> bool:
+def _is_gru(memory) -> bool:
+    return isinstance(getattr(memory, "rnn", None), torch.nn.GRU)
+
+
+def serves(memory_a, memory_c, obs: torch.Tensor, critic_obs: torch.Tensor | None = None, gru_memories: bool = False) -> bool:
     """Whether `memory_rollout_sequence` sends (memories, obs, critic_obs) through the HIP form: f32 rows and parameters on a GPU, in
     the set `unsupported` describes."""
     critic_obs = obs if critic_obs is None else critic_obs
     return bool(use_hip_kernels and obs.is_cuda and critic_obs.is_cuda and obs.dtype == torch.float32 and memory_a.rnn.weight_ih_l0.is_cuda
-                and unsupported(memory_a, memory_c, obs, critic_obs) is None)
+                and unsupported(memory_a, memory_c, obs, critic_obs, gru_memories=gru_memories) is None)
 
 
-def memory_rollout_sequence(memory_a, memory_c, obs, critic_obs, dones, hc0_a, hc0_c):
+def memory_rollout_sequence(memory_a, memory_c, obs, critic_obs, dones, hc0_a, hc0_c, gru_memories: bool = False):
     """(out_a, out_c), each [T, E, H]: `memory_a` over obs [T, E, I_a] and `memory_c` over critic_obs [T, E, I_c] for the whole rollout of
     an env block, from the states hc0_* = (h0, c0) saved at step 0 ([1, E, H] or [E, H]); the carried state is replaced by zeros wherever
     dones[t - 1] ([T, E] or [T, E, 1], any integer or bool dtype; None: no reset) is set.
@@ -239,19 +407,24 @@ def memory_rollout_sequence(memory_a, memory_c, obs, critic_obs, dones, hc0_a, h
     runs the same blocks more than once hands over contiguous copies made once, as `PPO._recurrent_update` does per update.
 
     Rows whose dtype is not the memories' own, GRU or multi-layer memories raise `ValueError`; there is no quiet change of path on them.
-    The HIP form runs where `serves` says so, the PyTorch-op form elsewhere (the CPU, other dtypes, `use_hip_kernels` off)."""
+    The HIP form runs where `serves` says so, the PyTorch-op form elsewhere (the CPU, other dtypes, `use_hip_kernels` off).
+
+    `gru_memories=True`: two GRU memories are served too; hc0_* is then the one state tensor h0 ([1, E, H] or [E, H], or a 1-tuple)."""
     T, E, _ = obs.shape
-    why = unsupported(memory_a, memory_c, obs, critic_obs, kernels=False)  # (a size outside the kernels' set has the PyTorch-op form)
+    why = unsupported(memory_a, memory_c, obs, critic_obs, kernels=False, gru_memories=gru_memories)  # (a size outside the kernels' set has the PyTorch-op form)
     if why is not None:
         raise ValueError(f"memory_rollout_sequence: {why}")
     d = _dones2d(dones, T, E)
+    if gru_memories and _is_gru(memory_a):
+        states = (_gru_state(hc0_a, E), _gru_state(hc0_c, E))
+        params = (*_params(memory_a), *_params(memory_c))
+        if serves(memory_a, memory_c, obs, critic_obs, gru_memories=True):
+            return _GruMemorySeqHip.apply(obs, critic_obs, _dones_bytes(d), *states, *params)
+        return _GruMemorySeq.apply(obs, critic_obs, d, *states, *params)
     states = (*_state(hc0_a, E), *_state(hc0_c, E))
     params = (*_params(memory_a), *_params(memory_c))
     if serves(memory_a, memory_c, obs, critic_obs):
-        if d is not None:
-            d = d if d.dtype == torch.uint8 else (d != 0).to(torch.uint8)
-            d = d if d.stride(1) == 1 else d.contiguous()  # the kernels read E contiguous bytes per step, any stride between steps
-        return _MemorySeqHip.apply(obs, critic_obs, d, *states, *params)
+        return _MemorySeqHip.apply(obs, critic_obs, _dones_bytes(d), *states, *params)
     return _MemorySeq.apply(obs, critic_obs, d, *states, *params)
 
 

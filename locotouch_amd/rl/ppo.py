@@ -33,6 +33,8 @@ class PPO:
         self.direct_update = on_gpu and bool(unused.get("direct_update", True))  # no autograd graph, no host read between minibatch steps (_direct_update)
         # opt-in: recurrent (LSTM) policies update on whole rollouts of env blocks, without padding (_recurrent_update, rl/memory_seq.py)
         self.fused_recurrent_update = bool(unused.get("fused_recurrent_update", False))
+        # opt-in: `fused_recurrent_update` serves GRU memories as well (csrc/lt_memory_gru.hip); on its own it does nothing
+        self.fused_gru_memories = bool(unused.get("fused_gru_memories", False))
         if self.fused_recurrent_update:
             why = self._recurrent_update_unsupported()
             if why is not None:
@@ -318,10 +320,11 @@ class PPO:
         if type(ac) is not ActorCriticRecurrent:
             return f"the policy is a {type(ac).__name__}: only a plain ActorCriticRecurrent is served"
         st = getattr(self, "storage", None)  # (None at construction: the observation rows' dtype is checked at the first update)
-        return unsupported(ac.memory_a, ac.memory_c, *((None, None) if st is None else (st.observations, st.privileged_observations)))
+        return unsupported(ac.memory_a, ac.memory_c, *((None, None) if st is None else (st.observations, st.privileged_observations)),
+                           gru_memories=self.fused_gru_memories)
 
     def _recurrent_update(self):
-        """The update of an `ActorCriticRecurrent` with LSTM memories on WHOLE ROLLOUTS of env blocks (rl/memory_seq.py: why this equals
+        """The update of an `ActorCriticRecurrent` with LSTM (with `fused_gru_memories`: or GRU) memories on WHOLE ROLLOUTS of env blocks (rl/memory_seq.py: why this equals
         the padded trajectories of `_eager_update`): no `split_and_pad_trajectories`, no `recurrent_mini_batches`, no boolean indexing.
         Per optimizer step: the env block [e0, e1) of the reference's dealing (per = N // num_mini_batches, leftover envs dropped), both
         memories over its T steps from the states saved at step 0 (`memory_rollout_sequence`; on the GPU csrc/lt_memory.hip), the two
@@ -353,7 +356,8 @@ class PPO:
             for sl, obs, cobs in blocks:
                 hc_a = tuple(h[0][sl] for h in st.saved_hidden_states_a)
                 hc_c = tuple(h[0][sl] for h in st.saved_hidden_states_c)
-                out_a, out_c = memory_rollout_sequence(ac.memory_a, ac.memory_c, obs, cobs, dones[sl], hc_a, hc_c)
+                out_a, out_c = memory_rollout_sequence(ac.memory_a, ac.memory_c, obs, cobs, dones[sl], hc_a, hc_c,
+                                                       gru_memories=self.fused_gru_memories)
                 adv = st.advantages[sl]
                 if self.normalize_advantage_per_mini_batch:
                     with torch.no_grad():

@@ -40,6 +40,8 @@ class OnPolicyRunner:
         ac = getattr(_m, cls_name)(num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
         if "fused_recurrent_update" in self.cfg:  # opt-in (rl/ppo.py `_recurrent_update`); a refusal is PPO's ValueError
             self.alg_cfg["fused_recurrent_update"] = bool(self.cfg["fused_recurrent_update"])
+        if "fused_gru_memories" in self.cfg:  # opt-in: the two switches above / below also serve GRU memories (csrc/lt_memory_gru.hip)
+            self.alg_cfg["fused_gru_memories"] = bool(self.cfg["fused_gru_memories"])
         self.alg = PPO(ac, device=device, dist=self.dist, **self.alg_cfg)
         self.num_steps_per_env = int(self.cfg["num_steps_per_env"])
         self.save_interval = int(self.cfg.get("save_interval", 50))
@@ -180,11 +182,13 @@ class OnPolicyRunner:
         if type(ac) is ActorCriticRecurrent:
             from .fused import recurrent_unsupported
 
-            # single-layer f32 LSTM memories alone, without the normaliser (it would have to feed the memory step, not the MLPs)
+            # single-layer f32 LSTM memories alone (GRU ones too behind `fused_gru_memories`), without the normaliser (it would have to
+            # feed the memory step, not the MLPs)
+            gru = bool(self.cfg.get("fused_gru_memories", False))
             if (not self.cfg.get("fused_recurrent_rollout", False) or self.empirical_normalization
-                    or recurrent_unsupported(ac, self.alg.storage) is not None):
+                    or recurrent_unsupported(ac, self.alg.storage, gru_memories=gru) is not None):
                 return None
-            return FusedRollout(target, self.alg)
+            return FusedRollout(target, self.alg, fused_gru_memories=gru)
         if type(ac) is not ActorCritic:
             return None  # the fused rollout packs the actor / critic MLPs (ActorCriticEncoder keeps the eager loop)
         if not self.empirical_normalization:

@@ -52,6 +52,8 @@ def main() -> None:
                          "the kernels' Philox stream instead of torch's generator")
     ap.add_argument("--fused_recurrent_update", action="store_true",
                     help="recurrent (LSTM) policies: update on whole rollouts of env blocks, without padding (rl/ppo.py `_recurrent_update`)")
+    ap.add_argument("--fused_gru_memories", action="store_true",
+                    help="the two switches above also serve GRU memories (csrc/lt_memory_gru.hip); on its own it does nothing")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -72,6 +74,8 @@ def main() -> None:
         cfg["fused_recurrent_rollout"] = True
     if args.fused_recurrent_update:
         cfg["fused_recurrent_update"] = True
+    if args.fused_gru_memories:
+        cfg["fused_gru_memories"] = True
     device = f"cuda:{dist.local_rank}"
     torch.cuda.set_device(device)
     torch.manual_seed(cfg["seed"])

@@ -11,7 +11,10 @@ Per leg: `rollout_ms` - one 24-step rollout, host wall clock between two device 
 ends in the update's host read), same statistics.  The `on` leg also times the rollout captured into one hipGraph (events).
 The memory-step kernel's own time comes from a `rocprofv3 --kernel-trace --stats` run of its own (`--mode trace` under the profiler).
 
-    python tools/recurrent_rollout_bench.py [--envs 4096] [--rounds 7] [--out profiles/recurrent_rollout_4096.json]
+`--rnn_type gru`: GRU memories; the on leg then also sets `fused_gru_memories` (csrc/lt_memory_gru.hip), the off leg is the eager loop
+through `nn.GRU`, and the file is profiles/recurrent_rollout_gru_<n>.json.
+
+    python tools/recurrent_rollout_bench.py [--envs 4096] [--rounds 7] [--rnn_type lstm] [--out profiles/recurrent_rollout_4096.json]
 """
 from __future__ import annotations
 
@@ -37,13 +40,15 @@ def stats(xs: list[float]) -> dict:
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "rounds": len(xs)}
 
 
-def make_runner(envs: int, on: bool):
+def make_runner(envs: int, on: bool, rnn_type: str = "lstm"):
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.env import make
     from locotouch_amd.rl import OnPolicyRunner
 
     cfg = dict(train_cfg(TASK), fused_recurrent_rollout=on)
-    cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=HIDDEN, rnn_num_layers=1)
+    if rnn_type == "gru":
+        cfg["fused_gru_memories"] = on
+    cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type=rnn_type, rnn_hidden_size=HIDDEN, rnn_num_layers=1)
     return OnPolicyRunner(make(TASK, num_envs=envs, device="cuda:0", seed=1), cfg, log_dir=None, device="cuda:0")
 
 
@@ -62,11 +67,11 @@ def eager_rollout(runner, obs, critic_obs):
     return obs, critic_obs
 
 
-def measure(mode: str, envs: int, rounds: int, warmup: int) -> dict:
+def measure(mode: str, envs: int, rounds: int, warmup: int, rnn_type: str = "lstm") -> dict:
     import torch
 
     on = mode != "off"
-    runner = make_runner(envs, on)
+    runner = make_runner(envs, on, rnn_type)
     T = runner.num_steps_per_env
     fused = runner._make_fused()
     assert (fused is not None) == on
@@ -116,23 +121,25 @@ def measure(mode: str, envs: int, rounds: int, warmup: int) -> dict:
     return out
 
 
-def kernel_trace(envs: int) -> dict:
-    """lt_memory_step_kernel's own time: a `rocprofv3 --kernel-trace --stats` run of three fused rollouts, nothing else traced."""
+def kernel_trace(envs: int, rnn_type: str = "lstm") -> dict:
+    """The memory-step kernel's own time: a `rocprofv3 --kernel-trace --stats` run of three fused rollouts, nothing else traced."""
+    kernel = "lt_memory_gru_step_kernel" if rnn_type == "gru" else "lt_memory_step_kernel"
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return {"error": "rocprofv3 not found"}
     tmp = tempfile.mkdtemp(prefix="recurrent_trace_")
     try:
         p = subprocess.run([exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "trace", "--", sys.executable,
-                            os.path.abspath(__file__), "--mode", "trace", "--envs", str(envs)], capture_output=True, text=True, timeout=600)
+                            os.path.abspath(__file__), "--mode", "trace", "--envs", str(envs), "--rnn_type", rnn_type], capture_output=True, text=True,
+                           timeout=600)
         if p.returncode != 0:
             return {"error": f"rocprofv3 exit {p.returncode}: {p.stderr[-500:]}"}
         for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(path)):
-                if "lt_memory_step_kernel" in row.get("Name", ""):
+                if kernel in row.get("Name", ""):
                     return {"kernel": row["Name"], "calls": int(row["Calls"]), "average_us": float(row["AverageNs"]) / 1e3,
                             "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
-        return {"error": "no lt_memory_step_kernel row in the kernel statistics"}
+        return {"error": f"no {kernel} row in the kernel statistics"}
     except (OSError, subprocess.TimeoutExpired, KeyError, ValueError) as exc:
         return {"error": f"{type(exc).__name__}: {exc}"}
     finally:
@@ -144,6 +151,7 @@ def main() -> None:
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rnn_type", choices=["lstm", "gru"], default="lstm")
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", help="what to record as measured_on_commit (default: git rev-parse --short HEAD, null outside a checkout)")
     ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
@@ -152,12 +160,12 @@ def main() -> None:
     if args.rounds < 5:
         sys.exit("--rounds must be at least 5")
     if args.mode:
-        print("RESULT " + json.dumps(measure(args.mode, args.envs, args.rounds, args.warmup)))
+        print("RESULT " + json.dumps(measure(args.mode, args.envs, args.rounds, args.warmup, args.rnn_type)))
         return
     legs = {}
     for mode in ("off", "on"):  # a fresh process each: no allocator or graph state carried from one to the next
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--envs", str(args.envs), "--rounds", str(args.rounds),
-                            "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=900)
+                            "--warmup", str(args.warmup), "--rnn_type", args.rnn_type], capture_output=True, text=True, timeout=900)
         line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
         if p.returncode != 0 or not line:
             sys.exit(f"{mode}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
@@ -170,16 +178,16 @@ def main() -> None:
     def faster(key):  # on is faster by MORE than the spread of either leg: the intervals [min, max] do not even touch
         return legs["on"][key]["max"] < legs["off"][key]["min"]
 
-    res = {"task": TASK, "envs": args.envs, "hidden": HIDDEN, "measured_on_commit": args.commit or commit,
+    res = {"task": TASK, "envs": args.envs, "hidden": HIDDEN, "rnn_type": args.rnn_type, "measured_on_commit": args.commit or commit,
            "notes": {"off": "the switch off: the runner's eager loop, the same code as before the switch existed",
                      "rollout_ms": "host wall clock of one rollout between two device synchronisations",
                      "iteration_ms": "runner wall clock, collection + learning (the update ends in a host read)",
                      "spread": "min and max over the rounds, beside the median"},
-           **legs, "memory_step_kernel": None if args.no_trace else kernel_trace(args.envs),
+           **legs, "memory_step_kernel": None if args.no_trace else kernel_trace(args.envs, args.rnn_type),
            "off_over_on_rollout": legs["off"]["rollout_ms"]["median"] / legs["on"]["rollout_ms"]["median"],
            "off_over_on_iteration": legs["off"]["iteration_ms"]["median"] / legs["on"]["iteration_ms"]["median"],
            "on_faster_than_the_spread": {"rollout": faster("rollout_ms"), "iteration": faster("iteration_ms")}}
-    out = args.out or os.path.join(REPO, "profiles", f"recurrent_rollout_{args.envs}.json")
+    out = args.out or os.path.join(REPO, "profiles", f"recurrent_rollout_{'gru_' if args.rnn_type == 'gru' else ''}{args.envs}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(res, f, indent=1)

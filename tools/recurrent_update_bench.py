@@ -11,7 +11,11 @@ tree with the switch off (the same code path, `_eager_update`), and the file say
 The two new kernels' per-launch time comes from a `rocprofv3 --kernel-trace --stats` run of its own (`--mode trace` under the profiler,
 no counters in it).  A gain is claimed only where the legs' [min, max] intervals do not overlap.
 
-    python tools/recurrent_update_bench.py [--envs 4096] [--rounds 7] [--off-result FILE] [--out profiles/recurrent_update_4096.json]
+`--rnn_type gru`: GRU memories; both legs set `fused_gru_memories` (a tree without the key ignores it and collects in the eager loop:
+`update_ms` is the figure that compares), the off leg updates through `nn.GRU` on padded trajectories, the on leg through
+csrc/lt_memory_gru.hip, and the file is profiles/recurrent_update_gru_<n>.json.
+
+    python tools/recurrent_update_bench.py [--envs 4096] [--rounds 7] [--rnn_type lstm] [--off-result FILE] [--out profiles/recurrent_update_4096.json]
 """
 from __future__ import annotations
 
@@ -30,7 +34,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 TASK = "Isaac-RandCylinderTransportTeacher-LocoTouch-v1"
 HIDDEN = 256
-KERNELS = ("lt_memory_step_kernel", "lt_memory_seq_bwd_kernel", "lt_memory_seq_bwd_open_kernel")
+KERNELS = {"lstm": ("lt_memory_step_kernel", "lt_memory_seq_bwd_kernel", "lt_memory_seq_bwd_open_kernel"),
+           "gru": ("lt_memory_gru_step_kernel", "lt_memory_gru_seq_bwd_kernel", "lt_memory_gru_seq_bwd_open_kernel")}
 
 
 def stats(xs: list[float]) -> dict:
@@ -44,18 +49,20 @@ def tree() -> str | None:
         return None
 
 
-def make_runner(envs: int, on: bool):
+def make_runner(envs: int, on: bool, rnn_type: str = "lstm"):
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.env import make
     from locotouch_amd.rl import OnPolicyRunner
 
     cfg = dict(train_cfg(TASK), fused_recurrent_rollout=True, fused_recurrent_update=on)
-    cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=HIDDEN, rnn_num_layers=1)
+    if rnn_type == "gru":
+        cfg["fused_gru_memories"] = True
+    cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type=rnn_type, rnn_hidden_size=HIDDEN, rnn_num_layers=1)
     return OnPolicyRunner(make(TASK, num_envs=envs, device="cuda:0", seed=1), cfg, log_dir=None, device="cuda:0")
 
 
-def measure(mode: str, envs: int, rounds: int, warmup: int) -> dict:
-    runner = make_runner(envs, mode != "off")
+def measure(mode: str, envs: int, rounds: int, warmup: int, rnn_type: str = "lstm") -> dict:
+    runner = make_runner(envs, mode != "off", rnn_type)
     alg = runner.alg
     out = {"mode": mode, "tree": tree(), "switch": bool(getattr(alg, "fused_recurrent_update", False)), "steps": runner.num_steps_per_env,
            "num_mini_batches": alg.num_mini_batches, "num_learning_epochs": alg.num_learning_epochs}
@@ -69,7 +76,7 @@ def measure(mode: str, envs: int, rounds: int, warmup: int) -> dict:
     return out
 
 
-def kernel_trace(envs: int) -> dict:
+def kernel_trace(envs: int, rnn_type: str = "lstm") -> dict:
     """Per-launch time of the sequence kernels: a `rocprofv3 --kernel-trace --stats` run of two iterations, nothing else traced."""
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
@@ -77,13 +84,14 @@ def kernel_trace(envs: int) -> dict:
     tmp = tempfile.mkdtemp(prefix="recurrent_update_trace_")
     try:
         p = subprocess.run([exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "trace", "--", sys.executable,
-                            os.path.abspath(__file__), "--mode", "trace", "--envs", str(envs)], capture_output=True, text=True, timeout=600)
+                            os.path.abspath(__file__), "--mode", "trace", "--envs", str(envs), "--rnn_type", rnn_type], capture_output=True, text=True,
+                           timeout=600)
         if p.returncode != 0:
             return {"error": f"rocprofv3 exit {p.returncode}: {p.stderr[-500:]}"}
         rows = {}
         for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(path)):
-                if any(k in row.get("Name", "") for k in KERNELS):
+                if any(k in row.get("Name", "") for k in KERNELS[rnn_type]):
                     rows[row["Name"]] = {"calls": int(row["Calls"]), "average_us": float(row["AverageNs"]) / 1e3,
                                          "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
         return rows or {"error": "no sequence-kernel row in the kernel statistics"}
@@ -98,6 +106,7 @@ def main() -> None:
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rnn_type", choices=["lstm", "gru"], default="lstm")
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", help="what to record as measured_on_commit (default: git rev-parse --short HEAD, null outside a checkout)")
     ap.add_argument("--off-result", help="file holding the RESULT line of `--mode off` run in a checkout of the parent commit")
@@ -107,7 +116,7 @@ def main() -> None:
     if args.rounds < 5:
         sys.exit("--rounds must be at least 5")
     if args.mode:
-        print("RESULT " + json.dumps(measure(args.mode, args.envs, args.rounds, args.warmup)))
+        print("RESULT " + json.dumps(measure(args.mode, args.envs, args.rounds, args.warmup, args.rnn_type)))
         return
     legs = {}
     if args.off_result:
@@ -119,7 +128,7 @@ def main() -> None:
         if mode in legs:
             continue
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--envs", str(args.envs), "--rounds", str(args.rounds),
-                            "--warmup", str(args.warmup)], capture_output=True, text=True, timeout=900)
+                            "--warmup", str(args.warmup), "--rnn_type", args.rnn_type], capture_output=True, text=True, timeout=900)
         line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
         if p.returncode != 0 or not line:
             sys.exit(f"{mode}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
@@ -130,16 +139,16 @@ def main() -> None:
     def faster(key):  # on is faster by MORE than the spread of either leg: the intervals [min, max] do not even touch
         return legs["on"][key]["max"] < legs["off"][key]["min"]
 
-    res = {"task": TASK, "envs": args.envs, "hidden": HIDDEN, "measured_on_commit": args.commit or tree(),
+    res = {"task": TASK, "envs": args.envs, "hidden": HIDDEN, "rnn_type": args.rnn_type, "measured_on_commit": args.commit or tree(),
            "notes": {"off": "the parent commit's tree where `tree` differs from the on leg's; else this tree with the switch off",
                      "update_ms": "runner wall clock of alg.update() (it ends in a host read)",
                      "iteration_ms": "runner wall clock, collection + learning",
                      "spread": "min and max over the rounds, beside the median"},
-           **legs, "kernels": None if args.no_trace else kernel_trace(args.envs),
+           **legs, "kernels": None if args.no_trace else kernel_trace(args.envs, args.rnn_type),
            "off_over_on_update": legs["off"]["update_ms"]["median"] / legs["on"]["update_ms"]["median"],
            "off_over_on_iteration": legs["off"]["iteration_ms"]["median"] / legs["on"]["iteration_ms"]["median"],
            "on_faster_than_the_spread": {"update": faster("update_ms"), "iteration": faster("iteration_ms")}}
-    out = args.out or os.path.join(REPO, "profiles", f"recurrent_update_{args.envs}.json")
+    out = args.out or os.path.join(REPO, "profiles", f"recurrent_update_{'gru_' if args.rnn_type == 'gru' else ''}{args.envs}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
