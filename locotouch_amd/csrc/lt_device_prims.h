@@ -32,6 +32,11 @@ __device__ __forceinline__ int wave_uniform(int x) { return __builtin_amdgcn_rea
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0); }
 
+// the cell arithmetic of the recurrent kernels (lt_lstm.hip, lt_gru.hip, lt_memory.hip, lt_memory_gru.hip): v_exp_f32 forms; tanh from
+// exp(-2 |x|), which never overflows
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+__device__ __forceinline__ float tanhf_(float x) { const float e = __expf(-2.f * fabsf(x)); const float t = (1.f - e) / (1.f + e); return x < 0.f ? -t : t; }
+
 // nothing is scheduled across this point: loads issued above it stay above the arithmetic below it
 __device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 

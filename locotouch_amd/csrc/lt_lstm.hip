@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "lt_device_prims.h"
 #include "lt_env.h"
 #include "lt_internal.h"
 #include "lt_lstm.h"
@@ -23,8 +24,8 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) { const float e = __expf(-2.f * fabsf(x)); const float t = (1.f - e) / (1.f + e); return x < 0.f ? -t : t; }
+using lt::sigmoidf_;
+using lt::tanhf_;
 
 // ---- forward step: (h', c') = LSTM(ig_t, h, c) for a 16-unit x 16-row tile; ws = the activated gates (i, f, g, o) ------------------
 // grid (H / 16, ceil(B / 16)), block 256 (4 waves, wave w reduces k in [w * H / 4, (w + 1) * H / 4)); four accumulators, one per gate.

@@ -27,7 +27,8 @@ Recurrent policies (`ActorCriticRecurrent` with single-layer LSTM memories; the 
  -> [policy + value on the two h buffers] -> [env step]
 and one `lt_memory_finish` launch behind the last step leaves where(dones[T-1], 0, state) in the modules' `hidden_states`
 (csrc/lt_memory.hip; DESIGN.md 4 "Recurrent rollout step").  With `fused_gru_memories=True` two GRU memories take the same path through
-`lt_memory_gru_step` / `lt_memory_gru_finish` (csrc/lt_memory_gru.hip): the state is one tensor per memory instead of (h, c).
+`lt_memory_gru_step` / `lt_memory_gru_finish` (csrc/lt_memory_gru.hip): the state is one tensor per memory instead of (h, c).  Both files
+are a cell on the one row-block kernel of csrc/lt_memory_tile.h.
 """
 from __future__ import annotations
 

@@ -11,13 +11,13 @@ reset state is a constant), and the output [T, E, H] is already in the row order
 `memory_rollout_sequence` is one `torch.autograd.Function` over both memories' `nn.LSTM` parameters (the modules' own: checkpoints are
 unaffected), in two forms as rl/lstm.py:
   * a PyTorch-op time loop with `where(dones[t - 1], 0, .)` on the carry: the CPU, any dtype, shapes the kernels do not cover;
-  * csrc/lt_memory.hip (include/lt_memory_seq.h): `lt_memory_seq_forward` (T launches, both networks in each, the observation rows
-    read in place) and `lt_memory_seq_backward` (T launches).  What is not sequential stays outside the loop, one call each:
+  * csrc/lt_memory.hip (the LSTM cell on the kernels of csrc/lt_memory_tile.h; include/lt_memory_seq.h): `lt_memory_seq_forward`
+    (T launches, both networks in each, the observation rows read in place) and `lt_memory_seq_backward` (T launches).  What is not sequential stays outside the loop, one call each:
     dW_hh = dgates^T h_prev and dW_ih = dgates^T X through rl/gru.py `_wgrad`, the bias gradients as column sums.
 The observations and the initial states carry no gradient: dX, dh0 and dc0 are not computed.
 
 GRU memories (`gru_memories=True`, the opt-in `fused_gru_memories` of rl/ppo.py) have the same two forms: the op loop `_gru_forward_ops`
-/ `_gru_backward_ops` and csrc/lt_memory_gru.hip (include/lt_memory_gru.h).  The state is one tensor, the forward record is (out, gates
+/ `_gru_backward_ops` and csrc/lt_memory_gru.hip (the GRU cell on the same kernels; include/lt_memory_gru.h).  The state is one tensor, the forward record is (out, gates
 = r | z | n | hn, h_prev), and the backward pass leaves TWO gate-gradient arrays, dig = (dr, dz, dn) and dhg = (dr, dz, dn * r): dW_ih =
 dig^T X and db_ih come from the first, dW_hh = dhg^T h_prev and db_hh from the second, each as the kernel wrote it.
 """

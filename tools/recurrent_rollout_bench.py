@@ -123,7 +123,7 @@ def measure(mode: str, envs: int, rounds: int, warmup: int, rnn_type: str = "lst
 
 def kernel_trace(envs: int, rnn_type: str = "lstm") -> dict:
     """The memory-step kernel's own time: a `rocprofv3 --kernel-trace --stats` run of three fused rollouts, nothing else traced."""
-    kernel = "lt_memory_gru_step_kernel" if rnn_type == "gru" else "lt_memory_step_kernel"
+    kernel = "lt_memory_step_kernel"  # both cells: the cell is a template argument of the one kernel (csrc/lt_memory_tile.h)
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return {"error": "rocprofv3 not found"}

@@ -34,8 +34,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 TASK = "Isaac-RandCylinderTransportTeacher-LocoTouch-v1"
 HIDDEN = 256
-KERNELS = {"lstm": ("lt_memory_step_kernel", "lt_memory_seq_bwd_kernel", "lt_memory_seq_bwd_open_kernel"),
-           "gru": ("lt_memory_gru_step_kernel", "lt_memory_gru_seq_bwd_kernel", "lt_memory_gru_seq_bwd_open_kernel")}
+# (one set of kernel templates serves both cells, csrc/lt_memory_tile.h: the cell is a template argument in the traced name)
+KERNELS = {rnn: ("lt_memory_step_kernel", "lt_memory_seq_bwd_kernel", "lt_memory_seq_bwd_open_kernel") for rnn in ("lstm", "gru")}
 
 
 def stats(xs: list[float]) -> dict:
