@@ -25,6 +25,7 @@ LSTM_HEADER = os.path.join(REPO, "include", "lt_lstm.h")  # included by lt_env.h
 MEMORY_HEADER = os.path.join(REPO, "include", "lt_memory.h")  # included by lt_env.h: one rollout step of a recurrent policy's two LSTM memories
 MEMORY_SEQ_HEADER = os.path.join(REPO, "include", "lt_memory_seq.h")  # a header of its own: the two memories over a whole rollout, forward and backward
 MEMORY_GRU_HEADER = os.path.join(REPO, "include", "lt_memory_gru.h")  # a header of its own: GRU memories, one rollout step and whole rollouts
+POLICY_HEADER = os.path.join(REPO, "include", "lt_policy.h")  # a header of its own: one inference step of a recurrent policy
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -222,6 +223,19 @@ if (not MEMORY_GRU_VALUE_QUERIES <= set(MEMORY_GRU_SIGNATURES) or any(r is not c
     raise ImportError("_abi.MEMORY_GRU_VALUE_QUERIES does not match include/lt_memory_gru.h, or an entry point there returns no int or "
                       "repeats one of another header")
 
+# include/lt_policy.h (not included by lt_env.h): constants and two structures of its own (lt_mlp_desc is lt_env.h's); POLICY_VALUE_QUERIES
+# is to this header what VALUE_QUERIES is to lt_env.h
+POLICY_CONSTS, _policy_structs, POLICY_SIGNATURES = parse_header(open(POLICY_HEADER).read(), structs=STRUCTS)
+globals().update(POLICY_CONSTS)
+LtPolicyDesc, LtPolicyMemory = _policy_structs["lt_policy_desc"], _policy_structs["lt_policy_memory"]
+POLICY_VALUE_QUERIES = frozenset({"lt_policy_step_launches"})
+if (not POLICY_VALUE_QUERIES <= set(POLICY_SIGNATURES) or any(r is not ctypes.c_int for r, _ in POLICY_SIGNATURES.values())
+        or set(POLICY_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
+                                     | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES)
+                                     | set(MEMORY_SIGNATURES) | set(MEMORY_SEQ_SIGNATURES) | set(MEMORY_GRU_SIGNATURES))):
+    raise ImportError("_abi.POLICY_VALUE_QUERIES does not match include/lt_policy.h, or an entry point there returns no int or repeats "
+                      "one of another header")
+
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
@@ -237,11 +251,11 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES, **LEDGER_SIGNATURES,
                                       **CNN_TRAIN_SIGNATURES, **BC_SIGNATURES, **LSTM_SIGNATURES, **MEMORY_SIGNATURES,
-                                      **MEMORY_SEQ_SIGNATURES, **MEMORY_GRU_SIGNATURES}.items():
+                                      **MEMORY_SEQ_SIGNATURES, **MEMORY_GRU_SIGNATURES, **POLICY_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
         if (name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES and name not in CNN_TRAIN_VALUE_QUERIES
-                and name not in MEMORY_SEQ_VALUE_QUERIES and name not in MEMORY_GRU_VALUE_QUERIES):
+                and name not in MEMORY_SEQ_VALUE_QUERIES and name not in MEMORY_GRU_VALUE_QUERIES and name not in POLICY_VALUE_QUERIES):
             _calls[name] = (fn, [ptr if t is ctypes.c_void_p else _ref if issubclass(t, ctypes._Pointer) and issubclass(t._type_, ctypes.Structure)
                                  else None for t in argtypes])
     if lib.lt_cfg_sizeof() != ctypes.sizeof(LtCfg):
@@ -283,7 +297,7 @@ def call(name: str, *args) -> None:
         fn, conv = _calls[name]
     except KeyError:
         if (name in VALUE_QUERIES or name in STUDENT_VALUE_QUERIES or name in CNN_TRAIN_VALUE_QUERIES or name in MEMORY_SEQ_VALUE_QUERIES
-                or name in MEMORY_GRU_VALUE_QUERIES):
+                or name in MEMORY_GRU_VALUE_QUERIES or name in POLICY_VALUE_QUERIES):
             raise TypeError(f"{name} returns a value, not a status: call load().{name}(...)") from None
         if _lib is not None:
             raise

@@ -630,15 +630,45 @@ class RslRlVecEnvWrapper:
         return getattr(self.env.unwrapped, name)
 
 
+class _FrozenNormalizer(torch.nn.Module):
+    """`EmpiricalNormalization` in evaluation mode with its statistics frozen: the same three ops on the same buffers (`_mean`, `_std`),
+    without the running update, which is not scriptable and which a deployed policy never runs."""
+
+    __constants__ = ["eps"]
+
+    def __init__(self, normalizer):
+        super().__init__()
+        self.eps = float(normalizer.eps)
+        self.register_buffer("_mean", normalizer._mean.detach().cpu().clone())
+        self.register_buffer("_std", normalizer._std.detach().cpu().clone())
+
+    def forward(self, x):
+        return (x - self._mean) / (self._std + self.eps)
+
+
 class _PolicyExport(torch.nn.Module):
-    """Deployment module of `export_policy_as_jit` / `_onnx` [DEP isaaclab_rl.rsl_rl.exporter]: normaliser -> actor."""
+    """Deployment module of `export_policy_as_jit` / `_onnx` [DEP isaaclab_rl.rsl_rl.exporter]: normaliser -> actor, and for a recurrent
+    policy normaliser -> one rnn step on the module's own state -> actor.  The recurrent form is what IsaacLab's exporter writes: a plain
+    `nn.LSTM` / `nn.GRU` (attribute `rnn`), buffers `hidden_state` (and `cell_state` for an LSTM) of shape [layers][1][H] that `forward`
+    advances, and an exported `reset()`; it is fed one row at a time.  `is_recurrent` / `is_lstm` are compile-time constants of the
+    scripted module: the branch that is not taken is not compiled."""
+
+    __constants__ = ["is_recurrent", "is_lstm"]
 
     def __init__(self, actor_critic, normalizer=None):
         super().__init__()
         import copy
 
-        if getattr(actor_critic, "is_recurrent", False):
-            raise NotImplementedError("recurrent actor export is not implemented (no registered LocoTouch task trains one)")
+        self.is_recurrent = bool(getattr(actor_critic, "is_recurrent", False))
+        self.is_lstm = False
+        if self.is_recurrent:
+            src = actor_critic.memory_a.rnn
+            self.is_lstm = isinstance(src, torch.nn.LSTM)
+            self.rnn = type(src)(input_size=src.input_size, hidden_size=src.hidden_size, num_layers=src.num_layers)
+            self.rnn.load_state_dict({k: v.detach().cpu() for k, v in src.state_dict().items()})
+            self.register_buffer("hidden_state", torch.zeros(src.num_layers, 1, src.hidden_size))
+            if self.is_lstm:
+                self.register_buffer("cell_state", torch.zeros(src.num_layers, 1, src.hidden_size))
         layers = []  # plain nn.Sequential of plain nn.Linear (rl/linear.py's training-time nodes are not scriptable)
         for m in copy.deepcopy(actor_critic.actor).cpu():
             if isinstance(m, torch.nn.Linear) and type(m) is not torch.nn.Linear:
@@ -647,10 +677,30 @@ class _PolicyExport(torch.nn.Module):
                 m = lin
             layers.append(m)
         self.actor = torch.nn.Sequential(*layers)
-        self.normalizer = copy.deepcopy(normalizer).cpu() if normalizer is not None else torch.nn.Identity()
+        if all(hasattr(normalizer, k) for k in ("_mean", "_std", "eps")):  # rl/normalizer.py's, or the reference's of the same names
+            self.normalizer = _FrozenNormalizer(normalizer)
+        else:
+            self.normalizer = copy.deepcopy(normalizer).cpu() if normalizer is not None else torch.nn.Identity()
 
     def forward(self, x):
-        return self.actor(self.normalizer(x))
+        x = self.normalizer(x)
+        if self.is_recurrent:
+            if self.is_lstm:
+                x, (h, c) = self.rnn(x.unsqueeze(0), (self.hidden_state, self.cell_state))
+                self.hidden_state[:] = h
+                self.cell_state[:] = c
+            else:
+                x, h = self.rnn(x.unsqueeze(0), self.hidden_state)
+                self.hidden_state[:] = h
+            x = x.squeeze(0)
+        return self.actor(x)
+
+    @torch.jit.export
+    def reset(self):
+        if self.is_recurrent:
+            self.hidden_state[:] = 0.0
+            if self.is_lstm:
+                self.cell_state[:] = 0.0
 
 
 def export_policy_as_jit(actor_critic, normalizer=None, path: str = ".", filename: str = "policy.pt") -> str:
@@ -672,6 +722,9 @@ def export_policy_as_onnx(actor_critic, path: str = ".", normalizer=None, filena
                           "export_policy_as_jit writes the same network as TorchScript") from e
     os.makedirs(path, exist_ok=True)
     mod = _PolicyExport(actor_critic, normalizer).eval()
+    if mod.is_recurrent:
+        raise NotImplementedError("export_policy_as_onnx: a recurrent policy keeps its state in the module, which an ONNX graph cannot; "
+                                  "export_policy_as_jit writes it as TorchScript")
     out = os.path.join(path, filename)
     n_in = mod.actor[0].in_features
     torch.onnx.export(mod, torch.zeros(1, n_in), out, export_params=True, opset_version=11, verbose=verbose, input_names=["obs"],

@@ -1,82 +1,15 @@
 // The two LSTM memories of a recurrent policy: one rollout step of both in one launch (include/lt_memory.h), and both over a whole
 // rollout of an env block, forward and backward (include/lt_memory_seq.h).  The kernels are lt_memory_tile.h's row-block skeleton with
-// the LSTM cell below: this file holds the cell, the checks of its argument structs and the entry points.
+// the LSTM cell of lt_memory_cells.h: this file holds the checks of its argument structs and the entry points.
 //
 // Step kernel: a unit's four panel rows are its gates i, f, g, o (PyTorch's order), each [W_ih row | W_hh row]; the state is (h, c) and
 // the epilogue's operand is c.  TRAIN stores the activated gates.  Backward: K = 4H, the carry is dc_t * f_t.
 #include "lt_memory.h"
+#include "lt_memory_cells.h"
 #include "lt_memory_seq.h"
 #include "lt_memory_tile.h"
 
 namespace {
-
-struct LstmCell {
-  static constexpr int NS = 2;  // h, c
-  static constexpr int KG = 4;
-  static __device__ __forceinline__ int ih_gate(int v) { return v; }
-  static __device__ __forceinline__ int hh_gate(int v) { return v; }
-  static __device__ __forceinline__ bool ih_used(int) { return true; }
-  static __device__ __forceinline__ bool hh_used(int) { return true; }
-  static __device__ __forceinline__ void load_bias(const float* b_ih, const float* b_hh, int H, int j0, int qm, int mt, float* bias) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int wrow = v * H + j0 + qm + mt;
-      bias[v] = b_ih[wrow] + b_hh[wrow];
-    }
-  }
-  // next = (h', c'), act = the activated gates i, f, g, o
-  static __device__ __forceinline__ void gates(const f32x4& sum, const float* bias, float cp, float* next, float* act) {
-    const float gi = sigmoidf_(sum[0] + bias[0]);
-    const float gf = sigmoidf_(sum[1] + bias[1]);
-    const float gg = tanhf_(sum[2] + bias[2]);
-    const float go = sigmoidf_(sum[3] + bias[3]);
-    next[1] = gf * cp + gi * gg;
-    next[0] = go * tanhf_(next[1]);
-    act[0] = gi; act[1] = gf; act[2] = gg; act[3] = go;
-  }
-
-  struct BwdNet {
-    const float* w_hh; const float* dg_next; const float* dout; const float* cell; const float* gates; const float* c_prev;
-    float* dg; float* carry;
-  };
-  // The gate gradients of four consecutive units of one row (lt_lstm.hip's formula; tanh(c_t) recomputed): reads gates / cell / c_prev /
-  // dout at element offset o of [E][H] (gates: row * 4H + unit), writes dgates and the new carry dc_t * f_t.
-  struct GradOps { f32x4 dout, ct, cp, g[4]; };
-
-  static __device__ __forceinline__ GradOps load_grad_ops(const BwdNet& p, long long row, int unit, int H) {
-    GradOps e;
-    const long long o = row * H + unit;
-    e.dout = *(const f32x4*)(p.dout + o);
-    e.ct = *(const f32x4*)(p.cell + o);
-    e.cp = *(const f32x4*)(p.c_prev + o);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) e.g[v] = *(const f32x4*)(p.gates + row * 4 * H + v * H + unit);
-    return e;
-  }
-
-  // the GEMM's sum and the dc carry are masked separately and enter at different places
-  static __device__ __forceinline__ void store_gate_grads(const BwdNet& p, long long row, int unit, int H, const GradOps& e, f32x4 dh_next, f32x4 dc_in,
-                                                          bool done) {
-    if (done) dh_next = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 d[4], dc;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const float dh = e.dout[v] + dh_next[v];
-      const float tc = tanhf_(e.ct[v]);
-      const float gi = e.g[0][v], gf = e.g[1][v], gg = e.g[2][v], go = e.g[3][v];
-      const float dcv = dc_in[v] + dh * go * (1.f - tc * tc);
-      d[0][v] = dcv * gg * gi * (1.f - gi);
-      d[1][v] = dcv * e.cp[v] * gf * (1.f - gf);
-      d[2][v] = dcv * gi * (1.f - gg * gg);
-      d[3][v] = dh * tc * go * (1.f - go);
-      dc[v] = dcv * gf;
-    }
-    float* g = p.dg + row * 4 * H + unit;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) *(f32x4*)(g + v * H) = d[v];
-    *(f32x4*)(p.carry + row * H + unit) = dc;
-  }
-};
 
 int check_net(const char* fn, const char* who, const lt_memory_net* n, int H) {
   if (const int rc = check_net_head(fn, who, n, H)) return rc;

@@ -1,6 +1,6 @@
 // The two GRU memories of a recurrent policy: one rollout step of both in one launch, and both over a whole rollout of an env block,
 // forward and backward (include/lt_memory_gru.h).  The GRU counterpart of lt_memory.hip: the kernels are lt_memory_tile.h's row-block
-// skeleton with the GRU cell below; this file holds the cell, the checks of its argument structs and the entry points.
+// skeleton with the GRU cell of lt_memory_cells.h; this file holds the checks of its argument structs and the entry points.
 //
 // Step kernel.  The n gate needs its x part and its h part as SEPARATE sums (b_hn sits inside r * (...)), so a unit again has four
 // panel rows:
@@ -10,76 +10,11 @@
 // 4 g + v: three rows per unit do not divide it) and the epilogue through LDS.  The state is h alone; TRAIN stores r, z, n and hn.
 //
 // Backward: K = 3H, dh = dhg[t+1] W_hh (3H / 16 k blocks are whole groups of four); the carry is dh * z.
+#include "lt_memory_cells.h"
 #include "lt_memory_gru.h"
 #include "lt_memory_tile.h"
 
 namespace {
-
-struct GruCell {
-  static constexpr int NS = 1;  // h
-  static constexpr int KG = 3;
-  static __device__ __forceinline__ int ih_gate(int v) { return v; }
-  static __device__ __forceinline__ int hh_gate(int v) { return v == 3 ? 2 : v; }
-  static __device__ __forceinline__ bool ih_used(int v) { return v < 3; }
-  static __device__ __forceinline__ bool hh_used(int v) { return v != 2; }
-  // b_ir + b_hr, b_iz + b_hz, b_in, b_hn
-  static __device__ __forceinline__ void load_bias(const float* b_ih, const float* b_hh, int H, int j0, int qm, int mt, float* bias) {
-    const int unit = j0 + qm + mt;
-    bias[0] = b_ih[unit] + b_hh[unit];
-    bias[1] = b_ih[H + unit] + b_hh[H + unit];
-    bias[2] = b_ih[2 * H + unit];
-    bias[3] = b_hh[2 * H + unit];
-  }
-  // next = (h'), act = r, z, n, hn
-  static __device__ __forceinline__ void gates(const f32x4& sum, const float* bias, float hp, float* next, float* act) {
-    const float gr = sigmoidf_(sum[0] + bias[0]);
-    const float gz = sigmoidf_(sum[1] + bias[1]);
-    const float hn = sum[3] + bias[3];
-    const float gn = tanhf_(sum[2] + bias[2] + gr * hn);
-    next[0] = (1.f - gz) * gn + gz * hp;
-    act[0] = gr; act[1] = gz; act[2] = gn; act[3] = hn;
-  }
-
-  struct BwdNet {
-    const float* w_hh; const float* dg_next; const float* dout; const float* gates; const float* h_prev;
-    float* dig; float* dhg; float* carry;  // dg_next: dhg of step t + 1
-  };
-  struct GradOps { f32x4 dout, hp, g[4]; };  // g: r, z, n, hn
-
-  static __device__ __forceinline__ GradOps load_grad_ops(const BwdNet& p, long long row, int unit, int H) {
-    GradOps e;
-    const long long o = row * H + unit;
-    e.dout = *(const f32x4*)(p.dout + o);
-    e.hp = *(const f32x4*)(p.h_prev + o);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) e.g[v] = *(const f32x4*)(p.gates + row * 4 * H + v * H + unit);
-    return e;
-  }
-
-  // the gate gradients of four consecutive units of one row; what comes back is where(done, 0, dhg[t+1] W_hh + carry): the carry joins
-  // the GEMM's sum first, then the mask
-  static __device__ __forceinline__ void store_gate_grads(const BwdNet& p, long long row, int unit, int H, const GradOps& e, f32x4 sum, f32x4 carry_in,
-                                                          bool done) {
-    f32x4 back = sum + carry_in;
-    if (done) back = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 dr, dz, dn, dnr, carry;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const float dh = e.dout[v] + back[v];
-      const float gr = e.g[0][v], gz = e.g[1][v], gn = e.g[2][v], hn = e.g[3][v];
-      dn[v] = dh * (1.f - gz) * (1.f - gn * gn);
-      dz[v] = dh * (e.hp[v] - gn) * gz * (1.f - gz);
-      dr[v] = dn[v] * hn * gr * (1.f - gr);
-      dnr[v] = dn[v] * gr;
-      carry[v] = dh * gz;
-    }
-    float* gi = p.dig + row * 3 * H + unit;
-    float* gh = p.dhg + row * 3 * H + unit;
-    *(f32x4*)gi = dr; *(f32x4*)(gi + H) = dz; *(f32x4*)(gi + 2 * H) = dn;
-    *(f32x4*)gh = dr; *(f32x4*)(gh + H) = dz; *(f32x4*)(gh + 2 * H) = dnr;
-    *(f32x4*)(p.carry + row * H + unit) = carry;
-  }
-};
 
 int check_net(const char* fn, const char* who, const lt_memory_gru_net* n, int H) {
   if (const int rc = check_net_head(fn, who, n, H)) return rc;

@@ -4,7 +4,7 @@
 //                    of w_ih / w_hh panel row kind v = 0..3 of a unit holds) and ih_used(v) / hh_used(v) (false: that side of the row
 //                    is zeros), load_bias, gates (the epilogue's arithmetic)
 //   backward kernel  KG (K = KG H gate columns), BwdNet (with the fields w_hh, dg_next, carry), GradOps, load_grad_ops, store_gate_grads
-// Internal to those two translation units: everything is in an unnamed namespace, as it was in each of them.
+// The two cells live in lt_memory_cells.h.  Internal to the translation units that include it: everything is in an unnamed namespace.
 //
 // Step kernel.  Shape: B = num_envs rows (4096 and up), K = I + H (observation width + hidden size), four panel rows per hidden unit, two
 // networks.  lt_lstm.hip's step kernel is laid out for the update (B ~ 47: a 16 x 16 tile per workgroup, weights streamed once per tile);

@@ -270,10 +270,18 @@ class OnPolicyRunner:
     def get_backbone_weights(self):  # :463-464 (RMA distillation: the teacher's actor becomes the student's frozen backbone)
         return self.alg.actor_critic.actor.state_dict()
 
-    def get_inference_policy(self, device=None):  # reference on_policy_runner.py:424-436
+    def get_inference_policy(self, device=None, fused=False):  # reference on_policy_runner.py:424-436
+        """`fused=True` with a recurrent policy: the opt-in front of rl/fused_policy.py (one memory launch and one actor launch per
+        step, the normaliser folded into the first); it raises for what the kernels do not serve.  Everything else is the reference's."""
         self.eval_mode()
         if device is not None:
             self.alg.actor_critic.to(device)
+        if fused and getattr(self.alg.actor_critic, "is_recurrent", False):
+            from .fused_policy import FusedRecurrentPolicy
+
+            if self.empirical_normalization and device is not None:
+                self.obs_normalizer.to(device)
+            return FusedRecurrentPolicy.for_actor_critic(self.alg.actor_critic, self.obs_normalizer if self.empirical_normalization else None)
         policy = self.alg.actor_critic.act_inference
         if self.empirical_normalization:
             if device is not None:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Play a trained policy: the reference's `locotouch/scripts/play.py` flow on the MI355X-native env: the loop steps the policy, prints
-episode statistics, optionally exports the actor as TorchScript for the robot-side runtime, and with `--video` records env 0 (animated
-PNG, locotouch_amd/video.py) into <run>/videos/play.
+episode statistics, optionally exports the actor (with its memory, for a recurrent policy) as TorchScript for the robot-side runtime,
+with `--fused_policy` serves a recurrent policy from the fused HIP inference step (include/lt_policy.h), and with `--video` records env 0 (animated
+PNG, locotouch_amd/video.py) into <run>/videos/play.  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
+`policy` and `empirical_normalization` entries take the place of the registered agent cfg's, so a recurrent checkpoint loads.
 
     python -m locotouch_amd.scripts.play --task Isaac-RandCylinderTransportTeacher-LocoTouch-Play-v1 --num_envs 50 --steps 1000 --export
 """
@@ -25,6 +27,8 @@ def main() -> None:
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--steps", type=int, default=None, help="stop after this many env steps (default: run until interrupted)")
     ap.add_argument("--export", action="store_true", help="write <run>/exported/policy.pt (TorchScript: normaliser -> actor)")
+    ap.add_argument("--fused_policy", action="store_true",
+                    help="recurrent policies: step through the fused HIP inference step (rl/fused_policy.py) and reset the memory of finished envs")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -40,12 +44,22 @@ def main() -> None:
     print(f"[INFO] Loading experiment from directory: {root}")
     resume = args.checkpoint if (args.checkpoint and os.path.isfile(args.checkpoint)) else get_checkpoint_path(
         root, args.load_run or ".*", args.checkpoint or "model_.*.pt")
+    # the run's own record of what was trained (scripts/train.py `dump_params`): a policy class or normaliser switch that differs from
+    # the registered agent cfg - a recurrent teacher - is played as it was trained
+    params = os.path.join(os.path.dirname(resume), "params", "agent.yaml")
+    if os.path.isfile(params):
+        import yaml
+
+        with open(params) as f:
+            trained = yaml.safe_load(f) or {}
+        agent.update({k: trained[k] for k in ("policy", "empirical_normalization") if k in trained})
     torch.cuda.set_device(args.device)
     env = make(args.task, num_envs=args.num_envs, device=args.device, seed=args.seed if args.seed is not None else agent["seed"])
     runner = OnPolicyRunner(env, agent, log_dir=None, device=args.device)
     print(f"[INFO]: Loading model checkpoint from: {resume}")
     runner.load(resume)
-    policy = runner.get_inference_policy(device=args.device)
+    policy = runner.get_inference_policy(device=args.device, fused=True) if args.fused_policy else runner.get_inference_policy(device=args.device)
+    reset_memory = args.fused_policy and hasattr(policy, "reset")
     if args.export:
         out = export_policy_as_jit(runner.alg.actor_critic, runner.obs_normalizer if runner.empirical_normalization else None,
                                    path=os.path.join(os.path.dirname(resume), "exported"), filename="policy.pt")
@@ -61,9 +75,11 @@ def main() -> None:
         with torch.inference_mode():
             while args.steps is None or t < args.steps:
                 obs, rew, dones, _ = env.step(policy(obs))
+                if reset_memory:
+                    policy.reset(dones)
                 ret_sum += rew
                 t += 1
-                if t % 200 == 0:
+                if t % 200 == 0 or t == args.steps:  # (a run of --steps ends on a statistics line)
                     log = env.episode_log()
                     print(f"[play] step {t}: " + ", ".join(f"{k}={v:.3f}" for k, v in sorted(log.items()) if k.startswith(("Episode/", "Metrics/"))))
     finally:
