@@ -510,11 +510,15 @@ int lt_head_wgrad_nblk(int64_t M);
 int64_t lt_adam_clip_step_ws_floats(int64_t n);
 /* GRU recurrence of the student's tactile encoder over a padded batch of whole trajectories (reference
  * loco_rl/loco_rl/models/memory_module.py:10-14 -> nn.GRU, single layer; locotouch/distill/student.py:119-123 trains it on
- * (L, B, .) batches).  One launch per time step whose grid covers the chip (csrc/lt_gru.hip); the time loop runs here.
+ * (L, B, .) batches).  One launch per time step whose grid covers the chip (csrc/lt_gru.hip on csrc/lt_seq_tile.h's kernels, shared
+ * with lt_lstm_*); the time loop runs here.
  *   forward : ig [L][B][3H] = X W_ih^T (no bias), h0 [B][H]  ->  out [L][B][H], ws [L][B][4H] (r, z, n, W_hn h + b_hn)
- *   backward: dout [L][B][H], dhn [B][H] | NULL  ->  dig, dhg [L][B][3H] (gate gradients, input / hidden side), dh0 [B][H];
- *             scratch [3][B][H].  The caller forms dW_hh = dhg^T H_prev, dW_ih = dig^T X, dX = dig W_ih and the bias sums.
- * Gate order and formulas are PyTorch's (r, z, n).  H must be a multiple of 64.  Device pointers, f32. */
+ *   backward: dout [L][B][H], dhn [B][H] | NULL (= 0)  ->  dig, dhg [L][B][3H] (gate gradients, input / hidden side), dh0 [B][H];
+ *             scratch [B][H] (a larger buffer stays valid).  The caller forms dW_hh = dhg^T H_prev, dW_ih = dig^T X, dX = dig W_ih
+ *             and the bias sums.
+ * Gate order and formulas are PyTorch's (r, z, n).  Device pointers, f32, every one 16-byte aligned (the kernels move float4s) and,
+ * dhn apart, non-null; L >= 1, B in [1, 16 * 65535], H a multiple of 64.  Anything else is refused by name (LT_EINVAL,
+ * "<function>: invalid argument: <what> must be ...") before a launch. */
 int lt_gru_forward(const float* ig, const float* h0, const float* w_hh, const float* b_ih, const float* b_hh, int L, int B, int H,
                    float* out, float* ws, void* stream);
 int lt_gru_backward(const float* dout, const float* dhn, const float* out, const float* ws, const float* h0, const float* w_hh, int L, int B,

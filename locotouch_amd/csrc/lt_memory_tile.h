@@ -24,7 +24,7 @@
 // pre-step state of their row block into the storage slot (`saved_hidden_states`).
 //
 // Arithmetic: v_mfma_f32_16x16x4_f32, exact f32 products, f32 accumulation, k blocks in index order (x side first, then h) dealt to four
-// partial sums that are added pairwise: one fixed order, no atomics.  Operand trick as lt_lstm.hip: MFMA step s of a 16-wide k block
+// partial sums that are added pairwise: one fixed order, no atomics.  Operand trick as lt_seq_tile.h: MFMA step s of a 16-wide k block
 // consumes the k-set {kb + 4 q + s}, so lane (i, q) supplies component s of ONE 16-byte load.
 #pragma once
 
@@ -36,6 +36,7 @@
 
 #include "lt_device_prims.h"
 #include "lt_env.h"
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 namespace {
@@ -333,27 +334,7 @@ __global__ __launch_bounds__(256) void lt_memory_seq_bwd_kernel(const BwdArgs<Ce
   }
 }
 
-// ---- host side: validation before anything is launched --------------------------------------------------------------------------------
-int refuse(const char* fn, const char* who, const char* field, const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: invalid argument: %s%s must be %s", fn, who, field, what);
-  lt_set_error(msg);
-  return LT_EINVAL;
-}
-
-struct ptr_check { const char* name; const void* p; int align; };
-
-int check_ptr(const char* fn, const char* who, const ptr_check& e) {
-  if (!e.p || (uintptr_t)e.p % e.align != 0) return refuse(fn, who, e.name, e.align == 16 ? "non-null and 16-byte aligned" : "non-null and 4-byte aligned");
-  return LT_OK;
-}
-
-template <int n> int check_ptrs(const char* fn, const char* who, const ptr_check (&ptrs)[n]) {
-  for (const auto& e : ptrs)
-    if (const int rc = check_ptr(fn, who, e)) return rc;
-  return LT_OK;
-}
-
+// ---- host side: validation before anything is launched (refuse, check_ptr(s), launch_status: lt_host_check.h) -------------------------
 int check_sizes(const char* fn, const char* rows, int N, int H) {
   if (N < 1 || N > 16 * 65535) return refuse(fn, "", rows, "in [1, 16 * 65535]");
   if (H < 64 || H > 512 || (H % 64) != 0) return refuse(fn, "", "H", "a multiple of 64 in [64, 512]");
@@ -422,12 +403,6 @@ int bwd_units(int E, int H, int panel_stride) {
 int bwd_units_or_zero(int E, int H, int KG) {
   if (E < 1 || E > 16 * 65535 || H < 64 || H > 512 || (H % 64) != 0) return 0;
   return bwd_units(E, H, bwd_panel_stride(KG, H));
-}
-
-int launch_status() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
 }
 
 // ---- host side: launches ------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@
 //             the work would be the gather), for 215 k MACs per env.
 //   launch 2  lt_student_gru_kernel: grid (H / 64, row tiles of 16).  The tile's [x | h] rows are staged in LDS - the done mask
 //             zeroes h as it is read - and each of the four waves owns 16 hidden units: gates r, z and the two halves of n against
-//             [W_ih | W_hh] on v_mfma_f32_16x16x4_f32 (the operand trick of lt_gru.hip: MFMA step s of a 16-wide k block consumes
+//             [W_ih | W_hh] on v_mfma_f32_16x16x4_f32 (the operand trick of lt_seq_tile.h: MFMA step s of a 16-wide k block consumes
 //             k = kb + 4 q + s, one 16-byte load per four MFMAs), four accumulator chains per gate (independent MFMAs back to back,
 //             and a shorter rounding chain).  The gate arithmetic is the epilogue.  The new state goes to the scratch, NOT to h:
 //             the other seven workgroups of the row tile are still reading the old one.

@@ -131,7 +131,7 @@ class _GRUSequenceHip(torch.autograd.Function):
         dout = dout.contiguous()
         dig = x.new_empty(L, B, 3 * H)
         dhg = x.new_empty(L, B, 3 * H)
-        scratch = x.new_empty(3, B, H)
+        scratch = x.new_empty(B, H)
         dh0 = x.new_empty(B, H)
         dhn = dhn.contiguous() if dhn is not None else None
         _abi.call("lt_gru_backward", dout, dhn, out, ws, h0, w_hh, L, B, H, dig, dhg, scratch, dh0, _abi.stream(x.device))

@@ -99,8 +99,8 @@ RAGGED = [(1, 3, 8, 256), (2, 16, 8, 512), (7, 1, 5, 64), (20, 37, 64, 512), (33
 @pytest.mark.parametrize("L,B,I,H", RAGGED)
 def test_hip_lstm_kernels_on_ragged_shapes(L, B, I, H, hip_on):
     """Row counts that are not multiples of the 16-row tile, a single row, every compile-time hidden size and the generic form (192), and
-    the one- and two-step sequences where the backward recursion opens and closes at once (lt_lstm_step_bwd_gates ->
-    lt_lstm_step_bwd_fused).  Bound: 2e-4 of max(scale, 1) against nn.LSTM on the GPU, the bound of tests/test_rl_gru.py for the same
+    the one- and two-step sequences where the backward recursion opens and closes at once (lt_seq_step_bwd_open ->
+    lt_seq_step_bwd_fused, csrc/lt_seq_tile.h).  Bound: 2e-4 of max(scale, 1) against nn.LSTM on the GPU, the bound of tests/test_rl_gru.py for the same
     kernel plan on the same shapes.  The errors of both forms against a float64 nn.LSTM on the CPU are printed (DESIGN.md section 4
     records them)."""
     lstm, x, h0, c0, g, ref, got = _check("cuda:0", L, B, I, H, 2e-4, function=LS._LSTMSequenceHip)
