@@ -48,7 +48,14 @@ __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restric
         isg[a] = 1.f / sg;
         z[a] = (x - m) * isg[a];
         logp += -0.5f * z[a] * z[a] - __logf(sg) - kHalfLog2Pi;
-        kl += __logf(sg / os + 1.0e-5f) + (os * os + (om - m) * (om - m)) / (2.f * sg * sg) - 0.5f;
+        {
+          // The two sigmas are state-independent, so an error in sg / os is the SAME in every row and does not average out over the
+          // minibatch, and each action's KL is a small difference of terms ~0.1: with the library's -freciprocal-math quotients and
+          // __logf the mean KL sat 2 - 8 times further from float64 than plain float32 does (tests/test_hip_ppo_f64.py).  True
+          // divisions and logf here; the kernel waits on memory either way.
+#pragma clang fp reciprocal(off)
+          kl += logf(sg / os + 1.0e-5f) + (os * os + (om - m) * (om - m)) / (2.f * sg * sg) - 0.5f;
+        }
       }
     }
     const float advr = adv[src];
@@ -138,7 +145,7 @@ __global__ __launch_bounds__(64) void lt_ppo_finalize_kernel(const float* __rest
 // dz = da * elu'(z) with elu'(z) recovered from the OUTPUT a = elu(z): 1 for a > 0, a + alpha otherwise (PyTorch's own
 // `elu_backward(..., is_result=true)`), and db[n] = sum over rows of dz[., n] in the same pass.  A thread owns 4 adjacent columns
 // (one 16-byte load per operand and row); the 256 / (N / 4) row lanes of a block meet in LDS; per-block column sums go to `ws`
-// and a second, tiny launch adds them in a fixed order (deterministic, no float atomics).
+// and a second, tiny launch adds them in a fixed order (deterministic, no float atomics; lt_partial_sums_kernel below).
 constexpr int EB_ROWS = 48;  // rows per block: 512 blocks at 24 576 rows
 
 __global__ __launch_bounds__(256) void lt_elu_bwd_bias_kernel(const float* da, const float* __restrict__ a, long long M, int N, float alpha,
@@ -183,37 +190,11 @@ __global__ __launch_bounds__(256) void lt_elu_bwd_bias_kernel(const float* da, c
   }
 }
 
-// out[e] = sum over b < nblk of ws[b * stride + e], e < count, added in block order by 16 row lanes of 16 adjacent elements each
-// (a lane's loads are independent, so a block's latency is ~nblk / 16 loads deep, not nblk); elements >= split go to out1.
-__global__ __launch_bounds__(256) void lt_partial_sum_kernel(const float* __restrict__ ws, int nblk, long long stride, int count, int split,
-                                                             float* __restrict__ out0, float* __restrict__ out1) {
-  const int e = blockIdx.x * 16 + (threadIdx.x & 15), lane = threadIdx.x >> 4;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (e < count) {
-    int b = lane;
-    for (; b + 48 < nblk; b += 64) {
-      s0 += ws[(long long)b * stride + e];
-      s1 += ws[(long long)(b + 16) * stride + e];
-      s2 += ws[(long long)(b + 32) * stride + e];
-      s3 += ws[(long long)(b + 48) * stride + e];
-    }
-    for (; b < nblk; b += 16) s0 += ws[(long long)b * stride + e];
-  }
-  __shared__ float red[16][16];
-  red[lane][threadIdx.x & 15] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (lane == 0 && e < count) {
-    float t = 0.f;
-#pragma unroll
-    for (int l = 0; l < 16; ++l) t += red[l][threadIdx.x];
-    if (e < split) out0[e] = t;
-    else if (out1) out1[e - split] = t;
-  }
-}
-
-// Several such sums in ONE launch (the backward pass of both stacks leaves ~14 partial buffers - per-block bias sums of
-// lt_elu_bwd_bias_kernel / lt_head_wgrad_kernel and the split-K slabs of the weight-gradient GEMMs - whose sums were 14 launches of
-// ~5 us): job j owns blocks [first[j], first[j + 1]); a fixed order of additions per element (not lt_partial_sum_kernel's: see the kernel).
+// Ordered sums of partials, several in ONE launch: out[e] = sum over b < nblk of ws[b * stride + e], e < count; elements >= split go to
+// out1.  (The backward pass of both stacks leaves ~14 partial buffers - per-block bias sums of lt_elu_bwd_bias_kernel /
+// lt_head_wgrad_kernel and the split-K slabs of the weight-gradient GEMMs - whose sums were 14 launches of ~5 us.)  Job j owns blocks
+// [first[j], first[j + 1]); a fixed order of additions per element (see the kernel), the same whether a sum is one job of many or, as
+// the direct forms of lt_elu_backward_bias / lt_head_wgrad launch it, the only one: a caller gets the same bits either way.
 constexpr int SUM_MAX_JOBS = 24;
 struct SumJobs {
   const float* ws[SUM_MAX_JOBS];
@@ -287,6 +268,17 @@ __global__ __launch_bounds__(256) void lt_partial_sums_kernel(const SumJobs J) {
       else if (J.out1[j]) J.out1[j][ei - split] = o[i];
     }
   }
+}
+
+// One sum as a launch of its own
+void launch_one_sum(const float* ws, int nblk, long long stride, int count, int split, float* out0, float* out1, hipStream_t stream) {
+  SumJobs J = {};
+  J.njobs = 1;
+  J.ws[0] = ws; J.out0[0] = out0; J.out1[0] = out1; J.stride[0] = stride;
+  J.nblk[0] = nblk; J.count[0] = count; J.split[0] = split;
+  const int epb = 256 / sum_row_lanes(nblk) * 4;  // elements per block
+  J.first[1] = (count + epb - 1) / epb;
+  hipLaunchKernelGGL(lt_partial_sums_kernel, dim3((unsigned)J.first[1]), dim3(256), 0, stream, J);
 }
 
 // ---- weight + bias gradient of a narrow head layer -----------------------------------------------------------------------------------
@@ -454,6 +446,9 @@ __global__ __launch_bounds__(64) void lt_ppo_lr_rule_kernel(const float* __restr
   if (dstd_out && scalars && (int)threadIdx.x < A) dstd_out[threadIdx.x] = scalars[8 + threadIdx.x];  // d loss / d sigma_a -> the gradient bucket
   if (threadIdx.x != 0) return;
   if (kl_mean && desired > 0.f) {
+    // (the library is built with -freciprocal-math: v / factor would be v * rcp(factor), an ulp off the quotient for some rates; the
+    // rule is one correctly rounded division, the nearest float32 form of the reference's `learning_rate / 1.5`)
+#pragma clang fp reciprocal(off)
     const float kl = *kl_mean;
     float v = *lr;
     if (kl > desired * 2.f) v = fmaxf(lr_min, v / factor);
@@ -491,7 +486,7 @@ static int elu_backward_bias(const float* da, const float* a, int64_t M, int N, 
   }
   const int nblk = (int)((M + EB_ROWS - 1) / EB_ROWS);
   hipLaunchKernelGGL(lt_elu_bwd_bias_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, da, a, (long long)M, N, alpha, dz, ws, amax);
-  if (db) hipLaunchKernelGGL(lt_partial_sum_kernel, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, (hipStream_t)stream, ws, nblk, (long long)N, N, N, db, (float*)nullptr);
+  if (db) launch_one_sum(ws, nblk, (long long)N, N, N, db, nullptr, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
   return LT_OK;
@@ -525,7 +520,7 @@ extern "C" int lt_head_wgrad(const float* dy, const float* x, int x_split, int64
     case 12: hipLaunchKernelGGL(lt_head_wgrad_kernel<12>, g, b, lds, st, dy, x, x_split, (long long)M, n, k, ws); break;
     default: hipLaunchKernelGGL(lt_head_wgrad_kernel<16>, g, b, lds, st, dy, x, x_split, (long long)M, n, k, ws); break;
   }
-  if (dw) hipLaunchKernelGGL(lt_partial_sum_kernel, dim3((unsigned)((n * k + n + 15) / 16)), b, 0, st, ws, nblk, (long long)n * k + HW_MAX_N, n * k + n, n * k, dw, db);
+  if (dw) launch_one_sum(ws, nblk, (long long)n * k + HW_MAX_N, n * k + n, n * k, dw, db, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
   return LT_OK;

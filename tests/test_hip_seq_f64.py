@@ -18,12 +18,10 @@ import pytest
 import torch
 
 from tests import seq_ref as R
+from tests.guarded import DEV, GUARD, NAN_BITS
+from tests.guarded import guarded as _guarded
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-GUARD = 64               # floats on each side of every array
-NAN_BITS = 0x7FC0BEEF    # a quiet NaN with a payload no arithmetic produces
 
 # (L, B, H) -> what it reaches in lt_seq_tile.h
 SHAPES = [(1, 1, 64),      # generic form, one k-block per wave, one row; the opening and the closing backward launch meet
@@ -33,19 +31,6 @@ SHAPES = [(1, 1, 64),      # generic form, one k-block per wave, one row; the op
           (2, 33, 320),    # generic form above the largest small compile-time size
           (5, 33, 512)]    # KB = 8, the student's H; three row tiles
 CASES = ([(s, "plain") for s in SHAPES] + [((2, 17, 128), "saturated"), ((3, 15, 192), "saturated"), ((2, 17, 128), "null_carries")])
-
-
-def _guarded(shape, data=None):
-    """-> (the whole allocation as int32, the float32 view of `shape` in its middle)"""
-    n = 1
-    for s in shape:
-        n *= s
-    buf = torch.full((n + 2 * GUARD,), NAN_BITS, dtype=torch.int32, device=DEV)
-    view = buf[GUARD:GUARD + n].view(torch.float32).view(*shape)
-    assert view.data_ptr() % 16 == 0
-    if data is not None:
-        view.copy_(data)
-    return buf, view
 
 
 def _run_kernels(cell, case, carries):
