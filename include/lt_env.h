@@ -706,6 +706,9 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1_or_n
 /* ---- one rollout step of the two LSTM memories of a recurrent policy in one launch: lt_memory_* - declared in a header of their own,
  * part of this ABI. */
 #include "lt_memory.h"
+/* ---- the log-std policy and the per-minibatch advantage normalisation on the fused PPO path: lt_std_from_log, lt_ppo_loss_opts,
+ * lt_adv_stats - declared in a header of their own, part of this ABI. */
+#include "lt_ppo_opts.h"
 
 #ifdef __cplusplus
 }

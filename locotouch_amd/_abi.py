@@ -26,6 +26,7 @@ MEMORY_HEADER = os.path.join(REPO, "include", "lt_memory.h")  # included by lt_e
 MEMORY_SEQ_HEADER = os.path.join(REPO, "include", "lt_memory_seq.h")  # a header of its own: the two memories over a whole rollout, forward and backward
 MEMORY_GRU_HEADER = os.path.join(REPO, "include", "lt_memory_gru.h")  # a header of its own: GRU memories, one rollout step and whole rollouts
 POLICY_HEADER = os.path.join(REPO, "include", "lt_policy.h")  # a header of its own: one inference step of a recurrent policy
+PPO_OPTS_HEADER = os.path.join(REPO, "include", "lt_ppo_opts.h")  # included by lt_env.h: the log-std policy and per-minibatch advantage statistics
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -236,6 +237,15 @@ if (not POLICY_VALUE_QUERIES <= set(POLICY_SIGNATURES) or any(r is not ctypes.c_
     raise ImportError("_abi.POLICY_VALUE_QUERIES does not match include/lt_policy.h, or an entry point there returns no int or repeats "
                       "one of another header")
 
+# include/lt_ppo_opts.h: all status-returning, launched through `call`
+PPO_OPTS_SIGNATURES = parse_header(open(PPO_OPTS_HEADER).read())[2]
+if (any(r is not ctypes.c_int for r, _ in PPO_OPTS_SIGNATURES.values())
+        or set(PPO_OPTS_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
+                                       | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES)
+                                       | set(MEMORY_SIGNATURES) | set(MEMORY_SEQ_SIGNATURES) | set(MEMORY_GRU_SIGNATURES)
+                                       | set(POLICY_SIGNATURES))):
+    raise ImportError("include/lt_ppo_opts.h: every entry point returns a status and none repeats one of another header")
+
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
 
@@ -251,7 +261,8 @@ def load() -> ctypes.CDLL:
     lib = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES, **LEDGER_SIGNATURES,
                                       **CNN_TRAIN_SIGNATURES, **BC_SIGNATURES, **LSTM_SIGNATURES, **MEMORY_SIGNATURES,
-                                      **MEMORY_SEQ_SIGNATURES, **MEMORY_GRU_SIGNATURES, **POLICY_SIGNATURES}.items():
+                                      **MEMORY_SEQ_SIGNATURES, **MEMORY_GRU_SIGNATURES, **POLICY_SIGNATURES,
+                                      **PPO_OPTS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
         if (name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES and name not in CNN_TRAIN_VALUE_QUERIES

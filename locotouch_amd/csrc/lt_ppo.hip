@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "lt_env.h"
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 namespace {
@@ -19,19 +20,34 @@ namespace {
 constexpr int MAX_A = 16;
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;
 
+// sigma of a log-std policy (actor_critic.py:109-112).  The ONE exponential of lt_std_from_log (what a rollout stores as sigma) and of
+// the loss kernel (what it compares that sigma against): the same bits from the same log_std.  Formed in float64 and rounded once: an
+// error in sigma is the same in every row and enters a row's log-prob times z^2 (64 at |z| = 8), so the ulp an f32 exponential may be
+// off by showed as 6.5e-6 of max |dmu| against float64 where the nearest float32 sigma gives 1e-6 (tests/test_hip_ppo_opts_f64.py).
+// A workgroup forms its A sigmas once (the loss kernel keeps them in LDS).
+__device__ __forceinline__ float lt_sigma_of_log(float log_std) { return (float)exp((double)log_std); }
+
 // acc layout: [0] sum surrogate, [1] sum value loss, [2] sum kl, [3] unused, [4 .. 4 + A) sum over rows of d surrogate / d sigma_a,
 // [20] max |dmu|, [21] max |dvalue| (bit patterns of non-negative floats, merged with an integer atomicMax: order-independent) - the
 // scales the backward chain brings the two gradients into f16's range with (lt_mlp_backward_pair)
+// LOG: stdp is log sigma, and slots [4 .. 4 + A) hold d surrogate / d LOG sigma_a.  NORM: the advantage enters as (adv - adv_stats[0]) *
+// adv_stats[1] (lt_adv_stats).  Both are compile-time: the <false, false> form is the kernel as it was.
+template <bool LOG, bool NORM>
 __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restrict__ mu, const float* __restrict__ stdp, const float* __restrict__ value,
                                                           const float* __restrict__ actions, const float* __restrict__ old_logp,
                                                           const float* __restrict__ adv, const float* __restrict__ returns,
                                                           const float* __restrict__ old_values, const float* __restrict__ old_mu,
                                                           const float* __restrict__ old_sigma, const long long* __restrict__ idx,
                                                           long long M, int A, float clip, float vcoef, int clipped_value,
-                                                          float* __restrict__ dmu, float* __restrict__ dvalue, float* __restrict__ acc) {
+                                                          const float* __restrict__ adv_stats, float* __restrict__ dmu, float* __restrict__ dvalue, float* __restrict__ acc) {
   const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
   const bool ok = row < M;
   const long long src = (ok && idx) ? idx[row] : row;  // row of the rollout storage this minibatch row was drawn from
+  __shared__ float sigma_lds[MAX_A];  // (LOG alone; unreferenced otherwise)
+  if constexpr (LOG) {
+    if ((int)threadIdx.x < A) sigma_lds[threadIdx.x] = lt_sigma_of_log(stdp[threadIdx.x]);
+    __syncthreads();
+  }
   float part[4 + MAX_A];
   float amax_mu = 0.f, amax_v = 0.f;
 #pragma unroll
@@ -43,11 +59,12 @@ __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restric
 #pragma unroll
     for (int a = 0; a < MAX_A; ++a) {
       if (a < A) {
-        const float sg = stdp[a], m = mu[row * A + a], x = actions[src * A + a];
+        const float sg = LOG ? sigma_lds[a] : stdp[a], m = mu[row * A + a], x = actions[src * A + a];
         const float om = old_mu[src * A + a], os = old_sigma[src * A + a];
         isg[a] = 1.f / sg;
         z[a] = (x - m) * isg[a];
-        logp += -0.5f * z[a] * z[a] - __logf(sg) - kHalfLog2Pi;
+        if constexpr (LOG) logp += -0.5f * z[a] * z[a] - stdp[a] - kHalfLog2Pi;  // log sigma is the parameter itself
+        else logp += -0.5f * z[a] * z[a] - __logf(sg) - kHalfLog2Pi;
         {
           // The two sigmas are state-independent, so an error in sg / os is the SAME in every row and does not average out over the
           // minibatch, and each action's KL is a small difference of terms ~0.1: with the library's -freciprocal-math quotients and
@@ -58,7 +75,8 @@ __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restric
         }
       }
     }
-    const float advr = adv[src];
+    float advr = adv[src];
+    if constexpr (NORM) advr = (advr - adv_stats[0]) * adv_stats[1];
     const float ratio = __expf(logp - old_logp[src]);
     const float s1 = -advr * ratio;
     const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
@@ -71,7 +89,8 @@ __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restric
       if (a < A) {
         dmu[row * A + a] = dlogp * z[a] * isg[a];
         amax_mu = fmaxf(amax_mu, fabsf(dlogp * z[a] * isg[a]));
-        part[4 + a] = dlogp * (z[a] * z[a] - 1.f) * isg[a];  // d logp / d sigma_a = ((x - mu)^2 / sigma^3 - 1 / sigma)
+        if constexpr (LOG) part[4 + a] = dlogp * (z[a] * z[a] - 1.f);  // d logp / d log sigma_a = sigma_a d logp / d sigma_a = z^2 - 1
+        else part[4 + a] = dlogp * (z[a] * z[a] - 1.f) * isg[a];  // d logp / d sigma_a = ((x - mu)^2 / sigma^3 - 1 / sigma)
       }
     }
     const float v = value[row], R = returns[src];
@@ -124,11 +143,16 @@ __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restric
 // The scalars of the minibatch loss from the sums of lt_ppo_loss_kernel (one wave, behind it on the stream): out[0] loss, [1] mean
 // surrogate, [2] mean value loss, [3] entropy, [4] mean KL, [8 + a] d loss / d sigma_a.  In PyTorch ops this was a dozen launches on
 // 12-float tensors.  entropy = sum_a (0.5 + 0.5 log 2 pi + log sigma_a) (the same in every row: the std is state-independent).
+// std_is_log (uniform): stdp is log sigma - the entropy's summand is the parameter itself, and its share of d loss / d log sigma_a is
+// -ecoef.
 __global__ __launch_bounds__(64) void lt_ppo_finalize_kernel(const float* __restrict__ acc, const float* __restrict__ stdp, int A, float inv_m,
-                                                             float vcoef, float ecoef, float* __restrict__ out) {
+                                                             float vcoef, float ecoef, int std_is_log, float* __restrict__ out) {
   const int a = threadIdx.x;
   float e = 0.f;
-  if (a < A) {
+  if (a < A && std_is_log) {
+    e = 0.5f + kHalfLog2Pi + stdp[a];
+    out[8 + a] = acc[4 + a] - ecoef;
+  } else if (a < A) {
     const float sg = stdp[a];
     e = 0.5f + kHalfLog2Pi + logf(sg);
     out[8 + a] = acc[4 + a] - ecoef / sg;
@@ -435,6 +459,44 @@ __global__ __launch_bounds__(256) void lt_adam_kernel(float* __restrict__ p, flo
   }
 }
 
+// std[a] = sigma of log_std[a]: one wave, once per rollout (rl/fused.py), so that the policy launches read a sigma as they do for the
+// scalar std.
+__global__ __launch_bounds__(64) void lt_std_from_log_kernel(const float* __restrict__ log_std, int A, float* __restrict__ stdp) {
+  if ((int)threadIdx.x < A) stdp[threadIdx.x] = lt_sigma_of_log(log_std[threadIdx.x]);
+}
+
+// Per-minibatch advantage statistics (ppo.py:223-225): workgroup b owns minibatch b.  A thread adds its rows (tid, tid + 256, ...) in
+// float64, the 256 partial sums meet by wave butterflies and four LDS slots - one fixed order, no atomics.  Pass 1 the mean, pass 2 the
+// squared deviations from the float64 mean; the unbiased std and 1 / (std + 1e-8f) are roundings of float64 values.
+__device__ __forceinline__ double lt_block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  __syncthreads();  // (red is reused by the second pass)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void lt_adv_stats_kernel(const float* __restrict__ adv, const long long* __restrict__ idx, long long M,
+                                                           float* __restrict__ stats) {
+#pragma clang fp reciprocal(off)  // (the library is built with -freciprocal-math: true divisions here)
+  __shared__ double red[4];
+  const long long base = (long long)blockIdx.x * M;
+  double s = 0.0;
+  for (long long r = threadIdx.x; r < M; r += 256) s += (double)adv[idx ? idx[base + r] : base + r];
+  const double mean = lt_block_sum_f64(s, red) / (double)M;
+  double q = 0.0;
+  for (long long r = threadIdx.x; r < M; r += 256) {
+    const double d = (double)adv[idx ? idx[base + r] : base + r] - mean;
+    q += d * d;
+  }
+  const double var = lt_block_sum_f64(q, red) / (double)(M - 1);
+  if (threadIdx.x == 0) {
+    stats[2 * blockIdx.x] = (float)mean;
+    stats[2 * blockIdx.x + 1] = (float)(1.0 / (sqrt(var) + (double)1.0e-8f));
+  }
+}
+
 // The adaptive learning-rate rule of the reference on the device (loco_rl/loco_rl/algorithms/ppo.py:273-281): one lane.
 //   kl > 2 desired -> lr = max(lr_min, lr / factor);   0 < kl < desired / 2 -> lr = min(lr_max, lr * factor)
 // `kl_mean`: the minibatch's mean KL (lt_ppo_loss's out[4]; all-reduced by the caller in a multi-rank job).  The host read of the KL
@@ -602,6 +664,31 @@ static int adam_clip_step(float* params, float* grads, float* exp_avg, float* ex
 
 extern "C" int64_t lt_adam_clip_step_ws_floats(int64_t n) { return (n + AD_PER_BLOCK - 1) / AD_PER_BLOCK; }
 
+// One body for lt_ppo_loss and lt_ppo_loss_opts (include/lt_ppo_opts.h), behind their own validation.
+static int ppo_loss(const float* mu, const float* stdp, const float* value, const float* actions, const float* old_logp,
+                    const float* adv, const float* returns, const float* old_values, const float* old_mu, const float* old_sigma,
+                    const int64_t* idx, int64_t M, int A, float clip, float value_loss_coef, float entropy_coef, int use_clipped_value_loss,
+                    int std_is_log, const float* adv_stats, float* dmu, float* dvalue, float* acc, float* out, void* stream) {
+  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * (4 + MAX_A + 4), (hipStream_t)stream);
+  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
+  const dim3 grid((unsigned)((M + 255) / 256));
+#define LT_PPO_LOSS_LAUNCH(LOG, NORM)                                                                                                      \
+  hipLaunchKernelGGL((lt_ppo_loss_kernel<LOG, NORM>), grid, dim3(256), 0, (hipStream_t)stream, mu, stdp, value, actions, old_logp, adv, returns, \
+                     old_values, old_mu, old_sigma, (const long long*)idx, (long long)M, A, clip, value_loss_coef, use_clipped_value_loss,   \
+                     adv_stats, dmu, dvalue, acc)
+  if (std_is_log && adv_stats) LT_PPO_LOSS_LAUNCH(true, true);
+  else if (std_is_log) LT_PPO_LOSS_LAUNCH(true, false);
+  else if (adv_stats) LT_PPO_LOSS_LAUNCH(false, true);
+  else LT_PPO_LOSS_LAUNCH(false, false);
+#undef LT_PPO_LOSS_LAUNCH
+  if (out)
+    hipLaunchKernelGGL(lt_ppo_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, stdp, A, 1.f / (float)M, value_loss_coef, entropy_coef,
+                       std_is_log ? 1 : 0, out);
+  e = hipGetLastError();
+  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
+  return LT_OK;
+}
+
 extern "C" int lt_ppo_loss(const float* mu, const float* stdp, const float* value, const float* actions, const float* old_logp, const float* adv,
                            const float* returns, const float* old_values, const float* old_mu, const float* old_sigma, const int64_t* idx,
                            int64_t M, int A, float clip, float value_loss_coef, float entropy_coef, int use_clipped_value_loss, float* dmu, float* dvalue,
@@ -611,12 +698,45 @@ extern "C" int lt_ppo_loss(const float* mu, const float* stdp, const float* valu
     lt_set_error("lt_ppo_loss: invalid argument (1 <= num_actions <= 16)");
     return LT_EINVAL;
   }
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * (4 + MAX_A + 4), (hipStream_t)stream);
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  hipLaunchKernelGGL(lt_ppo_loss_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mu, stdp, value, actions, old_logp, adv,
-                     returns, old_values, old_mu, old_sigma, (const long long*)idx, (long long)M, A, clip, value_loss_coef, use_clipped_value_loss, dmu, dvalue, acc);
-  if (out) hipLaunchKernelGGL(lt_ppo_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, stdp, A, 1.f / (float)M, value_loss_coef, entropy_coef, out);
-  e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return ppo_loss(mu, stdp, value, actions, old_logp, adv, returns, old_values, old_mu, old_sigma, idx, M, A, clip, value_loss_coef,
+                  entropy_coef, use_clipped_value_loss, 0, nullptr, dmu, dvalue, acc, out, stream);
+}
+
+extern "C" int lt_ppo_loss_opts(const float* mu, const float* stdp, const float* value, const float* actions, const float* old_logp,
+                                const float* adv, const float* returns, const float* old_values, const float* old_mu, const float* old_sigma,
+                                const int64_t* idx, int64_t M, int A, float clip, float value_loss_coef, float entropy_coef,
+                                int use_clipped_value_loss, int std_is_log, const float* adv_stats, float* dmu, float* dvalue, float* acc,
+                                float* out, void* stream) {
+  const char* fn = "lt_ppo_loss_opts";
+  const ptr_check ptrs[] = {{"mu", mu, 4}, {"std", stdp, 4}, {"value", value, 4}, {"actions", actions, 4}, {"old_logp", old_logp, 4}, {"adv", adv, 4},
+                            {"returns", returns, 4}, {"old_values", old_values, 4}, {"old_mu", old_mu, 4}, {"old_sigma", old_sigma, 4},
+                            {"dmu", dmu, 4}, {"dvalue", dvalue, 4}, {"acc", acc, 4}};
+  if (const int rc = check_ptrs(fn, "", ptrs)) return rc;
+  if ((uintptr_t)idx % 8 != 0) return refuse(fn, "", "idx", "NULL or 8-byte aligned");
+  if ((uintptr_t)adv_stats % 4 != 0) return refuse(fn, "", "adv_stats", "NULL or 4-byte aligned");
+  if ((uintptr_t)out % 4 != 0) return refuse(fn, "", "out", "NULL or 4-byte aligned");
+  if (M < 1) return refuse(fn, "", "M", ">= 1");
+  if (A < 1 || A > MAX_A) return refuse(fn, "", "A", "in [1, 16]");
+  return ppo_loss(mu, stdp, value, actions, old_logp, adv, returns, old_values, old_mu, old_sigma, idx, M, A, clip, value_loss_coef, entropy_coef,
+                  use_clipped_value_loss, std_is_log, adv_stats, dmu, dvalue, acc, out, stream);
+}
+
+extern "C" int lt_std_from_log(const float* log_std, int A, float* stdp, void* stream) {
+  const char* fn = "lt_std_from_log";
+  const ptr_check ptrs[] = {{"log_std", log_std, 4}, {"std", stdp, 4}};
+  if (const int rc = check_ptrs(fn, "", ptrs)) return rc;
+  if (A < 1 || A > MAX_A) return refuse(fn, "", "A", "in [1, 16]");
+  hipLaunchKernelGGL(lt_std_from_log_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, log_std, A, stdp);
+  return launch_status();
+}
+
+extern "C" int lt_adv_stats(const float* adv, const int64_t* idx, int64_t M, int nmb, float* stats, void* stream) {
+  const char* fn = "lt_adv_stats";
+  const ptr_check ptrs[] = {{"adv", adv, 4}, {"stats", stats, 4}};
+  if (const int rc = check_ptrs(fn, "", ptrs)) return rc;
+  if ((uintptr_t)idx % 8 != 0) return refuse(fn, "", "idx", "NULL or 8-byte aligned");
+  if (M < 2) return refuse(fn, "", "M", ">= 2 (the unbiased std of one element is NaN)");
+  if (nmb < 1) return refuse(fn, "", "nmb", ">= 1");
+  hipLaunchKernelGGL(lt_adv_stats_kernel, dim3((unsigned)nmb), dim3(256), 0, (hipStream_t)stream, adv, (const long long*)idx, (long long)M, stats);
+  return launch_status();
 }

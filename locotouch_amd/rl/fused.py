@@ -21,6 +21,10 @@ Observation normalisation (the runner's `empirical_normalization`, rl/normalizer
 still on the one stream.  The storage slots stay RAW during the rollout (the step kernel shifts its observation history from slot t
 to slot t + 1), `normalize_storage()` rewrites them in place through the per-slot snapshots before the update reads them.
 
+Log-type std (`ActorCritic(noise_std_type="log")`): the policy launches read sigma from a [12] buffer of this object, which ONE
+`lt_std_from_log` launch at the head of every rollout refreshes from `log_std` (include/lt_ppo_opts.h) - inside a captured region, so a
+replayed graph follows the optimizer.  The launches of a step are the same two.
+
 Recurrent policies (`ActorCriticRecurrent` with single-layer LSTM memories; the runner's `fused_recurrent_rollout`): a step is
     [lt_memory_step: both memories - reset mask of the previous step's dones, the pre-step state into the storage's
      `saved_hidden_states` slot t, the LSTM cell on the observation rows of slot t, new raw (h, c) into a ping-pong buffer]
@@ -106,8 +110,11 @@ class FusedRollout:
         if not isinstance(env, LocoTouchVecEnv):
             raise TypeError("FusedRollout drives a LocoTouchVecEnv (HIP env)")
         ac = alg.actor_critic
-        if getattr(ac, "noise_std_type", "scalar") != "scalar":
-            raise ValueError("FusedRollout supports the 'scalar' noise_std_type of the LocoTouch agent configs")
+        # noise_std_type="log": the policy launches read sigma from a buffer of this object, refreshed from `log_std` by one
+        # `lt_std_from_log` launch at the head of every rollout (inside a captured region: a replay sees the last update's log_std)
+        self._std_buf = torch.zeros(12, device=env.device) if getattr(ac, "noise_std_type", "scalar") == "log" else None
+        if self._std_buf is not None and ac.log_std.shape != (12,):
+            raise ValueError("FusedRollout: log_std must hold the env's 12 actions")
         # recurrent policy: the two LSTM memories run in one launch in front of the MLPs (csrc/lt_memory.hip)
         self.recurrent = bool(getattr(ac, "is_recurrent", False))
         self.gru = False  # GRU memories (opt-in `fused_gru_memories`): one state tensor per memory, csrc/lt_memory_gru.hip
@@ -348,10 +355,14 @@ class FusedRollout:
             obs, cobs = self.norm_rows
         self._policy_value(t, obs, cobs)
 
+    def _sigma(self) -> torch.Tensor:
+        """The state-independent sigma the policy launches read: the `std` parameter, or the buffer `rollout()` refreshed from `log_std`."""
+        return self.alg.actor_critic.std.data if self._std_buf is None else self._std_buf
+
     def _policy_value(self, t: int, obs, cobs) -> None:
         st = self.alg.storage
         _abi.call("lt_rollout_policy_value", self.actor_mlp.desc, self.actor_mlp.packed, obs, self.critic_mlp.desc, self.critic_mlp.packed,
-                  cobs, st.values[t], self.env.num_envs, self._noise_seed, self._act_counter, t, self.alg.actor_critic.std.data,
+                  cobs, st.values[t], self.env.num_envs, self._noise_seed, self._act_counter, t, self._sigma(),
                   st.actions[t], st.mu[t], st.sigma[t], st.actions_log_prob[t], self.actions, _abi.stream(self.device))
 
     def _step_packed(self, t: int, last: bool) -> None:
@@ -399,7 +410,7 @@ class FusedRollout:
             seen, cseen = self._memory_rows(t)
         mu = ac.actor(seen)
         rows = (None, None, None, None) if self.rows_in_storage else (obs, cobs, st.observations[t], st.privileged_observations[t])
-        _abi.call("lt_rollout_act", n, env.num_obs, self._noise_seed, self._act_counter, mu, ac.std.data, None, *rows,
+        _abi.call("lt_rollout_act", n, env.num_obs, self._noise_seed, self._act_counter, mu, self._sigma(), None, *rows,
                   st.actions[t], st.mu[t], st.sigma[t], None, st.actions_log_prob[t], self.actions, stream)
         self.side.wait_stream(main)
         with torch.cuda.stream(self.side):
@@ -425,6 +436,9 @@ class FusedRollout:
         main = torch.cuda.current_stream(self.device)
         with torch.inference_mode():
             self._act_counter.copy_(env.counters[:1])
+            if self._std_buf is not None:  # sigma = exp(log_std) as the optimizer left it: one launch per rollout (include/lt_ppo_opts.h)
+                log_std = self.alg.actor_critic.log_std.data
+                _abi.call("lt_std_from_log", log_std, log_std.numel(), self._std_buf, _abi.stream(self.device))
             if self.normalizers is not None:
                 self._snaps[0].copy_(self._carry)
             if self.actor_mlp is not None:  # the optimizer has stepped since the last rollout

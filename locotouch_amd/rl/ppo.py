@@ -127,8 +127,8 @@ class PPO:
     def _fused_loss_ok(self, b) -> bool:
         ac = self.actor_critic
         st = self.storage
-        return (self.fused_loss and st.observations.is_cuda and type(ac) is ActorCritic and getattr(ac, "noise_std_type", "scalar") == "scalar"
-                and st.actions.shape[-1] <= 16)
+        # (both noise_std_types: the loss kernel forms sigma from `std` or from `log_std`, include/lt_ppo_opts.h)
+        return self.fused_loss and st.observations.is_cuda and type(ac) is ActorCritic and st.actions.shape[-1] <= 16
 
     def _packed_pair(self):
         """PackedPair of the policy's two stacks (None: shapes the MLP kernel does not cover, or `packed_forward=False`)."""
@@ -157,27 +157,37 @@ class PPO:
         """The update of the plain ActorCritic on the GPU: per minibatch step two row gathers (obs, critic obs), the two MLPs,
         ONE loss launch that reads the seven small per-row tensors of the rollout storage through the minibatch index
         (csrc/lt_ppo.hip), backward, two launches of clip + Adam; one host read per step (the KL of the learning-rate rule,
-        ppo.py:273-281), the statistics once at the end.  Same arithmetic as the op chain below (tests/test_hip_ppo_graph.py)."""
-        from .fused_loss import fused_ppo_loss
+        ppo.py:273-281), the statistics once at the end.  Same arithmetic as the op chain below (tests/test_hip_ppo_graph.py).
+
+        A `noise_std_type="log"` policy passes `log_std` and takes its gradient back.  `normalize_advantage_per_mini_batch`: ONE
+        `lt_adv_stats` launch per update on the update's permutation (the reference reuses it in every epoch, so the statistics of
+        minibatch i are the same in every epoch), and the loss launch of minibatch i normalises with its two floats while it loads.
+        In a multi-rank job those statistics stay per rank, as the op chain below has them."""
+        from .fused_loss import adv_stats, fused_ppo_loss, std_param
 
         ac, st = self.actor_critic, self.storage
         obs, cobs, small = self._flat_storage()
         stats = torch.zeros(3, device=obs.device)
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         pair = self._packed_pair()
-        if pair is not None and self._flat_adam is not None and self.direct_update and ac.std.requires_grad:
+        std_p, std_is_log = std_param(ac)
+        if pair is not None and self._flat_adam is not None and self.direct_update and std_p.requires_grad:
             return self._direct_update(pair)
         if pair is not None:
             pair.arm_domain_check()  # the first minibatch of the update reports the largest layer input (LT_MLP_INPUT_CLAMP)
-        for idx in st.mini_batch_indices(self.num_mini_batches, self.num_learning_epochs):
+        perm, mb = st.mini_batch_permutation(self.num_mini_batches)
+        mb_stats = adv_stats(small[2], perm, mb, self.num_mini_batches) if self.normalize_advantage_per_mini_batch else None
+        for step_i in range(self.num_learning_epochs * self.num_mini_batches):
+            i = step_i % self.num_mini_batches
+            idx = perm[i * mb:(i + 1) * mb]
             # both networks' forward in one launch of the MFMA MLP kernel where their shape allows (rl/mlp.py PackedPair)
             o, co = obs[idx], cobs[idx]
             if o.dtype != torch.float32:  # bf16 observation storage (BASELINE config 5): the update computes in f32
                 o, co = o.float(), co.float()
             mu, value = pair(o, co) if pair is not None else (ac.actor(o), ac.critic(co))
             loss, surrogate_loss, value_loss, ent, kl_mean = fused_ppo_loss(
-                mu, ac.std, value, *small, self.clip_param, self.value_loss_coef, self.entropy_coef,
-                self.use_clipped_value_loss, idx=idx)
+                mu, std_p, value, *small, self.clip_param, self.value_loss_coef, self.entropy_coef,
+                self.use_clipped_value_loss, idx=idx, std_is_log=std_is_log, adv_stats=None if mb_stats is None else mb_stats[i])
             # the 1-float KL all-reduce starts here and its host read waits until the backward pass is enqueued: the collective's
             # latency (and the host round trip of the learning-rate rule, ppo.py:273-281) hides under the backward GEMMs; the
             # decision still precedes this step's optimizer update, as in the reference
@@ -202,7 +212,12 @@ class PPO:
         stacks' backward chains writing their gradients straight into the flat bucket (rl/mlp.py `backward_chain`), [gradient
         all-reduce], clip + Adam with the learning rate read from the device (`lt_adam_clip_step_dev`).  Statistics and the learning
         rate come back in ONE read at the end.  Arithmetic equal to `_fused_update` (tests/test_hip_ppo_graph.py); the host used to
-        wait for the KL of every step - 20 stalls per iteration, ~350 us of idle GPU each."""
+        wait for the KL of every step - 20 stalls per iteration, ~350 us of idle GPU each.
+
+        Log-type std and per-minibatch advantage normalisation as in `_fused_update`: `log_std` and its slot of the bucket stand where
+        `std` and its slot do, the statistics come from one `lt_adv_stats` launch per update and stay per rank in a multi-rank job."""
+        from .fused_loss import adv_stats, std_param
+
         ac, st, fa = self.actor_critic, self.storage, self._flat_adam
         obs, cobs, small = self._flat_storage()
         small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
@@ -213,7 +228,8 @@ class PPO:
         state[0] = self.learning_rate
         lr_dev, stats = state[:1], state[1:]
         grad_of = fa.grad_views()
-        std_c = ac.std.detach()
+        std_p, std_is_log = std_param(ac)
+        std_c = std_p.detach()
         pair.arm_domain_check()
         n_steps = 0
         # The reference draws ONE permutation per update and reuses it in every epoch (rollout_storage.py:189): the two observation
@@ -224,6 +240,7 @@ class PPO:
         two_buckets = split_buckets and 0 < critic_at < self._flat_grad.numel()
         perm, m = st.mini_batch_permutation(self.num_mini_batches)
         perm_o, perm_co = obs[perm], cobs[perm]
+        mb_stats = adv_stats(small[2], perm, m, self.num_mini_batches) if self.normalize_advantage_per_mini_batch else None
         if perm_o.dtype != torch.float32:  # bf16 observation storage (BASELINE config 5): the update computes in f32
             perm_o, perm_co = perm_o.float(), perm_co.float()
         # the same rows in the MLP kernels' split format (f16 hi | f16 lo): what the first layer's weight gradient multiplies, 20 times
@@ -239,14 +256,19 @@ class PPO:
             acc = torch.empty(24, device=dev, dtype=torch.float32)
             out = torch.empty(24, device=dev, dtype=torch.float32)
             stream = _abi.stream(dev)
-            _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                      float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
+            if std_is_log or mb_stats is not None:
+                _abi.call("lt_ppo_loss_opts", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
+                          None if mb_stats is None else mb_stats[i], dmu, dvalue, acc, out, stream)
+            else:
+                _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
             kl = None
             if adaptive:
                 kl = out[4:5]
                 if self.dist.world_size > 1:  # every rank must take the same decision; the collective is stream-ordered
                     kl = self.dist.all_reduce_mean_(kl.clone())
-            _abi.call("lt_ppo_lr_rule", kl, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out, grad_of[ac.std], a_dim, stream)
+            _abi.call("lt_ppo_lr_rule", kl, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out, grad_of[std_p], a_dim, stream)
             if self.dist.world_size > 1 and two_buckets:
                 # the bucket in two halves (std + actor | critic): the actor's all-reduce runs on RCCL's stream under the critic's
                 # three weight-gradient launches (~105 us at 24 576 rows), only the critic's half stays exposed
@@ -402,7 +424,10 @@ class PPO:
         sum_value = sum_surr = sum_ent = 0.0
         stats = None
         recurrent = getattr(ac, "is_recurrent", False)
-        if not recurrent and not self.normalize_advantage_per_mini_batch and self._fused_loss_ok(None):
+        # (per-minibatch advantage normalisation rides on the fused update too; minibatches of one row, whose std is NaN in the
+        # reference, keep the op chain below)
+        one_row = self.normalize_advantage_per_mini_batch and (self.storage.num_envs * self.storage.num_steps) // self.num_mini_batches < 2
+        if not recurrent and not one_row and self._fused_loss_ok(None):
             return self._fused_update()
         batches = (self.storage.recurrent_mini_batches(self.num_mini_batches, self.num_learning_epochs) if recurrent
                    else self.storage.mini_batches(self.num_mini_batches, self.num_learning_epochs))
@@ -419,11 +444,12 @@ class PPO:
                     adv = (adv - adv.mean()) / (adv.std() + 1e-8)
             if self._fused_loss_ok(b):
                 # GPU: log-prob, KL, surrogate, value loss, entropy and their gradients in one launch (csrc/lt_ppo.hip)
-                from .fused_loss import fused_ppo_loss
+                from .fused_loss import fused_ppo_loss, std_param
 
+                std_p, std_is_log = std_param(ac)
                 loss, surrogate_loss, value_loss, ent, kl_mean = fused_ppo_loss(
-                    ac.actor(b.obs), ac.std, ac.critic(b.critic_obs), b.actions, b.log_prob, adv, b.returns, b.values, b.mu, b.sigma,
-                    self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
+                    ac.actor(b.obs), std_p, ac.critic(b.critic_obs), b.actions, b.log_prob, adv, b.returns, b.values, b.mu, b.sigma,
+                    self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss, std_is_log=std_is_log)
                 if self.desired_kl is not None and self.schedule == "adaptive":
                     self._apply_kl(kl_mean)
                 if stats is None:

@@ -163,7 +163,7 @@ class OnPolicyRunner:
                 self.writer.flush()
 
     def _make_fused(self):
-        """FusedRollout when the env is the HIP env on a GPU and the policy is the plain feed-forward ActorCritic, or - behind the cfg
+        """FusedRollout when the env is the HIP env on a GPU and the policy is the plain feed-forward ActorCritic (either noise_std_type), or - behind the cfg
         key `fused_recurrent_rollout` (default False: the fused path draws its exploration noise from the kernels' Philox stream, which
         would change existing runs) - an ActorCriticRecurrent whose memories csrc/lt_memory.hip serves."""
         try:
@@ -177,8 +177,6 @@ class OnPolicyRunner:
         if not isinstance(target, LocoTouchVecEnv) or self.cfg.get("fused_rollout", True) is False:
             return None
         ac = self.alg.actor_critic
-        if getattr(ac, "noise_std_type", "scalar") != "scalar":
-            return None
         if type(ac) is ActorCriticRecurrent:
             from .fused import recurrent_unsupported
 
