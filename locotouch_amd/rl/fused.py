@@ -25,14 +25,15 @@ Log-type std (`ActorCritic(noise_std_type="log")`): the policy launches read sig
 `lt_std_from_log` launch at the head of every rollout refreshes from `log_std` (include/lt_ppo_opts.h) - inside a captured region, so a
 replayed graph follows the optimizer.  The launches of a step are the same two.
 
-Recurrent policies (`ActorCriticRecurrent` with single-layer LSTM memories; the runner's `fused_recurrent_rollout`): a step is
-    [lt_memory_step: both memories - reset mask of the previous step's dones, the pre-step state into the storage's
-     `saved_hidden_states` slot t, the LSTM cell on the observation rows of slot t, new raw (h, c) into a ping-pong buffer]
+Recurrent policies (`ActorCriticRecurrent` with two single-layer memories of one kind - LSTM, or GRU with `fused_gru_memories=True`; the
+runner's `fused_recurrent_rollout`): a step is
+    [the cell's `step`: both memories - reset mask of the previous step's dones, the pre-step state into the storage's
+     `saved_hidden_states` slot t, the cell on the observation rows of slot t, the new raw state into a ping-pong buffer]
  -> [policy + value on the two h buffers] -> [env step]
-and one `lt_memory_finish` launch behind the last step leaves where(dones[T-1], 0, state) in the modules' `hidden_states`
-(csrc/lt_memory.hip; DESIGN.md 4 "Recurrent rollout step").  With `fused_gru_memories=True` two GRU memories take the same path through
-`lt_memory_gru_step` / `lt_memory_gru_finish` (csrc/lt_memory_gru.hip): the state is one tensor per memory instead of (h, c).  Both files
-are a cell on the one row-block kernel of csrc/lt_memory_tile.h.
+and one launch of the cell's `finish` behind the last step leaves where(dones[T-1], 0, state) in the modules' `hidden_states` (DESIGN.md
+4 "Recurrent rollout step").  What differs between the kinds stands in the `Cell` table of rl/memory_seq.py: the state is (h, c) or h
+alone, the launches are `lt_memory_step` / `lt_memory_finish` (csrc/lt_memory.hip) or `lt_memory_gru_step` / `lt_memory_gru_finish`
+(csrc/lt_memory_gru.hip) - both a cell on the one row-block kernel of csrc/lt_memory_tile.h.
 """
 from __future__ import annotations
 
@@ -40,8 +41,7 @@ from __future__ import annotations
 import torch
 
 from .. import _abi
-
-MEMORY_MIN_HIDDEN, MEMORY_MAX_HIDDEN, MEMORY_MAX_K = 64, 512, 1248  # include/lt_memory.h
+from .memory_seq import cell_of, memories_unsupported
 
 
 def recurrent_unsupported(ac, storage, gru_memories: bool = False) -> str | None:
@@ -51,24 +51,12 @@ def recurrent_unsupported(ac, storage, gru_memories: bool = False) -> str | None
     mems = (getattr(ac, "memory_a", None), getattr(ac, "memory_c", None))
     if any(m is None for m in mems):
         return "the policy has no memory_a / memory_c"
-    kind = torch.nn.GRU if gru_memories and isinstance(mems[0].rnn, torch.nn.GRU) else torch.nn.LSTM
+    why = memories_unsupported(*mems, gru_memories=gru_memories)  # (the checks rl/memory_seq.py `unsupported` makes as well)
+    if why is not None:
+        return why
     for name, m in zip(("memory_a", "memory_c"), mems):
-        rnn = m.rnn
-        if not isinstance(rnn, kind):
-            if gru_memories and isinstance(rnn, (torch.nn.LSTM, torch.nn.GRU)):
-                return f"{name} is a {type(rnn).__name__} beside a {kind.__name__}: the two memories must be of one kind"
-            return f"{name} is a {type(rnn).__name__}: only LSTM memories are served"
-        if rnn.num_layers != 1 or rnn.bidirectional or rnn.batch_first or not rnn.bias or getattr(rnn, "proj_size", 0) != 0:
-            return f"{name} must be a single-layer, unidirectional, time-major {kind.__name__} with biases and without projection"
-        h = rnn.hidden_size
-        if h % 64 or not MEMORY_MIN_HIDDEN <= h <= MEMORY_MAX_HIDDEN:
-            return f"{name}: hidden size {h} is not a multiple of 64 in [{MEMORY_MIN_HIDDEN}, {MEMORY_MAX_HIDDEN}]"
-        if rnn.input_size + h > MEMORY_MAX_K:
-            return f"{name}: input size + hidden size exceeds {MEMORY_MAX_K}"
-        if rnn.weight_ih_l0.dtype != torch.float32:
+        if m.rnn.weight_ih_l0.dtype != torch.float32:
             return f"{name} is not f32"
-    if mems[0].rnn.hidden_size != mems[1].rnn.hidden_size:
-        return "the two memories differ in hidden size"
     if storage.observations.dtype != torch.float32:
         return "bf16 observation rows: the memory step reads f32 rows"
     return None
@@ -115,9 +103,9 @@ class FusedRollout:
         self._std_buf = torch.zeros(12, device=env.device) if getattr(ac, "noise_std_type", "scalar") == "log" else None
         if self._std_buf is not None and ac.log_std.shape != (12,):
             raise ValueError("FusedRollout: log_std must hold the env's 12 actions")
-        # recurrent policy: the two LSTM memories run in one launch in front of the MLPs (csrc/lt_memory.hip)
+        # recurrent policy: the two memories run in one launch in front of the MLPs; `cell` is their kind (rl/memory_seq.py `LSTM` / `GRU`)
         self.recurrent = bool(getattr(ac, "is_recurrent", False))
-        self.gru = False  # GRU memories (opt-in `fused_gru_memories`): one state tensor per memory, csrc/lt_memory_gru.hip
+        self.cell = None
         if not self.recurrent and type(ac).__name__ == "ActorCriticEncoder":
             raise ValueError("FusedRollout does not serve ActorCriticEncoder: its encoders are not part of the fused step")
         if self.recurrent:
@@ -126,7 +114,8 @@ class FusedRollout:
                 why = "observation normalisers are not served together with a recurrent policy"
             if why is not None:
                 raise ValueError(f"FusedRollout does not serve this recurrent policy: {why}")
-            self.gru = isinstance(ac.memory_a.rnn, torch.nn.GRU)
+            self.cell = cell_of(ac.memory_a, fused_gru_memories)
+        self.gru = self.cell is not None and self.cell.nn is torch.nn.GRU
         self.env, self.alg = env, alg
         self.device = env.device
         self.actions = torch.zeros(env.num_envs, 12, device=self.device)
@@ -172,13 +161,13 @@ class FusedRollout:
             self._init_memory()
 
     def _init_memory(self) -> None:
-        """Ping-pong buffers of the raw (h, c) of both memories - of h alone for GRU memories - and the storage's `saved_hidden_states`
-        slots."""
+        """Ping-pong buffers of the raw state of both memories - (h, c), or h alone: one tensor per state field of the cell - and the
+        storage's `saved_hidden_states` slots."""
         st, ac, n = self.alg.storage, self.alg.actor_critic, self.env.num_envs
         hid = ac.memory_a.rnn.hidden_size
         steps = st.observations.shape[0]
         rows = n + (-n) % 64  # (the MLP launch reads whole row tiles)
-        ns = 1 if self.gru else 2  # state tensors per memory
+        ns = len(self.cell.state)  # state tensors per memory
         # _hc[parity][network] = (h, c), or (h,): step t reads parity (t - 1) & 1 - at t = 0 the modules' own state - and writes parity t & 1
         self._hc = [[tuple(torch.zeros(rows, hid, device=self.device) for _ in range(ns)) for _ in range(2)] for _ in range(2)]
         for name in ("saved_hidden_states_a", "saved_hidden_states_c"):
@@ -186,28 +175,30 @@ class FusedRollout:
             if saved is None:
                 setattr(st, name, [torch.zeros(steps, 1, n, hid, device=self.device) for _ in range(ns)])
             elif len(saved) != ns or any(s.shape != (steps, 1, n, hid) or s.dtype != torch.float32 or not s.is_contiguous() for s in saved):
-                raise ValueError(f"storage.{name} must be {'[h]' if self.gru else '[h, c]'} of contiguous f32 ({steps}, 1, {n}, {hid}) tensors")
-        self._state = None  # the modules' (h, c) tensors of both memories, adopted by begin() / rollout()
+                raise ValueError(f"storage.{name} must be [{', '.join(f[0] for f in self.cell.state)}] of contiguous f32 ({steps}, 1, {n}, {hid}) tensors")
+        self._state = None  # the modules' state tensors of both memories, adopted by begin() / rollout()
 
     def _adopt_state(self) -> None:
         """The modules' `hidden_states` become the rollout's state tensors (zeros when a memory has none yet): step 0 reads them,
-        `lt_memory_finish` writes them."""
+        the cell's `finish` writes them."""
         ac, n = self.alg.actor_critic, self.env.num_envs
+        ns = len(self.cell.state)
+        one = ns == 1  # a module with one state tensor holds the tensor itself, as its nn module takes it, not a 1-tuple
         state = []
         for name, mem in (("memory_a", ac.memory_a), ("memory_c", ac.memory_c)):
             hid = mem.rnn.hidden_size
             if mem.hidden_states is None:
-                zeros = tuple(torch.zeros(1, n, hid, device=self.device) for _ in self._hc[0][0])
-                mem.hidden_states = zeros[0] if self.gru else zeros
-            hc = (mem.hidden_states,) if self.gru else mem.hidden_states  # (an nn.GRU's state is the tensor itself)
-            if (not isinstance(hc, tuple) or len(hc) != len(self._hc[0][0])
+                zeros = tuple(torch.zeros(1, n, hid, device=self.device) for _ in range(ns))
+                mem.hidden_states = zeros[0] if one else zeros
+            hc = (mem.hidden_states,) if one else mem.hidden_states
+            if (not isinstance(hc, tuple) or len(hc) != ns
                     or any(not torch.is_tensor(x) or x.shape != (1, n, hid) or x.dtype != torch.float32 or x.device != self._hc[0][0][0].device
                            for x in hc)):
-                raise ValueError(f"{name}.hidden_states must be {'h, an' if self.gru else '(h, c) of'} f32 [1, {n}, {hid}] "
-                                 f"tensor{'' if self.gru else 's'} on {self.device}")
+                raise ValueError(f"{name}.hidden_states must be {'the tensor' if one else 'a tuple'} ({', '.join(f[0] for f in self.cell.state)}) "
+                                 f"of f32 [1, {n}, {hid}] on {self.device}")
             if not all(x.is_contiguous() for x in hc):
                 hc = tuple(x.contiguous() for x in hc)
-                mem.hidden_states = hc[0] if self.gru else hc
+                mem.hidden_states = hc[0] if one else hc
             state.append(hc)
         self._state = state
 
@@ -219,15 +210,11 @@ class FusedRollout:
         nets = []
         for k, (mem, x, saved) in enumerate(((ac.memory_a, obs, st.saved_hidden_states_a), (ac.memory_c, cobs, st.saved_hidden_states_c))):
             rnn = mem.rnn
-            if self.gru:
-                nets.append(_abi.LtMemoryGruNet(x.data_ptr(), x.shape[1], rnn.weight_ih_l0.data_ptr(), rnn.weight_hh_l0.data_ptr(),
-                                                rnn.bias_ih_l0.data_ptr(), rnn.bias_hh_l0.data_ptr(), src[k][0].data_ptr(),
-                                                dst[k][0].data_ptr(), saved[0][t].data_ptr()))
-                continue
-            nets.append(_abi.LtMemoryNet(x.data_ptr(), x.shape[1], rnn.weight_ih_l0.data_ptr(), rnn.weight_hh_l0.data_ptr(),
-                                         rnn.bias_ih_l0.data_ptr(), rnn.bias_hh_l0.data_ptr(), src[k][0].data_ptr(), src[k][1].data_ptr(),
-                                         dst[k][0].data_ptr(), dst[k][1].data_ptr(), saved[0][t].data_ptr(), saved[1][t].data_ptr()))
-        _abi.call("lt_memory_gru_step" if self.gru else "lt_memory_step", nets[0], nets[1], st.dones[t - 1] if t > 0 else None, self.env.num_envs, ac.memory_a.rnn.hidden_size,
+            # the structure's fields in order: x, I, the four parameters, h_in[, c_in], h_out[, c_out], saved_h[, saved_c]
+            nets.append(self.cell.step_net(x.data_ptr(), x.shape[1], rnn.weight_ih_l0.data_ptr(), rnn.weight_hh_l0.data_ptr(),
+                                           rnn.bias_ih_l0.data_ptr(), rnn.bias_hh_l0.data_ptr(), *(s.data_ptr() for s in src[k]),
+                                           *(d.data_ptr() for d in dst[k]), *(s[t].data_ptr() for s in saved)))
+        _abi.call(self.cell.step, nets[0], nets[1], st.dones[t - 1] if t > 0 else None, self.env.num_envs, ac.memory_a.rnn.hidden_size,
                   _abi.stream(self.device))
 
     def _memory_rows(self, t: int):
@@ -236,14 +223,10 @@ class FusedRollout:
         return self._hc[t & 1][0][0][:n], self._hc[t & 1][1][0][:n]
 
     def _memory_finish(self, num_steps: int) -> None:
+        """h_a[, c_a], h_c[, c_c] of the last step, masked by its dones, into the modules' state tensors in the same order."""
         raw, st = self._hc[(num_steps - 1) & 1], self.alg.storage
-        if self.gru:
-            _abi.call("lt_memory_gru_finish", raw[0][0], raw[1][0], st.dones[num_steps - 1], self.env.num_envs,
-                      self.alg.actor_critic.memory_a.rnn.hidden_size, self._state[0][0], self._state[1][0], _abi.stream(self.device))
-            return
-        (ha, ca), (hc, cc) = self._state
-        _abi.call("lt_memory_finish", raw[0][0], raw[0][1], raw[1][0], raw[1][1], st.dones[num_steps - 1], self.env.num_envs,
-                  self.alg.actor_critic.memory_a.rnn.hidden_size, ha, ca, hc, cc, _abi.stream(self.device))
+        _abi.call(self.cell.finish, *raw[0], *raw[1], st.dones[num_steps - 1], self.env.num_envs,
+                  self.alg.actor_critic.memory_a.rnn.hidden_size, *self._state[0], *self._state[1], _abi.stream(self.device))
 
     def _init_normalizers(self, actor_norm, critic_norm) -> None:
         env, st = self.env, self.alg.storage

@@ -1,44 +1,72 @@
-"""The two LSTM memories of a recurrent policy over a WHOLE ROLLOUT of an env block: what `PPO._recurrent_update` runs per optimizer step
-instead of padded trajectories (`split_and_pad_trajectories` -> two `lstm_sequence` -> two `unpad_trajectories`).
+"""The two memories of a recurrent policy over a WHOLE ROLLOUT of an env block: what `PPO._recurrent_update` runs per optimizer step
+instead of padded trajectories (`split_and_pad_trajectories` -> two sequence passes -> two `unpad_trajectories`).
 
 Why this equals the padded form: `PolicyMemory.reset(dones)` zeroes the state of done envs, so the hidden state saved at the first step
 of a trajectory that starts after a done is all zeros.  The padded batch of trajectories that starts from the saved states therefore
 equals, row for row, ONE pass over the block's envs for all T steps that starts from `saved_hidden_states[0][:, e0:e1]` and replaces the
-carried (h, c) by zeros wherever `dones[t - 1]` is set.  No gradient crosses a done in either form (the padded tail has dout = 0, the
+carried state by zeros wherever `dones[t - 1]` is set.  No gradient crosses a done in either form (the padded tail has dout = 0, the
 reset state is a constant), and the output [T, E, H] is already in the row order `unpad_trajectories` produces
-(tests/test_recurrent_update_form.py).
+(tests/test_recurrent_update_form.py, tests/test_gru_update_form.py).
 
-`memory_rollout_sequence` is one `torch.autograd.Function` over both memories' `nn.LSTM` parameters (the modules' own: checkpoints are
-unaffected), in two forms as rl/lstm.py:
-  * a PyTorch-op time loop with `where(dones[t - 1], 0, .)` on the carry: the CPU, any dtype, shapes the kernels do not cover;
-  * csrc/lt_memory.hip (the LSTM cell on the kernels of csrc/lt_memory_tile.h; include/lt_memory_seq.h): `lt_memory_seq_forward`
-    (T launches, both networks in each, the observation rows read in place) and `lt_memory_seq_backward` (T launches).  What is not sequential stays outside the loop, one call each:
-    dW_hh = dgates^T h_prev and dW_ih = dgates^T X through rl/gru.py `_wgrad`, the bias gradients as column sums.
-The observations and the initial states carry no gradient: dX, dh0 and dc0 are not computed.
+Two kinds of memory are served, and everything this side knows about a kind stands once, in its `Cell`: `LSTM`, and `GRU` behind the
+opt-in `gru_memories=True` (`fused_gru_memories` of rl/ppo.py and rl/fused.py).
 
-GRU memories (`gru_memories=True`, the opt-in `fused_gru_memories` of rl/ppo.py) have the same two forms: the op loop `_gru_forward_ops`
-/ `_gru_backward_ops` and csrc/lt_memory_gru.hip (the GRU cell on the same kernels; include/lt_memory_gru.h).  The state is one tensor, the forward record is (out, gates
-= r | z | n | hn, h_prev), and the backward pass leaves TWO gate-gradient arrays, dig = (dr, dz, dn) and dhg = (dr, dz, dn * r): dW_ih =
-dig^T X and db_ih come from the first, dW_hh = dhg^T h_prev and db_hh from the second, each as the kernel wrote it.
+    LSTM  state (h, c); forward record (out, cell, gates = i | f | g | o, h_prev, c_prev); the backward pass leaves ONE gate-gradient
+          array, dgates [T, E, 4H], which feeds both dW_ih / db_ih and dW_hh / db_hh.  csrc/lt_memory.hip; include/lt_memory.h (one
+          rollout step) and include/lt_memory_seq.h (whole rollouts).
+    GRU   state h; forward record (out, gates = r | z | n | hn, h_prev); the backward pass leaves TWO arrays, dig = (dr, dz, dn) and dhg
+          = (dr, dz, dn * r), each [T, E, 3H]: dW_ih = dig^T X and db_ih come from the first, dW_hh = dhg^T h_prev and db_hh from the
+          second, each as the kernel wrote it.  csrc/lt_memory_gru.hip; include/lt_memory_gru.h.
+
+`memory_rollout_sequence` is one `torch.autograd.Function` over both memories' `nn.LSTM` / `nn.GRU` parameters (the modules' own:
+checkpoints are unaffected), in two forms as rl/lstm.py:
+  * `_SeqOps`: a PyTorch-op time loop (the cell's `forward_ops` / `backward_ops`) with `where(dones[t - 1], 0, .)` on the carry: the
+    CPU, any dtype, shapes the kernels do not cover;
+  * `_SeqHip`: the cell's `seq_forward` (T launches, both networks in each, the observation rows read in place) and `seq_backward` (T
+    launches) - both cells on the one row-block kernel of csrc/lt_memory_tile.h.  What is not sequential stays outside the loop, one
+    call each (`_finish`): the two weight gradients through rl/gru.py `_wgrad`, the bias gradients as column sums.
+The observations and the initial states carry no gradient: dX and the gradients of the initial states are not computed.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+from typing import Callable
+
 import torch
 
+from .. import _abi
 from .gru import _wgrad
 
-MIN_HIDDEN, MAX_HIDDEN, MAX_K = 64, 512, 1248  # include/lt_memory_seq.h
+MIN_HIDDEN, MAX_HIDDEN, MAX_K = 64, 512, 1248  # include/lt_memory.h, include/lt_memory_seq.h, include/lt_memory_gru.h
+
+
+@dataclass(frozen=True)
+class Cell:
+    """One kind of memory.  Widths are in units of H."""
+    nn: type                # the module class of `PolicyMemory.rnn`
+    state: tuple            # the initial-state fields of the sequence structure: as many tensors per memory, in this order
+    record: tuple           # (key, width) of the forward record, in the order `forward_ops` returns it; keys are the structure's fields
+    dgates: tuple           # (key, width) of the gate-gradient arrays, in the order `backward_ops` returns them; keys as above
+    d_ih: str               # the gate-gradient array behind dW_ih and db_ih
+    d_hh: str               # the one behind dW_hh and db_hh (times W_hh: what a step hands to the one before it)
+    reads: tuple            # record keys the backward structure reads, in the order `backward_ops` takes them
+    carry: str              # the backward structure's [E, H] scratch field
+    step_net: type          # ctypes structures: one rollout step, the sequence forward pass, the sequence backward pass
+    seq_net: type
+    seq_grad: type
+    step: str               # entry points
+    finish: str
+    seq_forward: str
+    seq_backward: str
+    backward_units: str
+    forward_ops: Callable   # the PyTorch-op form: (x, done_rows, *state, w_ih, w_hh, b_ih, b_hh) -> the record
+    backward_ops: Callable  # (dout, done_rows, w_hh, *reads) -> the gate-gradient arrays
 
 
 def _params(memory):
     rnn = memory.rnn
     return rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0
 
-
-def _state(hc0, E):
-    """(h0, c0) as [E, H] from `saved_hidden_states[i][0][:, e0:e1]`-shaped ([1, E, H]) or [E, H] tensors."""
-    h0, c0 = hc0
-    return h0.reshape(E, -1), c0.reshape(E, -1)
 
 
 def _dones2d(dones, T, E):
@@ -57,7 +85,7 @@ def _dones_bytes(d):
     return d
 
 
-# ---- the PyTorch-op form --------------------------------------------------------------------------------------------------------------
+# ---- the PyTorch-op forms -------------------------------------------------------------------------------------------------------------
 def _forward_ops(x, done_rows, h0, c0, w_ih, w_hh, b_ih, b_hh):
     """One network.  done_rows: bool [T, E, 1] or None.  Returns the forward record (out, cell, gates, h_prev, c_prev)."""
     T, E, _ = x.shape
@@ -85,7 +113,7 @@ def _forward_ops(x, done_rows, h0, c0, w_ih, w_hh, b_ih, b_hh):
 
 
 def _backward_ops(dout, done_rows, w_hh, cell, gates, c_prev):
-    """dgates [T, E, 4H] of one network from the forward record."""
+    """(dgates,), [T, E, 4H], of one network from the forward record."""
     T, E, H = cell.shape
     dgates = cell.new_empty(T, E, 4 * H)
     dh_next = dc_next = None  # what step t + 1 hands to step t: dgates[t+1] W_hh and dc_{t+1} f_{t+1}
@@ -102,117 +130,7 @@ def _backward_ops(dout, done_rows, w_hh, cell, gates, c_prev):
         dc = dh * o * (1 - tc * tc) if dc is None else dc + dh * o * (1 - tc * tc)
         dgates[t] = torch.cat([dc * g * i * (1 - i), dc * c_prev[t] * f * (1 - f), dc * i * (1 - g * g), dh * tc * o * (1 - o)], dim=1)
         dh_next, dc_next = dgates[t] @ w_hh, dc * f
-    return dgates
-
-
-def _finish(x, dgates, h_prev):
-    """(dW_ih, dW_hh, db_ih, db_hh) of one network: everything of the backward pass that is not sequential, one call each."""
-    T, E, H = h_prev.shape
-    dg2 = dgates.view(T * E, 4 * H)
-    db = dg2.sum(0)
-    return _wgrad(dg2, x.reshape(T * E, -1)), _wgrad(dg2, h_prev.view(T * E, H)), db, db.clone()
-
-
-class _MemorySeq(torch.autograd.Function):
-    """Both memories, time loop in PyTorch ops."""
-
-    @staticmethod
-    def forward(ctx, x_a, x_c, dones, h0_a, c0_a, h0_c, c0_c, *params):
-        done_rows = None if dones is None else (dones != 0).unsqueeze(-1)
-        ra = _forward_ops(x_a, done_rows, h0_a, c0_a, *params[:4])
-        rc = _forward_ops(x_c, done_rows, h0_c, c0_c, *params[4:])
-        ctx.save_for_backward(x_a, x_c, done_rows, params[1], params[5], *ra[1:], *rc[1:])
-        ctx.set_materialize_grads(False)
-        return ra[0], rc[0]
-
-    @staticmethod
-    def backward(ctx, dout_a, dout_c):
-        x_a, x_c, done_rows, w_hh_a, w_hh_c, *rec = ctx.saved_tensors
-        grads = []
-        for x, dout, w_hh, (cell, gates, h_prev, c_prev) in ((x_a, dout_a, w_hh_a, rec[:4]), (x_c, dout_c, w_hh_c, rec[4:])):
-            if dout is None:
-                grads += [None] * 4
-                continue
-            grads += _finish(x, _backward_ops(dout, done_rows, w_hh, cell, gates, c_prev), h_prev)
-        return (None,) * 7 + tuple(grads)
-
-
-# ---- the HIP form ---------------------------------------------------------------------------------------------------------------------
-def _rows(x):
-    """x [T, E, I] as the kernels read it: rows of I contiguous floats, E rows per step, any stride between steps."""
-    T, E, I = x.shape
-    if x.stride(2) != 1 or x.stride(1) != I or x.stride(0) < E * I:
-        x = x.contiguous()
-    return x
-
-
-def hip_forward(x_a, x_c, dones, h0_a, c0_a, h0_c, c0_c, params):
-    """`lt_memory_seq_forward`: T launches.  x_*: [T, E, I] f32 (a block `[:, e0:e1]` of the storage is read in place); dones: uint8
-    [T, E] (contiguous rows, any stride between steps) or None; params: the eight LSTM parameters (actor's four, critic's four).  Returns the two forward records
-    {out, cell, gates, h_prev, c_prev}."""
-    from .. import _abi
-
-    T, E, _ = x_a.shape
-    H = params[1].shape[1]
-    recs, nets = [], []
-    for x, h0, c0, (w_ih, w_hh, b_ih, b_hh) in ((x_a, h0_a, c0_a, params[:4]), (x_c, h0_c, c0_c, params[4:])):
-        x = _rows(x)
-        ops = [t.detach().contiguous() for t in (w_ih, w_hh, b_ih, b_hh, h0, c0)]
-        rec = {k: x.new_empty(T, E, 4 * H if k == "gates" else H) for k in ("out", "cell", "gates", "h_prev", "c_prev")}
-        nets.append(_abi.LtMemorySeqNet(x=x.data_ptr(), x_stride=x.stride(0), I=x.shape[2], w_ih=ops[0].data_ptr(), w_hh=ops[1].data_ptr(),
-                                        b_ih=ops[2].data_ptr(), b_hh=ops[3].data_ptr(), h0=ops[4].data_ptr(), c0=ops[5].data_ptr(),
-                                        **{k: v.data_ptr() for k, v in rec.items()}))
-        recs.append(rec)
-    assert dones is None or (dones.dtype == torch.uint8 and dones.stride(1) == 1)
-    _abi.call("lt_memory_seq_forward", nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H, _abi.stream(x_a.device))
-    return recs
-
-
-def hip_backward(douts, dones, w_hhs, recs):
-    """`lt_memory_seq_backward`: T launches.  Returns the two dgates [T, E, 4H]."""
-    from .. import _abi
-
-    T, E, H = recs[0]["out"].shape
-    nets, dgs = [], []
-    for dout, w_hh, rec in zip(douts, w_hhs, recs):
-        dout = torch.zeros_like(rec["out"]) if dout is None else dout.contiguous()
-        w = w_hh.detach().contiguous()
-        dg, carry = torch.empty_like(rec["gates"]), dout.new_empty(E, H)
-        nets.append(_abi.LtMemorySeqGrad(dout=dout.data_ptr(), w_hh=w.data_ptr(), cell=rec["cell"].data_ptr(), gates=rec["gates"].data_ptr(),
-                                         c_prev=rec["c_prev"].data_ptr(), dgates=dg.data_ptr(), dc_carry=carry.data_ptr()))
-        dgs.append(dg)
-    _abi.call("lt_memory_seq_backward", nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H, _abi.stream(dgs[0].device))
-    return dgs
-
-
-class _MemorySeqHip(torch.autograd.Function):
-    """Both memories, time loops in csrc/lt_memory.hip."""
-
-    @staticmethod
-    def forward(ctx, x_a, x_c, dones, h0_a, c0_a, h0_c, c0_c, *params):
-        ra, rc = hip_forward(x_a, x_c, dones, h0_a, c0_a, h0_c, c0_c, params)
-        ctx.save_for_backward(x_a, x_c, dones, params[1], params[5], *(r[k] for r in (ra, rc) for k in ("out", "cell", "gates", "h_prev", "c_prev")))
-        ctx.set_materialize_grads(False)
-        return ra["out"], rc["out"]
-
-    @staticmethod
-    def backward(ctx, dout_a, dout_c):
-        x_a, x_c, dones, w_hh_a, w_hh_c, *rec = ctx.saved_tensors
-        keys = ("out", "cell", "gates", "h_prev", "c_prev")
-        recs = [dict(zip(keys, rec[:5])), dict(zip(keys, rec[5:]))]
-        dgs = hip_backward((dout_a, dout_c), dones, (w_hh_a, w_hh_c), recs)
-        grads = []
-        for x, dg, r in zip((x_a, x_c), dgs, recs):
-            grads += _finish(x, dg, r["h_prev"])
-        return (None,) * 7 + tuple(grads)
-
-
-# ---- GRU memories: the PyTorch-op form -------------------------------------------------------------------------------------------------
-def _gru_state(h0, E):
-    """h0 as [E, H] from a `saved_hidden_states[0][0][:, e0:e1]`-shaped ([1, E, H]) or [E, H] tensor, or a 1-tuple of one."""
-    if isinstance(h0, (tuple, list)):
-        (h0,) = h0
-    return h0.reshape(E, -1)
+    return (dgates,)
 
 
 def _gru_forward_ops(x, done_rows, h0, w_ih, w_hh, b_ih, b_hh):
@@ -259,108 +177,156 @@ def _gru_backward_ops(dout, done_rows, w_hh, gates, h_prev):
         back = dhg[t] @ w_hh + dh * z
     return dig, dhg
 
+LSTM = Cell(nn=torch.nn.LSTM, state=("h0", "c0"), record=(("out", 1), ("cell", 1), ("gates", 4), ("h_prev", 1), ("c_prev", 1)),
+            dgates=(("dgates", 4),), d_ih="dgates", d_hh="dgates", reads=("cell", "gates", "c_prev"), carry="dc_carry",
+            step_net=_abi.LtMemoryNet, seq_net=_abi.LtMemorySeqNet, seq_grad=_abi.LtMemorySeqGrad,
+            step="lt_memory_step", finish="lt_memory_finish", seq_forward="lt_memory_seq_forward", seq_backward="lt_memory_seq_backward",
+            backward_units="lt_memory_seq_backward_units", forward_ops=_forward_ops, backward_ops=_backward_ops)
+GRU = Cell(nn=torch.nn.GRU, state=("h0",), record=(("out", 1), ("gates", 4), ("h_prev", 1)),
+           dgates=(("dig", 3), ("dhg", 3)), d_ih="dig", d_hh="dhg", reads=("gates", "h_prev"), carry="dh_carry",
+           step_net=_abi.LtMemoryGruNet, seq_net=_abi.LtMemoryGruSeqNet, seq_grad=_abi.LtMemoryGruSeqGrad,
+           step="lt_memory_gru_step", finish="lt_memory_gru_finish", seq_forward="lt_memory_gru_seq_forward",
+           seq_backward="lt_memory_gru_seq_backward", backward_units="lt_memory_gru_seq_backward_units",
+           forward_ops=_gru_forward_ops, backward_ops=_gru_backward_ops)
 
-def _gru_finish(x, dig, dhg, h_prev):
-    """(dW_ih, dW_hh, db_ih, db_hh) of one network: everything of the backward pass that is not sequential, one call each."""
+
+def cell_of(memory, gru_memories: bool = False) -> Cell:
+    """The cell `memory` is held to: `GRU` for an `nn.GRU` behind the opt-in, `LSTM` for everything else (`memories_unsupported` says
+    what does not fit it)."""
+    return GRU if gru_memories and isinstance(getattr(memory, "rnn", None), torch.nn.GRU) else LSTM
+
+
+def _state(cell, hc0, E):
+    """The cell's state tensors as [E, H] from a tuple of `saved_hidden_states[i][0][:, e0:e1]`-shaped ([1, E, H]) or [E, H] tensors; a
+    one-state cell takes the bare tensor as well."""
+    hc0 = (hc0,) if torch.is_tensor(hc0) else tuple(hc0)
+    if len(hc0) != len(cell.state):
+        raise ValueError(f"a {cell.nn.__name__} memory starts from {len(cell.state)} state tensor(s), not {len(hc0)}")
+    return tuple(s.reshape(E, -1) for s in hc0)
+
+
+def _finish(cell, x, grads, h_prev):
+    """(dW_ih, dW_hh, db_ih, db_hh) of one network from its gate-gradient arrays: everything of the backward pass that is not sequential,
+    one call each."""
     T, E, H = h_prev.shape
-    di2, dh2 = dig.view(T * E, 3 * H), dhg.view(T * E, 3 * H)
-    return _wgrad(di2, x.reshape(T * E, -1)), _wgrad(dh2, h_prev.view(T * E, H)), di2.sum(0), dh2.sum(0)
+    d_ih, d_hh = (grads[k].view(T * E, -1) for k in (cell.d_ih, cell.d_hh))
+    db_ih = d_ih.sum(0)
+    db_hh = db_ih.clone() if cell.d_hh == cell.d_ih else d_hh.sum(0)
+    return _wgrad(d_ih, x.reshape(T * E, -1)), _wgrad(d_hh, h_prev.view(T * E, H)), db_ih, db_hh
 
 
-class _GruMemorySeq(torch.autograd.Function):
-    """Both GRU memories, time loop in PyTorch ops."""
+def _records(cell, saved):
+    """The two forward records, as dicts, from the tensors `save_for_backward` held."""
+    keys = [k for k, _ in cell.record]
+    return dict(zip(keys, saved[:len(keys)])), dict(zip(keys, saved[len(keys):]))
+
+
+class _SeqOps(torch.autograd.Function):
+    """Both memories, time loop in PyTorch ops.  Arguments behind the dones: the state tensors (the actor's, then the critic's), then
+    the eight parameters."""
 
     @staticmethod
-    def forward(ctx, x_a, x_c, dones, h0_a, h0_c, *params):
+    def forward(ctx, cell, x_a, x_c, dones, *rest):
+        ns = len(cell.state)
+        states, params = rest[:2 * ns], rest[2 * ns:]
         done_rows = None if dones is None else (dones != 0).unsqueeze(-1)
-        ra = _gru_forward_ops(x_a, done_rows, h0_a, *params[:4])
-        rc = _gru_forward_ops(x_c, done_rows, h0_c, *params[4:])
-        ctx.save_for_backward(x_a, x_c, done_rows, params[1], params[5], *ra[1:], *rc[1:])
+        ra = cell.forward_ops(x_a, done_rows, *states[:ns], *params[:4])
+        rc = cell.forward_ops(x_c, done_rows, *states[ns:], *params[4:])
+        ctx.cell = cell
+        ctx.save_for_backward(x_a, x_c, done_rows, params[1], params[5], *ra, *rc)
         ctx.set_materialize_grads(False)
         return ra[0], rc[0]
 
     @staticmethod
     def backward(ctx, dout_a, dout_c):
-        x_a, x_c, done_rows, w_hh_a, w_hh_c, *rec = ctx.saved_tensors
+        cell = ctx.cell
+        x_a, x_c, done_rows, w_hh_a, w_hh_c, *saved = ctx.saved_tensors
         grads = []
-        for x, dout, w_hh, (gates, h_prev) in ((x_a, dout_a, w_hh_a, rec[:2]), (x_c, dout_c, w_hh_c, rec[2:])):
+        for x, dout, w_hh, rec in zip((x_a, x_c), (dout_a, dout_c), (w_hh_a, w_hh_c), _records(cell, saved)):
             if dout is None:
                 grads += [None] * 4
                 continue
-            grads += _gru_finish(x, *_gru_backward_ops(dout, done_rows, w_hh, gates, h_prev), h_prev)
-        return (None,) * 5 + tuple(grads)
+            dgs = cell.backward_ops(dout, done_rows, w_hh, *(rec[k] for k in cell.reads))
+            grads += _finish(cell, x, dict(zip((k for k, _ in cell.dgates), dgs)), rec["h_prev"])
+        return (None,) * (4 + 2 * len(cell.state)) + tuple(grads)
 
 
-# ---- GRU memories: the HIP form --------------------------------------------------------------------------------------------------------
-def gru_hip_forward(x_a, x_c, dones, h0_a, h0_c, params):
-    """`lt_memory_gru_seq_forward`: T launches.  Arguments as `hip_forward` without the cell states; params: the eight GRU parameters.
-    Returns the two forward records {out, gates, h_prev}."""
-    from .. import _abi
+# ---- the HIP form ---------------------------------------------------------------------------------------------------------------------
+def _rows(x):
+    """x [T, E, I] as the kernels read it: rows of I contiguous floats, E rows per step, any stride between steps."""
+    T, E, I = x.shape
+    if x.stride(2) != 1 or x.stride(1) != I or x.stride(0) < E * I:
+        x = x.contiguous()
+    return x
 
+
+def hip_forward(cell, x_a, x_c, dones, states, params):
+    """The cell's `seq_forward`: T launches.  x_*: [T, E, I] f32 (a block `[:, e0:e1]` of the storage is read in place); dones: uint8
+    [T, E] (contiguous rows, any stride between steps) or None; states: the [E, H] state tensors, the actor's then the critic's; params:
+    the eight parameters (actor's four, critic's four).  Returns the two forward records, dicts over the keys of `cell.record`."""
     T, E, _ = x_a.shape
     H = params[1].shape[1]
+    ns = len(cell.state)
     recs, nets = [], []
-    for x, h0, (w_ih, w_hh, b_ih, b_hh) in ((x_a, h0_a, params[:4]), (x_c, h0_c, params[4:])):
+    for k, x in enumerate((x_a, x_c)):
         x = _rows(x)
-        ops = [t.detach().contiguous() for t in (w_ih, w_hh, b_ih, b_hh, h0)]
-        rec = {k: x.new_empty(T, E, 4 * H if k == "gates" else H) for k in ("out", "gates", "h_prev")}
-        nets.append(_abi.LtMemoryGruSeqNet(x=x.data_ptr(), x_stride=x.stride(0), I=x.shape[2], w_ih=ops[0].data_ptr(), w_hh=ops[1].data_ptr(),
-                                           b_ih=ops[2].data_ptr(), b_hh=ops[3].data_ptr(), h0=ops[4].data_ptr(),
-                                           **{k: v.data_ptr() for k, v in rec.items()}))
+        ops = [t.detach().contiguous() for t in (*params[4 * k:4 * k + 4], *states[ns * k:ns * k + ns])]
+        rec = {key: x.new_empty(T, E, w * H) for key, w in cell.record}
+        nets.append(cell.seq_net(x=x.data_ptr(), x_stride=x.stride(0), I=x.shape[2],
+                                 **{f: t.data_ptr() for f, t in zip(("w_ih", "w_hh", "b_ih", "b_hh") + cell.state, ops)},
+                                 **{key: v.data_ptr() for key, v in rec.items()}))
         recs.append(rec)
     assert dones is None or (dones.dtype == torch.uint8 and dones.stride(1) == 1)
-    _abi.call("lt_memory_gru_seq_forward", nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H, _abi.stream(x_a.device))
+    _abi.call(cell.seq_forward, nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H, _abi.stream(x_a.device))
     return recs
 
 
-def gru_hip_backward(douts, dones, w_hhs, recs):
-    """`lt_memory_gru_seq_backward`: T launches.  Returns [(dig, dhg)] of the two networks, each [T, E, 3H]."""
-    from .. import _abi
-
+def hip_backward(cell, douts, dones, w_hhs, recs):
+    """The cell's `seq_backward`: T launches.  Returns the gate-gradient arrays of the two networks, dicts over the keys of `cell.dgates`."""
     T, E, H = recs[0]["out"].shape
     nets, dgs = [], []
     for dout, w_hh, rec in zip(douts, w_hhs, recs):
         dout = torch.zeros_like(rec["out"]) if dout is None else dout.contiguous()
         w = w_hh.detach().contiguous()
-        dig, dhg, carry = dout.new_empty(T, E, 3 * H), dout.new_empty(T, E, 3 * H), dout.new_empty(E, H)
-        nets.append(_abi.LtMemoryGruSeqGrad(dout=dout.data_ptr(), w_hh=w.data_ptr(), gates=rec["gates"].data_ptr(), h_prev=rec["h_prev"].data_ptr(),
-                                            dig=dig.data_ptr(), dhg=dhg.data_ptr(), dh_carry=carry.data_ptr()))
-        dgs.append((dig, dhg))
-    _abi.call("lt_memory_gru_seq_backward", nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H,
-              _abi.stream(dgs[0][0].device))
+        dg = {key: dout.new_empty(T, E, width * H) for key, width in cell.dgates}
+        carry = dout.new_empty(E, H)
+        nets.append(cell.seq_grad(dout=dout.data_ptr(), w_hh=w.data_ptr(), **{key: rec[key].data_ptr() for key in cell.reads},
+                                  **{key: v.data_ptr() for key, v in dg.items()}, **{cell.carry: carry.data_ptr()}))
+        dgs.append(dg)
+    _abi.call(cell.seq_backward, nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H, _abi.stream(recs[0]["out"].device))
     return dgs
 
 
-class _GruMemorySeqHip(torch.autograd.Function):
-    """Both GRU memories, time loops in csrc/lt_memory_gru.hip."""
+class _SeqHip(torch.autograd.Function):
+    """Both memories, time loops in csrc/lt_memory.hip / csrc/lt_memory_gru.hip.  Arguments as `_SeqOps`."""
 
     @staticmethod
-    def forward(ctx, x_a, x_c, dones, h0_a, h0_c, *params):
-        ra, rc = gru_hip_forward(x_a, x_c, dones, h0_a, h0_c, params)
-        ctx.save_for_backward(x_a, x_c, dones, params[1], params[5], *(r[k] for r in (ra, rc) for k in ("out", "gates", "h_prev")))
+    def forward(ctx, cell, x_a, x_c, dones, *rest):
+        ns = len(cell.state)
+        ra, rc = hip_forward(cell, x_a, x_c, dones, rest[:2 * ns], rest[2 * ns:])
+        ctx.cell = cell
+        ctx.save_for_backward(x_a, x_c, dones, rest[2 * ns + 1], rest[2 * ns + 5], *ra.values(), *rc.values())
         ctx.set_materialize_grads(False)
         return ra["out"], rc["out"]
 
     @staticmethod
     def backward(ctx, dout_a, dout_c):
-        x_a, x_c, dones, w_hh_a, w_hh_c, *rec = ctx.saved_tensors
-        keys = ("out", "gates", "h_prev")
-        recs = [dict(zip(keys, rec[:3])), dict(zip(keys, rec[3:]))]
-        dgs = gru_hip_backward((dout_a, dout_c), dones, (w_hh_a, w_hh_c), recs)
+        cell = ctx.cell
+        x_a, x_c, dones, w_hh_a, w_hh_c, *saved = ctx.saved_tensors
+        recs = _records(cell, saved)
+        dgs = hip_backward(cell, (dout_a, dout_c), dones, (w_hh_a, w_hh_c), recs)
         grads = []
-        for x, (dig, dhg), r in zip((x_a, x_c), dgs, recs):
-            grads += _gru_finish(x, dig, dhg, r["h_prev"])
-        return (None,) * 5 + tuple(grads)
+        for x, dg, rec in zip((x_a, x_c), dgs, recs):
+            grads += _finish(cell, x, dg, rec["h_prev"])
+        return (None,) * (4 + 2 * len(cell.state)) + tuple(grads)
 
 
-def unsupported(memory_a, memory_c, obs=None, critic_obs=None, kernels: bool = True, gru_memories: bool = False) -> str | None:
-    """Why `PPO(fused_recurrent_update=True)` and `memory_rollout_sequence` refuse these memories / rows (None: they do not):
-    include/lt_memory_seq.h covers two single-layer LSTMs with biases of one hidden size, a multiple of 64 in [64, 512], with
-    I + H <= 1248, on observation rows - BOTH tensors - of the memories' dtype (the HIP form itself: f32 on a GPU, `serves`; the
-    PyTorch-op form covers the same set on the CPU and in other dtypes).  `kernels=False`: what the PyTorch-op form refuses as well - all
-    of the above but the bounds on the sizes.  `gru_memories=True` (the opt-in `fused_gru_memories`): two GRUs of the same description
-    are served as well (include/lt_memory_gru.h), one LSTM beside one GRU is not."""
-    kind = type(getattr(memory_a, "rnn", None)) if gru_memories and _is_gru(memory_a) else torch.nn.LSTM
+# ---- what is served, and the entry point ----------------------------------------------------------------------------------------------
+def memories_unsupported(memory_a, memory_c, gru_memories: bool = False, kernels: bool = True, layer_count: bool = False) -> str | None:
+    """What `unsupported` here and `recurrent_unsupported` of rl/fused.py ask of the memories themselves (None: nothing is amiss): both of
+    the one kind `cell_of(memory_a)` names, single-layer and plain, and - `kernels` - of one hidden size within the limits of the
+    headers.  `layer_count`: the message about the layers ends in the number the memory has."""
+    kind = cell_of(memory_a, gru_memories).nn
     for name, m in (("memory_a", memory_a), ("memory_c", memory_c)):
         rnn = getattr(m, "rnn", None)
         if not isinstance(rnn, kind):
@@ -368,8 +334,8 @@ def unsupported(memory_a, memory_c, obs=None, critic_obs=None, kernels: bool = T
                 return f"{name} is a {type(rnn).__name__} beside a {kind.__name__}: the two memories must be of one kind"
             return f"{name} is a {type(rnn).__name__}: only LSTM memories are served"
         if rnn.num_layers != 1 or rnn.bidirectional or rnn.batch_first or not rnn.bias or getattr(rnn, "proj_size", 0) != 0:
-            return (f"{name} must be a single-layer, unidirectional, time-major {kind.__name__} with biases and without projection "
-                    f"(it has {rnn.num_layers} layers)")
+            return (f"{name} must be a single-layer, unidirectional, time-major {kind.__name__} with biases and without projection"
+                    + (f" (it has {rnn.num_layers} layers)" if layer_count else ""))
         h = rnn.hidden_size
         if not kernels:
             continue
@@ -379,14 +345,23 @@ def unsupported(memory_a, memory_c, obs=None, critic_obs=None, kernels: bool = T
             return f"{name}: input size + hidden size exceeds {MAX_K}"
     if memory_a.rnn.hidden_size != memory_c.rnn.hidden_size:
         return "the two memories differ in hidden size"
+    return None
+
+
+def unsupported(memory_a, memory_c, obs=None, critic_obs=None, kernels: bool = True, gru_memories: bool = False) -> str | None:
+    """Why `PPO(fused_recurrent_update=True)` and `memory_rollout_sequence` refuse these memories / rows (None: they do not):
+    include/lt_memory_seq.h covers two single-layer LSTMs with biases of one hidden size, a multiple of 64 in [64, 512], with
+    I + H <= 1248, on observation rows - BOTH tensors - of the memories' dtype (the HIP form itself: f32 on a GPU, `serves`; the
+    PyTorch-op form covers the same set on the CPU and in other dtypes).  `kernels=False`: what the PyTorch-op form refuses as well - all
+    of the above but the bounds on the sizes.  `gru_memories=True` (the opt-in `fused_gru_memories`): two GRUs of the same description
+    are served as well (include/lt_memory_gru.h), one LSTM beside one GRU is not."""
+    why = memories_unsupported(memory_a, memory_c, gru_memories=gru_memories, kernels=kernels, layer_count=True)
+    if why is not None:
+        return why
     for what, rows, m in (("observation", obs, memory_a), ("critic observation", critic_obs, memory_c)):
         if rows is not None and rows.dtype != m.rnn.weight_ih_l0.dtype:
             return f"{str(rows.dtype).replace('torch.', '')} {what} rows: the memories read rows of their own dtype (f32 on the GPU)"
     return None
-
-
-def _is_gru(memory) -> bool:
-    return isinstance(getattr(memory, "rnn", None), torch.nn.GRU)
 
 
 def serves(memory_a, memory_c, obs: torch.Tensor, critic_obs: torch.Tensor | None = None, gru_memories: bool = False) -> bool:
@@ -399,33 +374,28 @@ def serves(memory_a, memory_c, obs: torch.Tensor, critic_obs: torch.Tensor | Non
 
 def memory_rollout_sequence(memory_a, memory_c, obs, critic_obs, dones, hc0_a, hc0_c, gru_memories: bool = False):
     """(out_a, out_c), each [T, E, H]: `memory_a` over obs [T, E, I_a] and `memory_c` over critic_obs [T, E, I_c] for the whole rollout of
-    an env block, from the states hc0_* = (h0, c0) saved at step 0 ([1, E, H] or [E, H]); the carried state is replaced by zeros wherever
-    dones[t - 1] ([T, E] or [T, E, 1], any integer or bool dtype; None: no reset) is set.
+    an env block, from the states hc0_* saved at step 0 (a tuple of the cell's state tensors, (h0, c0) or (h0,), each [1, E, H] or [E, H];
+    for a GRU the tensor h0 itself will do); the carried state is replaced by zeros wherever dones[t - 1] ([T, E] or [T, E, 1], any
+    integer or bool dtype; None: no reset) is set.
 
     obs / critic_obs may be views `storage[:, e0:e1]`: the forward pass reads them in place.  The weight gradient dW_ih = dgates^T X
     wants contiguous rows, though, so the BACKWARD pass of a call on such a view copies the block (`reshape`) each time; a caller that
     runs the same blocks more than once hands over contiguous copies made once, as `PPO._recurrent_update` does per update.
 
-    Rows whose dtype is not the memories' own, GRU or multi-layer memories raise `ValueError`; there is no quiet change of path on them.
-    The HIP form runs where `serves` says so, the PyTorch-op form elsewhere (the CPU, other dtypes, `use_hip_kernels` off).
-
-    `gru_memories=True`: two GRU memories are served too; hc0_* is then the one state tensor h0 ([1, E, H] or [E, H], or a 1-tuple)."""
+    Rows whose dtype is not the memories' own, multi-layer memories, and GRU memories without `gru_memories=True` raise `ValueError`;
+    there is no quiet change of path on them.  The HIP form runs where `serves` says so, the PyTorch-op form elsewhere (the CPU, other
+    dtypes, `use_hip_kernels` off)."""
     T, E, _ = obs.shape
     why = unsupported(memory_a, memory_c, obs, critic_obs, kernels=False, gru_memories=gru_memories)  # (a size outside the kernels' set has the PyTorch-op form)
     if why is not None:
         raise ValueError(f"memory_rollout_sequence: {why}")
+    cell = cell_of(memory_a, gru_memories)
     d = _dones2d(dones, T, E)
-    if gru_memories and _is_gru(memory_a):
-        states = (_gru_state(hc0_a, E), _gru_state(hc0_c, E))
-        params = (*_params(memory_a), *_params(memory_c))
-        if serves(memory_a, memory_c, obs, critic_obs, gru_memories=True):
-            return _GruMemorySeqHip.apply(obs, critic_obs, _dones_bytes(d), *states, *params)
-        return _GruMemorySeq.apply(obs, critic_obs, d, *states, *params)
-    states = (*_state(hc0_a, E), *_state(hc0_c, E))
+    states = (*_state(cell, hc0_a, E), *_state(cell, hc0_c, E))
     params = (*_params(memory_a), *_params(memory_c))
-    if serves(memory_a, memory_c, obs, critic_obs):
-        return _MemorySeqHip.apply(obs, critic_obs, _dones_bytes(d), *states, *params)
-    return _MemorySeq.apply(obs, critic_obs, d, *states, *params)
+    if serves(memory_a, memory_c, obs, critic_obs, gru_memories=gru_memories):
+        return _SeqHip.apply(cell, obs, critic_obs, _dones_bytes(d), *states, *params)
+    return _SeqOps.apply(cell, obs, critic_obs, d, *states, *params)
 
 
 # False: `memory_rollout_sequence` takes the PyTorch-op time loop on the GPU as well.

@@ -48,13 +48,13 @@ def test_update_with_the_switches_on_is_as_close_to_float64_as_the_eager_update(
     on = twin(src, "cuda:0", torch.float32, **ON)
     assert on.fused_recurrent_update and on.fused_gru_memories and not off.fused_recurrent_update and on._flat_adam is not None
     calls = {"hip": 0}
-    forward = memory_seq.gru_hip_forward
+    forward = memory_seq.hip_forward
 
     def counted(*a, **k):
         calls["hip"] += 1
         return forward(*a, **k)
 
-    monkeypatch.setattr(memory_seq, "gru_hip_forward", counted)
+    monkeypatch.setattr(memory_seq, "hip_forward", counted)
     r_ref, r_off, r_on = ref._eager_update(), off._eager_update(), on.update()
     torch.cuda.synchronize()
     assert calls["hip"] == 4  # 2 epochs x 2 mini-batches went through csrc/lt_memory_gru.hip
@@ -95,7 +95,7 @@ def test_learn_iteration_with_all_three_switches_on(monkeypatch):
     runner = make_runner(64, fused_recurrent_update=True)
     assert runner.alg.fused_recurrent_update and runner.alg.fused_gru_memories and runner._make_fused() is not None
     calls = {"hip": 0}
-    forward = memory_seq.gru_hip_forward
+    forward = memory_seq.hip_forward
 
     def counted(*a, **k):
         calls["hip"] += 1
@@ -104,7 +104,7 @@ def test_learn_iteration_with_all_three_switches_on(monkeypatch):
     def no_padding(self, *a, **k):
         raise AssertionError("recurrent_mini_batches ran with fused_recurrent_update on")
 
-    monkeypatch.setattr(memory_seq, "gru_hip_forward", counted)
+    monkeypatch.setattr(memory_seq, "hip_forward", counted)
     monkeypatch.setattr(RolloutStorage, "recurrent_mini_batches", no_padding)
     before = [p.detach().clone() for p in runner.alg.actor_critic.parameters()]
     runner.learn(1)

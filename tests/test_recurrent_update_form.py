@@ -7,7 +7,7 @@ import copy
 import pytest
 import torch
 
-from locotouch_amd.rl import PPO
+from locotouch_amd.rl import PPO, memory_seq
 from locotouch_amd.rl.memory_seq import memory_rollout_sequence
 from locotouch_amd.rl.modules import ActorCriticRecurrent
 from locotouch_amd.rl.storage import Batch
@@ -133,3 +133,24 @@ def test_the_switch_refuses_what_it_does_not_serve():
     alg.init_storage(N, T, [OBS], [COBS], [ACT], obs_dtype=torch.bfloat16)
     with pytest.raises(ValueError, match="bfloat16"):
         alg.update()
+
+
+@pytest.mark.parametrize("cell", [memory_seq.LSTM, memory_seq.GRU], ids=["lstm", "gru"])
+def test_the_cell_table_names_only_what_the_headers_declare(cell):
+    """A field or an entry point renamed in include/lt_memory*.h fails here, not first in a launch on the GPU."""
+    from locotouch_amd import _abi
+
+    def fields(struct):
+        return [f for f, _ in struct._fields_]
+
+    shared = ["w_ih", "w_hh", "b_ih", "b_hh"]
+    record, dgates, short = [k for k, _ in cell.record], [k for k, _ in cell.dgates], [s[0] for s in cell.state]
+    assert set(fields(cell.seq_net)) == {"x", "x_stride", "I", *shared, *cell.state, *record}
+    assert set(fields(cell.seq_grad)) == {"dout", "w_hh", *cell.reads, *dgates, cell.carry}
+    assert set(cell.reads) <= set(record) and {cell.d_ih, cell.d_hh} == set(dgates) and record[0] == "out" and "h_prev" in record
+    # rl/fused.py fills the step structure by position
+    assert fields(cell.step_net) == ["x", "I", *shared, *(f"{s}_in" for s in short), *(f"{s}_out" for s in short), *(f"saved_{s}" for s in short)]
+    signatures = {**_abi.MEMORY_SIGNATURES, **_abi.MEMORY_SEQ_SIGNATURES, **_abi.MEMORY_GRU_SIGNATURES}
+    for name in (cell.step, cell.finish, cell.seq_forward, cell.seq_backward, cell.backward_units):
+        assert name in signatures, name
+    assert len(signatures[cell.finish][1]) == 4 * len(cell.state) + 4  # raw and masked state of both memories, dones, N, H, stream
