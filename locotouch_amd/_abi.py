@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lt_env.h and loader of the HIP library (the product path).
+"""ctypes mirror of include/lt_env.h and the headers beside it (one table, `HEADERS`), and loader of the HIP library (the product path).
 
 Everything is parsed mechanically from the header - the `LT_*` constants, every structure and the signature of every entry
 point - so the Python mirror cannot drift from the C ABI (a size check against `lt_cfg_sizeof()` guards it at load time) and
@@ -14,19 +14,6 @@ import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(_HERE)
-HEADER = os.path.join(REPO, "include", "lt_env.h")
-OBS_NORM_HEADER = os.path.join(REPO, "include", "lt_obs_norm.h")  # included by lt_env.h: the observation normaliser's entry points
-STUDENT_HEADER = os.path.join(REPO, "include", "lt_student.h")  # included by lt_env.h: the fused student inference step
-COLLECT_HEADER = os.path.join(REPO, "include", "lt_collect.h")  # included by lt_env.h: the tactile delay line and the step recording
-LEDGER_HEADER = os.path.join(REPO, "include", "lt_ledger.h")  # included by lt_env.h: the episode ledger of collection and evaluation
-CNN_TRAIN_HEADER = os.path.join(REPO, "include", "lt_cnn_train.h")  # the training form of the student's tactile CNN head
-BC_HEADER = os.path.join(REPO, "include", "lt_bc.h")  # included by lt_env.h: batch assembly, masked loss and AdamW of the student's BC step
-LSTM_HEADER = os.path.join(REPO, "include", "lt_lstm.h")  # included by lt_env.h: the LSTM recurrence over whole trajectories
-MEMORY_HEADER = os.path.join(REPO, "include", "lt_memory.h")  # included by lt_env.h: one rollout step of a recurrent policy's two LSTM memories
-MEMORY_SEQ_HEADER = os.path.join(REPO, "include", "lt_memory_seq.h")  # a header of its own: the two memories over a whole rollout, forward and backward
-MEMORY_GRU_HEADER = os.path.join(REPO, "include", "lt_memory_gru.h")  # a header of its own: GRU memories, one rollout step and whole rollouts
-POLICY_HEADER = os.path.join(REPO, "include", "lt_policy.h")  # a header of its own: one inference step of a recurrent policy
-PPO_OPTS_HEADER = os.path.join(REPO, "include", "lt_ppo_opts.h")  # included by lt_env.h: the log-std policy and per-minibatch advantage statistics
 LIB_PATH = os.environ.get("LOCOTOUCH_AMD_LIB", os.path.join(_HERE, "_lib", "liblocotouch_env.so"))
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint8_t": ctypes.c_uint8,
@@ -128,123 +115,68 @@ class _CfgMethods(ctypes.Structure):
         return {name: py(getattr(self, name)) for name, *_ in self._fields_ if not name.startswith("_")}
 
 
-CONSTS, STRUCTS, SIGNATURES = parse_header(open(HEADER).read(), bases={"lt_cfg": _CfgMethods})
-globals().update(CONSTS)
-LtCfg, LtView, LtMlpDesc = STRUCTS["lt_cfg"], STRUCTS["lt_view"], STRUCTS["lt_mlp_desc"]
-LtRenderView, LtRenderDesc = STRUCTS["lt_render_view"], STRUCTS["lt_render_desc"]
-EXPORTS = list(SIGNATURES)
-OBS_NORM_SIGNATURES = parse_header(open(OBS_NORM_HEADER).read())[2]  # all status-returning: launched through `call`
-if any(r is not ctypes.c_int for r, _ in OBS_NORM_SIGNATURES.values()) or set(OBS_NORM_SIGNATURES) & set(EXPORTS):
-    raise ImportError("include/lt_obs_norm.h: every entry point returns a status and none repeats one of lt_env.h")
-
-# Entry points that return a VALUE, not an LT_* status (the header's types cannot tell the two apart): never through `call`.
-VALUE_QUERIES = frozenset({
+# Entry points of lt_env.h that return a VALUE, not an LT_* status (the header's types cannot tell the two apart): never through `call`.
+_ENV_VALUE_QUERIES = (
     "lt_abi_version", "lt_cfg_sizeof", "lt_cfg_num_presets", "lt_cfg_preset_id", "lt_cfg_obs_dim", "lt_cfg_tactile_dim", "lt_last_error",
     "lt_wgrad_splits", "lt_wgrad_ws_floats", "lt_elu_backward_bias_ws_floats", "lt_head_wgrad_ws_floats", "lt_adam_clip_step_ws_floats",
-    "lt_elu_backward_bias_nblk", "lt_head_wgrad_nblk", "lt_mlp_backward_blocks", "lt_env_kernel_name", "lt_mlp_kernel_name"})
-if not VALUE_QUERIES <= set(EXPORTS) or any(SIGNATURES[n][0] is not ctypes.c_int for n in set(EXPORTS) - VALUE_QUERIES):
-    raise ImportError("_abi.VALUE_QUERIES does not match include/lt_env.h: a query it names is gone, or a new entry point returns no status")
+    "lt_elu_backward_bias_nblk", "lt_head_wgrad_nblk", "lt_mlp_backward_blocks", "lt_env_kernel_name", "lt_mlp_kernel_name")
 
-# include/lt_student.h: constants and structures of its own (CONSTS / STRUCTS stay those of lt_env.h); STUDENT_VALUE_QUERIES is to
-# this header what VALUE_QUERIES is to lt_env.h
-STUDENT_CONSTS, _student_structs, STUDENT_SIGNATURES = parse_header(open(STUDENT_HEADER).read(), structs=STRUCTS)
-globals().update(STUDENT_CONSTS)
-LtStudentDesc, LtStudentParams = _student_structs["lt_student_desc"], _student_structs["lt_student_params"]
-STUDENT_VALUE_QUERIES = frozenset({"lt_student_step_launches"})
-if (not STUDENT_VALUE_QUERIES <= set(STUDENT_SIGNATURES) or any(r is not ctypes.c_int for r, _ in STUDENT_SIGNATURES.values())
-        or set(STUDENT_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES))):
-    raise ImportError("_abi.STUDENT_VALUE_QUERIES does not match include/lt_student.h, or an entry point there returns no int or repeats "
-                      "one of another header")
+# THE TABLE: one row per header of the C ABI, bound in this order.  A row is (public prefix, file under include/, whether the header may
+# use lt_env.h's structures, its value queries, the structures published as Lt* classes).  A header with prefix P is published as
+# P_HEADER (its path), P_CONSTS, P_SIGNATURES and P_VALUE_QUERIES; lt_env.h has no prefix (HEADER, CONSTS, SIGNATURES, VALUE_QUERIES,
+# and STRUCTS, EXPORTS).  Every header's LT_* constants are module globals as well.  Adding a header is adding a row.
+HEADERS = (
+    ("", "lt_env.h", False, _ENV_VALUE_QUERIES, ("lt_cfg", "lt_view", "lt_mlp_desc", "lt_render_view", "lt_render_desc")),
+    ("OBS_NORM", "lt_obs_norm.h", False, (), ()),  # the observation normaliser
+    ("STUDENT", "lt_student.h", True, ("lt_student_step_launches",), ("lt_student_desc", "lt_student_params")),  # the fused student inference step
+    ("COLLECT", "lt_collect.h", False, (), ()),  # the tactile delay line and the step recording
+    ("LEDGER", "lt_ledger.h", False, (), ()),  # the episode ledger of collection and evaluation; LEDGER_CONSTS: the head's field indices
+    ("CNN_TRAIN", "lt_cnn_train.h", False, ("lt_cnn_launches",), ("lt_cnn_desc", "lt_cnn_params", "lt_cnn_grads")),  # the tactile CNN head, training form
+    ("BC", "lt_bc.h", False, (), ()),  # batch assembly, masked loss and AdamW of the student's BC step; BC_CONSTS: the stats record's field indices
+    ("LSTM", "lt_lstm.h", False, (), ()),  # the LSTM recurrence over whole trajectories
+    ("MEMORY", "lt_memory.h", False, (), ("lt_memory_net",)),  # one rollout step of a recurrent policy's two LSTM memories
+    ("MEMORY_SEQ", "lt_memory_seq.h", False, ("lt_memory_seq_backward_units",), ("lt_memory_seq_net", "lt_memory_seq_grad")),  # the two memories over a whole rollout
+    ("MEMORY_GRU", "lt_memory_gru.h", False, ("lt_memory_gru_seq_backward_units",),
+     ("lt_memory_gru_net", "lt_memory_gru_seq_net", "lt_memory_gru_seq_grad")),  # GRU memories, one rollout step and whole rollouts
+    ("POLICY", "lt_policy.h", True, ("lt_policy_step_launches",), ("lt_policy_desc", "lt_policy_memory")),  # one inference step of a recurrent policy
+    ("PPO_OPTS", "lt_ppo_opts.h", False, (), ()),  # the log-std policy and per-minibatch advantage statistics
+)
 
-# include/lt_collect.h: all status-returning, launched (or, for the size query, called) through `call`
-COLLECT_SIGNATURES = parse_header(open(COLLECT_HEADER).read())[2]
-if (any(r is not ctypes.c_int for r, _ in COLLECT_SIGNATURES.values())
-        or set(COLLECT_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES))):
-    raise ImportError("include/lt_collect.h: every entry point returns a status and none repeats one of another header")
 
-# include/lt_ledger.h: all status-returning, launched (or, for the size query, called) through `call`; LEDGER_CONSTS: the head's field indices
-LEDGER_CONSTS, _, LEDGER_SIGNATURES = parse_header(open(LEDGER_HEADER).read())
-if (any(r is not ctypes.c_int for r, _ in LEDGER_SIGNATURES.values())
-        or set(LEDGER_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES))):
-    raise ImportError("include/lt_ledger.h: every entry point returns a status and none repeats one of another header")
+def _bind(table, include_dir):
+    """Parse every header of `table` (rows as in HEADERS), in order: one (path, constants, structures, signatures, value queries) per row.
+    ImportError, naming the header and the entry point, if a value query of the row is not declared in its header, if an entry point
+    returns no int (in lt_env.h: one that is no value query - there a query may return a size or a string), or if a name repeats one of an
+    earlier header."""
+    bound, seen, env_structs = [], set(), None
+    for prefix, fname, uses_env_structs, queries, _ in table:
+        path, queries = os.path.join(include_dir, fname), frozenset(queries)
+        consts, structs, sigs = parse_header(open(path).read(), structs=env_structs if uses_env_structs else None, bases={"lt_cfg": _CfgMethods})
+        if not prefix:
+            env_structs = structs
+        for name in sorted(queries - set(sigs)):
+            raise ImportError(f"include/{fname}: the value query {name} named in _abi.HEADERS is not declared there")
+        for name, (restype, _) in sigs.items():
+            if name in seen:
+                raise ImportError(f"include/{fname}: {name} repeats an entry point of an earlier header")
+            if restype is not ctypes.c_int and (prefix or name not in queries):
+                raise ImportError(f"include/{fname}: {name} returns no int (a new value query of lt_env.h belongs in _abi.HEADERS)")
+        seen.update(sigs)
+        bound.append((path, consts, structs, sigs, queries))
+    return bound
 
-# include/lt_cnn_train.h: constants and structures of its own; CNN_TRAIN_VALUE_QUERIES is to this header what VALUE_QUERIES is to lt_env.h
-CNN_TRAIN_CONSTS, _cnn_structs, CNN_TRAIN_SIGNATURES = parse_header(open(CNN_TRAIN_HEADER).read())
-globals().update(CNN_TRAIN_CONSTS)
-LtCnnDesc, LtCnnParams, LtCnnGrads = _cnn_structs["lt_cnn_desc"], _cnn_structs["lt_cnn_params"], _cnn_structs["lt_cnn_grads"]
-CNN_TRAIN_VALUE_QUERIES = frozenset({"lt_cnn_launches"})
-if (not CNN_TRAIN_VALUE_QUERIES <= set(CNN_TRAIN_SIGNATURES) or any(r is not ctypes.c_int for r, _ in CNN_TRAIN_SIGNATURES.values())
-        or set(CNN_TRAIN_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                        | set(LEDGER_SIGNATURES))):
-    raise ImportError("_abi.CNN_TRAIN_VALUE_QUERIES does not match include/lt_cnn_train.h, or an entry point there returns no int or "
-                      "repeats one of another header")
 
-# include/lt_bc.h: all status-returning, launched (or, for the size query, called) through `call`; BC_CONSTS: the stats record's field indices
-BC_CONSTS, _, BC_SIGNATURES = parse_header(open(BC_HEADER).read())
-if (any(r is not ctypes.c_int for r, _ in BC_SIGNATURES.values())
-        or set(BC_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                 | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES))):
-    raise ImportError("include/lt_bc.h: every entry point returns a status and none repeats one of another header")
-
-# include/lt_lstm.h: all status-returning, launched through `call`
-LSTM_SIGNATURES = parse_header(open(LSTM_HEADER).read())[2]
-if (any(r is not ctypes.c_int for r, _ in LSTM_SIGNATURES.values())
-        or set(LSTM_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                   | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES))):
-    raise ImportError("include/lt_lstm.h: every entry point returns a status and none repeats one of another header")
-
-# include/lt_memory.h: a structure of its own (one memory's operands); all status-returning, launched through `call`
-_, _memory_structs, MEMORY_SIGNATURES = parse_header(open(MEMORY_HEADER).read())
-LtMemoryNet = _memory_structs["lt_memory_net"]
-if (any(r is not ctypes.c_int for r, _ in MEMORY_SIGNATURES.values())
-        or set(MEMORY_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                     | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES))):
-    raise ImportError("include/lt_memory.h: every entry point returns a status and none repeats one of another header")
-
-# include/lt_memory_seq.h (not included by lt_env.h): two structures of its own; all status-returning, launched through `call`
-_, _memory_seq_structs, MEMORY_SEQ_SIGNATURES = parse_header(open(MEMORY_SEQ_HEADER).read())
-LtMemorySeqNet, LtMemorySeqGrad = _memory_seq_structs["lt_memory_seq_net"], _memory_seq_structs["lt_memory_seq_grad"]
-MEMORY_SEQ_VALUE_QUERIES = frozenset({"lt_memory_seq_backward_units"})  # to this header what VALUE_QUERIES is to lt_env.h
-if (not MEMORY_SEQ_VALUE_QUERIES <= set(MEMORY_SEQ_SIGNATURES) or any(r is not ctypes.c_int for r, _ in MEMORY_SEQ_SIGNATURES.values())
-        or set(MEMORY_SEQ_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                         | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES)
-                                         | set(MEMORY_SIGNATURES))):
-    raise ImportError("_abi.MEMORY_SEQ_VALUE_QUERIES does not match include/lt_memory_seq.h, or an entry point there returns no int or "
-                      "repeats one of another header")
-
-# include/lt_memory_gru.h (not included by lt_env.h): four structures of its own; all status-returning but the one value query
-_, _memory_gru_structs, MEMORY_GRU_SIGNATURES = parse_header(open(MEMORY_GRU_HEADER).read())
-LtMemoryGruNet, LtMemoryGruSeqNet, LtMemoryGruSeqGrad = (_memory_gru_structs[k] for k in ("lt_memory_gru_net", "lt_memory_gru_seq_net",
-                                                                                           "lt_memory_gru_seq_grad"))
-MEMORY_GRU_VALUE_QUERIES = frozenset({"lt_memory_gru_seq_backward_units"})  # to this header what VALUE_QUERIES is to lt_env.h
-if (not MEMORY_GRU_VALUE_QUERIES <= set(MEMORY_GRU_SIGNATURES) or any(r is not ctypes.c_int for r, _ in MEMORY_GRU_SIGNATURES.values())
-        or set(MEMORY_GRU_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                         | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES)
-                                         | set(MEMORY_SIGNATURES) | set(MEMORY_SEQ_SIGNATURES))):
-    raise ImportError("_abi.MEMORY_GRU_VALUE_QUERIES does not match include/lt_memory_gru.h, or an entry point there returns no int or "
-                      "repeats one of another header")
-
-# include/lt_policy.h (not included by lt_env.h): constants and two structures of its own (lt_mlp_desc is lt_env.h's); POLICY_VALUE_QUERIES
-# is to this header what VALUE_QUERIES is to lt_env.h
-POLICY_CONSTS, _policy_structs, POLICY_SIGNATURES = parse_header(open(POLICY_HEADER).read(), structs=STRUCTS)
-globals().update(POLICY_CONSTS)
-LtPolicyDesc, LtPolicyMemory = _policy_structs["lt_policy_desc"], _policy_structs["lt_policy_memory"]
-POLICY_VALUE_QUERIES = frozenset({"lt_policy_step_launches"})
-if (not POLICY_VALUE_QUERIES <= set(POLICY_SIGNATURES) or any(r is not ctypes.c_int for r, _ in POLICY_SIGNATURES.values())
-        or set(POLICY_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                     | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES)
-                                     | set(MEMORY_SIGNATURES) | set(MEMORY_SEQ_SIGNATURES) | set(MEMORY_GRU_SIGNATURES))):
-    raise ImportError("_abi.POLICY_VALUE_QUERIES does not match include/lt_policy.h, or an entry point there returns no int or repeats "
-                      "one of another header")
-
-# include/lt_ppo_opts.h: all status-returning, launched through `call`
-PPO_OPTS_SIGNATURES = parse_header(open(PPO_OPTS_HEADER).read())[2]
-if (any(r is not ctypes.c_int for r, _ in PPO_OPTS_SIGNATURES.values())
-        or set(PPO_OPTS_SIGNATURES) & (set(EXPORTS) | set(OBS_NORM_SIGNATURES) | set(STUDENT_SIGNATURES) | set(COLLECT_SIGNATURES)
-                                       | set(LEDGER_SIGNATURES) | set(CNN_TRAIN_SIGNATURES) | set(BC_SIGNATURES) | set(LSTM_SIGNATURES)
-                                       | set(MEMORY_SIGNATURES) | set(MEMORY_SEQ_SIGNATURES) | set(MEMORY_GRU_SIGNATURES)
-                                       | set(POLICY_SIGNATURES))):
-    raise ImportError("include/lt_ppo_opts.h: every entry point returns a status and none repeats one of another header")
+ALL_SIGNATURES: dict = {}  # every header's entry points in one map (no name repeats: _bind), and the value queries among them
+ALL_VALUE_QUERIES: set = set()
+for (_prefix, _, _, _, _published), (_path, _consts, _structs, _sigs, _queries) in zip(HEADERS, _bind(HEADERS, os.path.join(REPO, "include"))):
+    _p = _prefix + "_" if _prefix else ""
+    globals().update(_consts)
+    globals().update({_p + "HEADER": _path, _p + "CONSTS": _consts, _p + "SIGNATURES": _sigs, _p + "VALUE_QUERIES": _queries})
+    globals().update({_structs[_c].__name__: _structs[_c] for _c in _published})  # lt_cfg -> LtCfg
+    if not _prefix:
+        STRUCTS, EXPORTS = _structs, list(_sigs)
+    ALL_SIGNATURES.update(_sigs)
+    ALL_VALUE_QUERIES |= _queries
 
 _lib = None
 _calls: dict = {}  # status-returning entry point -> (function, per-argument converter or None), filled by load()
@@ -259,14 +191,10 @@ def load() -> ctypes.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP extension is mandatory, there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**SIGNATURES, **OBS_NORM_SIGNATURES, **STUDENT_SIGNATURES, **COLLECT_SIGNATURES, **LEDGER_SIGNATURES,
-                                      **CNN_TRAIN_SIGNATURES, **BC_SIGNATURES, **LSTM_SIGNATURES, **MEMORY_SIGNATURES,
-                                      **MEMORY_SEQ_SIGNATURES, **MEMORY_GRU_SIGNATURES, **POLICY_SIGNATURES,
-                                      **PPO_OPTS_SIGNATURES}.items():
+    for name, (restype, argtypes) in ALL_SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
-        if (name not in VALUE_QUERIES and name not in STUDENT_VALUE_QUERIES and name not in CNN_TRAIN_VALUE_QUERIES
-                and name not in MEMORY_SEQ_VALUE_QUERIES and name not in MEMORY_GRU_VALUE_QUERIES and name not in POLICY_VALUE_QUERIES):
+        if name not in ALL_VALUE_QUERIES:
             _calls[name] = (fn, [ptr if t is ctypes.c_void_p else _ref if issubclass(t, ctypes._Pointer) and issubclass(t._type_, ctypes.Structure)
                                  else None for t in argtypes])
     if lib.lt_cfg_sizeof() != ctypes.sizeof(LtCfg):
@@ -307,8 +235,7 @@ def call(name: str, *args) -> None:
     try:
         fn, conv = _calls[name]
     except KeyError:
-        if (name in VALUE_QUERIES or name in STUDENT_VALUE_QUERIES or name in CNN_TRAIN_VALUE_QUERIES or name in MEMORY_SEQ_VALUE_QUERIES
-                or name in MEMORY_GRU_VALUE_QUERIES or name in POLICY_VALUE_QUERIES):
+        if name in ALL_VALUE_QUERIES:
             raise TypeError(f"{name} returns a value, not a status: call load().{name}(...)") from None
         if _lib is not None:
             raise

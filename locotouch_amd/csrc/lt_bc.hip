@@ -15,8 +15,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 namespace {
@@ -227,24 +227,6 @@ __global__ __launch_bounds__(TPB) void lt_adamw_kernel(const AdamwArgs a) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
-int refuse(const char* fn, const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s", fn, what);
-  lt_set_error(msg);  // (copies)
-  return LT_EINVAL;
-}
-
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", fn, hipGetErrorString(e));
-    lt_set_error(msg);
-    return LT_EHIP;
-  }
-  return LT_OK;
-}
-
 bool misaligned(const void* p, size_t bytes) { return (uintptr_t)p % bytes != 0; }
 
 // floats per vector for rows of `width` floats that start at a and at b: the widest of 4, 2, 1 that divides the width and both alignments
@@ -290,7 +272,7 @@ int lt_bc_gather(const float* policy, const float* tactile, int64_t rows_total, 
   a.vec_pe = row_vec(pe, policy, pol);
   a.vec_td = row_vec(td, tactile, tac);
   hipLaunchKernelGGL(lt_bc_gather_kernel, dim3((unsigned)((a.R + NW - 1) / NW)), dim3(TPB), 0, (hipStream_t)stream, a);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 int lt_bc_loss_ws_floats(int64_t R, size_t* floats) {
@@ -320,9 +302,9 @@ int lt_bc_loss_forward(const float* pred, const float* target, int64_t W, const 
   a.R = R; a.W = W; a.A = sa_or_null ? A : W; a.clip_range = clip_range;
   const int64_t nblk = loss_groups(R);
   hipLaunchKernelGGL(lt_bc_loss_partial_kernel, dim3((unsigned)nblk), dim3(TPB), 0, (hipStream_t)stream, a);
-  if (int rc = launched(fn)) return rc;
+  if (int rc = launch_status(fn)) return rc;
   hipLaunchKernelGGL(lt_bc_loss_finish_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, (const float*)ws, (long long)nblk, action_scale, stats);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 int lt_bc_loss_backward(const float* pred, const float* target, int64_t W, const uint8_t* mask, int64_t R, const float* g, const float* stats,
@@ -346,7 +328,7 @@ int lt_bc_loss_backward(const float* pred, const float* target, int64_t W, const
   else
     hipLaunchKernelGGL(lt_bc_loss_backward_kernel<1>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, pred, target, mask, g, stats, d_pred,
                        (long long)R, (long long)W);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 int lt_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
@@ -375,7 +357,7 @@ int lt_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_
     hipLaunchKernelGGL(lt_adamw_kernel<4>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(lt_adamw_kernel<1>, dim3((unsigned)blocks), dim3(TPB), 0, (hipStream_t)stream, a);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 }  // extern "C"

@@ -22,10 +22,10 @@
 //   input gradient   a "full" convolution of dz with the flipped weights in the forward's form: a lane owns one (image, input position),
 //             a wave six input channels, so the weights are wave-uniform (scalar loads; the pack writes an [oc][k][k][ic] copy for it).
 #include <hip/hip_runtime.h>
-#include <stdio.h>
 
 #include "../../include/lt_cnn_train.h"
 #include "lt_cnn_device.h"
+#include "lt_host_check.h"
 
 static_assert(LT_CNN_MAX_CONVS == LT_STUDENT_MAX_CONVS && LT_CNN_TILE == LT_STUDENT_ENV_TILE, "lt_cnn_train.h mirrors lt_student.h");
 
@@ -290,21 +290,9 @@ struct Plan : Geometry {
   int map_off[NL], g_off[2], demb_off, arg_off[MAXC], bwd_bytes, split[NL];
 };
 
-int refuse(const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "lt_cnn_desc: %s", what);
-  lt_set_error(msg);
-  return LT_EINVAL;
-}
-
-int einval(const char* msg) {
-  lt_set_error(msg);
-  return LT_EINVAL;
-}
-
 int plan_of(const lt_cnn_desc* d, Plan* L) {
-  if (!d) return refuse("desc is NULL");
-  if (const char* why = geometry_of(d, L)) return refuse(why);
+  if (!d) return refuse("lt_cnn_desc", "desc is NULL");
+  if (const char* why = geometry_of(d, L)) return refuse("lt_cnn_desc", why);
   const int nc = d->num_convs, D = d->head_out;
   size_t off = 0;
   auto take = [&](size_t floats) { const size_t at = off; off += (floats + 3) & ~(size_t)3; return at; };
@@ -338,7 +326,7 @@ int plan_of(const lt_cnn_desc* d, Plan* L) {
     if (L->pool[l] == 2) lds += pad4(ET * L->c[l + 1] * L->h[l + 1] * L->w[l + 1]) / 4;
   }
   L->bwd_bytes = lds * (int)sizeof(float);
-  if (L->bwd_bytes > MAX_LDS) return refuse("img_height / img_width / conv_channels: the maps and gradient maps of 8 images do not fit in LDS");
+  if (L->bwd_bytes > MAX_LDS) return refuse("lt_cnn_desc", "img_height / img_width / conv_channels: the maps and gradient maps of 8 images do not fit in LDS");
   return LT_OK;
 }
 
@@ -347,15 +335,6 @@ int slabs_of(int64_t n, int* tiles_per_slab, int* tiles) {
   *tiles = (int)t;
   *tiles_per_slab = (int)per;
   return (int)((t + per - 1) / per);
-}
-
-int hip_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return LT_OK;
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-  lt_set_error(msg);
-  return LT_EHIP;
 }
 
 bool complete(const lt_cnn_desc* d, const float* const* w, const float* const* b, const float* hw, const float* hb) {
@@ -385,7 +364,7 @@ int pack(const lt_cnn_desc* d, const Plan& L, const lt_cnn_params* p, float* ws,
   e->hw = ws + L.fw[nc]; e->hb = p->head_b;
   const int blocks = (most + TPB - 1) / TPB;
   hipLaunchKernelGGL(lt_cnn_pack_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)a.nseg), dim3(TPB), 0, stream, a);
-  return hip_status("lt_cnn_pack");
+  return launch_status("lt_cnn_pack");
 }
 
 }  // namespace
@@ -424,7 +403,7 @@ int lt_cnn_forward(const lt_cnn_desc* desc, const lt_cnn_params* p, const float*
   if (L.enc_bytes > 64 * 1024)
     if (const int err = lt_ensure_dynamic_lds((const void*)lt_cnn_forward_kernel, MAX_LDS)) { lt_set_error(lt_hip_error_string(err)); return LT_EHIP; }
   hipLaunchKernelGGL(lt_cnn_forward_kernel, dim3((unsigned)((n + ET - 1) / ET)), dim3(TPB), (size_t)L.enc_bytes, (hipStream_t)stream, e);
-  return hip_status("lt_cnn_forward");
+  return launch_status("lt_cnn_forward");
 }
 
 int lt_cnn_backward(const lt_cnn_desc* desc, const lt_cnn_params* p, const float* x, const float* d_emb, int64_t n, const lt_cnn_grads* grads,
@@ -459,7 +438,7 @@ int lt_cnn_backward(const lt_cnn_desc* desc, const lt_cnn_params* p, const float
     if (const int err = lt_ensure_dynamic_lds((const void*)lt_cnn_backward_kernel, MAX_LDS)) { lt_set_error(lt_hip_error_string(err)); return LT_EHIP; }
   hipLaunchKernelGGL(lt_cnn_backward_kernel, dim3((unsigned)slabs), dim3(BT), (size_t)L.bwd_bytes, (hipStream_t)stream, b);
   hipLaunchKernelGGL(lt_cnn_reduce_kernel, dim3((unsigned)((L.part_floats + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, r);
-  return hip_status("lt_cnn_backward");
+  return launch_status("lt_cnn_backward");
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@
 
 #include <cstdio>
 
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 namespace {
@@ -145,13 +146,6 @@ __global__ __launch_bounds__(STEP_TPB) void lt_collect_after_step_kernel(const S
   }
 }
 
-int refuse(const char* fn, const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s", fn, what);
-  lt_set_error(msg);  // (copies)
-  return LT_EINVAL;
-}
-
 size_t ring_bytes(int64_t n, int64_t d, int64_t depth) { return ((size_t)4 * (size_t)n * (size_t)depth * (size_t)d + 15) & ~(size_t)15; }
 
 // n, d, depth >= 1, the products in range (the ring below 2^62 bytes, the grids below 2^31 workgroups)
@@ -187,17 +181,6 @@ void split_state(void* state, int64_t n, int64_t d, int64_t depth, float** ring,
   *head = (int*)((char*)state + ring_bytes(n, d, depth));
   *count = *head + n;
   *delay = *count + n;
-}
-
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", fn, hipGetErrorString(e));
-    lt_set_error(msg);
-    return LT_EHIP;
-  }
-  return LT_OK;
 }
 
 int push_or_read(const char* fn, void* state, int64_t n, int64_t d, int64_t depth, const float* rows, int64_t rows_stride, float* out0,
@@ -239,7 +222,7 @@ int push_or_read(const char* fn, void* state, int64_t n, int64_t d, int64_t dept
   if (vec == 4) hipLaunchKernelGGL(lt_delay_push_kernel<4>, grid, dim3(TPB), 0, (hipStream_t)stream, a);
   else if (vec == 2) hipLaunchKernelGGL(lt_delay_push_kernel<2>, grid, dim3(TPB), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(lt_delay_push_kernel<1>, grid, dim3(TPB), 0, (hipStream_t)stream, a);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 }  // namespace
@@ -263,7 +246,7 @@ int lt_delay_reset(void* state, int64_t n, int64_t d, int64_t depth, const uint8
   split_state(state, n, d, depth, &ring, &head, &a.count, &a.delay);
   a.mask = mask_or_null; a.fresh = (const long long*)fresh_delays; a.n = n;
   hipLaunchKernelGGL(lt_collect_after_step_kernel, dim3((unsigned)((n + STEP_TPB - 1) / STEP_TPB)), dim3(STEP_TPB), 0, (hipStream_t)stream, a);
-  return launched("lt_delay_reset");
+  return launch_status("lt_delay_reset");
 }
 
 int lt_delay_push(void* state, int64_t n, int64_t d, int64_t depth, const float* rows, int64_t rows_stride, float* out0, int64_t out0_stride,
@@ -298,7 +281,7 @@ int lt_collect_after_step(void* state_or_null, int64_t n, int64_t d, int64_t dep
   a.reward = reward; a.dones = (const long long*)dones; a.fresh = (const long long*)fresh_delays;
   a.reward_out = reward_out; a.done_out = done_mask_out; a.n = n;
   hipLaunchKernelGGL(lt_collect_after_step_kernel, dim3((unsigned)((n + STEP_TPB - 1) / STEP_TPB)), dim3(STEP_TPB), 0, (hipStream_t)stream, a);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// Host-side helpers of the recurrent translation units (lt_memory_tile.h's and lt_seq_tile.h's entry points, lt_policy.hip): the named
-// refusal of an argument before anything is launched, and the status of the launches issued.  Internal: an unnamed namespace.
+// Host-side checks of every translation unit that answers with an LT_* status: the refusal of an argument before anything is launched
+// (three forms, by how the unit words its message) and the status of the launches issued.  Internal: an unnamed namespace.  The
+// launchers that hand back a raw hipError_t (lt_internal.h) do not come through here.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,12 +12,24 @@
 
 namespace {
 
+// LT_EINVAL with `msg` as it stands
+int einval(const char* msg) {
+  lt_set_error(msg);  // (copies)
+  return LT_EINVAL;
+}
+
+// LT_EINVAL with "<fn>: <what>"
+int refuse(const char* fn, const char* what) {
+  char msg[256];
+  snprintf(msg, sizeof msg, "%s: %s", fn, what);
+  return einval(msg);
+}
+
 // LT_EINVAL with "<fn>: invalid argument: <who><field> must be <what>"
 int refuse(const char* fn, const char* who, const char* field, const char* what) {
   char msg[256];
   snprintf(msg, sizeof msg, "%s: invalid argument: %s%s must be %s", fn, who, field, what);
-  lt_set_error(msg);
-  return LT_EINVAL;
+  return einval(msg);
 }
 
 struct ptr_check { const char* name; const void* p; int align; };
@@ -32,10 +45,14 @@ template <int n> int check_ptrs(const char* fn, const char* who, const ptr_check
   return LT_OK;
 }
 
-int launch_status() {
+// LT_EHIP if a launch since the last look failed, with the HIP error string - behind "<fn>: " where the unit names its entry point
+int launch_status(const char* fn = nullptr) {
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  if (e == hipSuccess) return LT_OK;
+  char msg[256];
+  if (fn) snprintf(msg, sizeof msg, "%s: %s", fn, hipGetErrorString(e));
+  lt_set_error(fn ? msg : hipGetErrorString(e));
+  return LT_EHIP;
 }
 
 }  // namespace

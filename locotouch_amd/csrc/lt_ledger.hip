@@ -18,8 +18,7 @@
 // No atomics, no float arithmetic other than the one f64 add per env and the f32 <-> f64 conversions at the two ends.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 namespace {
@@ -163,24 +162,6 @@ __global__ __launch_bounds__(ROW_TPB) void lt_ledger_end_kernel(const double* su
   if (e < n) out[e] = (float)sum[e];
 }
 
-int refuse(const char* fn, const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s", fn, what);
-  lt_set_error(msg);  // (copies)
-  return LT_EINVAL;
-}
-
-int launched(const char* fn) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: %s", fn, hipGetErrorString(e));
-    lt_set_error(msg);
-    return LT_EHIP;
-  }
-  return LT_OK;
-}
-
 const char* bad_state(const void* state, int64_t n) {
   if (n < 1 || n > INT32_MAX) return "n must be in [1, 2^31)";
   if (!state || (uintptr_t)state % 16) return "state must be non-null and 16-byte aligned";
@@ -218,7 +199,7 @@ int lt_ledger_begin(void* state, int64_t n, const float* reward_sums_in_or_null,
   split_state(state, n, &head, &sum, &start);
   hipLaunchKernelGGL(lt_ledger_begin_kernel, dim3(row_grid(n)), dim3(ROW_TPB), 0, (hipStream_t)stream, head, sum, start, reward_sums_in_or_null,
                      (long long)n, (long long)(keep_target < 0 ? -1 : keep_target), (long long)(episode_target < 0 ? -1 : episode_target));
-  return launched(fn);
+  return launch_status(fn);
 }
 
 int lt_ledger_step(void* state, int64_t n, const float* reward, const uint8_t* done, double* ep_reward, int64_t* ep_length, int64_t ep_first,
@@ -239,7 +220,7 @@ int lt_ledger_step(void* state, int64_t n, const float* reward, const uint8_t* d
   a.reward = reward; a.done = done; a.ep_reward = ep_reward; a.ep_length = (long long*)ep_length; a.traj = (long long*)traj;
   a.n = n; a.ep_first = ep_first; a.ep_cap = ep_reward && ep_length ? ep_cap : 0; a.traj_first = traj_first; a.traj_cap = traj_cap;
   hipLaunchKernelGGL(lt_ledger_step_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, a);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 int lt_ledger_end(const void* state, int64_t n, float* reward_sums_out, void* stream) {
@@ -250,7 +231,7 @@ int lt_ledger_end(const void* state, int64_t n, float* reward_sums_out, void* st
   double* sum;
   split_state((void*)state, n, &head, &sum, &start);
   hipLaunchKernelGGL(lt_ledger_end_kernel, dim3(row_grid(n)), dim3(ROW_TPB), 0, (hipStream_t)stream, (const double*)sum, reward_sums_out, (long long)n);
-  return launched(fn);
+  return launch_status(fn);
 }
 
 }  // extern "C"

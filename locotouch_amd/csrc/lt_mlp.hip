@@ -59,6 +59,7 @@
 #include <utility>
 
 #include "lt_device_math.h"
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 using namespace lt;
@@ -1235,18 +1236,18 @@ int lt_debug_mlp_stamps(unsigned long long* host) {
 #endif
 
 int lt_mlp_packed_floats(const lt_mlp_desc* desc, size_t* floats) {
-  if (!desc_ok(desc) || !floats) { lt_set_error("lt_mlp_packed_floats: unsupported network shape"); return LT_EINVAL; }
+  if (!desc_ok(desc) || !floats) return einval("lt_mlp_packed_floats: unsupported network shape");
   *floats = (size_t)geometry(desc).total_chunks * 256;
   return LT_OK;
 }
 
 int lt_mlp_pack(const lt_mlp_desc* desc, const float* const* weights, const float* const* biases, float* packed, void* stream) {
-  if (!desc_ok(desc) || !weights || !biases || !packed) { lt_set_error("lt_mlp_pack: invalid argument"); return LT_EINVAL; }
+  if (!desc_ok(desc) || !weights || !biases || !packed) return einval("lt_mlp_pack: invalid argument");
   const Geometry g = geometry(desc);
   long long bias_off = 0, most = 0;
   PackAll all = {};
   for (int l = 0; l < desc->num_layers; ++l) {
-    if (!weights[l] || !biases[l]) { lt_set_error("lt_mlp_pack: null layer pointer"); return LT_EINVAL; }
+    if (!weights[l] || !biases[l]) return einval("lt_mlp_pack: null layer pointer");
     PackArgs& p = all.layer[l];
     p.w = weights[l]; p.b = biases[l]; p.K = desc->dims[l]; p.N = desc->dims[l + 1]; p.packed = packed;
     for (int w = 0; w < NW; ++w) p.chunk_off[w] = g.layer_off[l][w];
@@ -1258,13 +1259,11 @@ int lt_mlp_pack(const lt_mlp_desc* desc, const float* const* weights, const floa
     most = total > most ? total : most;
   }
   hipLaunchKernelGGL(lt_mlp_pack_kernel<PackAll>, dim3((unsigned)((most + 255) / 256), (unsigned)desc->num_layers), dim3(256), 0, (hipStream_t)stream, all);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 int lt_mlp_forward(const lt_mlp_desc* desc, const float* packed, const float* x, int64_t m, float* y, void* stream) {
-  if (!desc_ok(desc) || !packed || !x || !y || m <= 0) { lt_set_error("lt_mlp_forward: invalid argument"); return LT_EINVAL; }
+  if (!desc_ok(desc) || !packed || !x || !y || m <= 0) return einval("lt_mlp_forward: invalid argument");
   DualArgs d = {};
   fill_args(desc, d.net[0]);
   d.net[0].mode = MODE_FORWARD;
@@ -1277,10 +1276,8 @@ int lt_mlp_forward(const lt_mlp_desc* desc, const float* packed, const float* x,
 // (acts0[l], acts1[l]: [m][dims[l + 1]], l < L - 1; hidden widths must be multiples of 4).
 int lt_mlp_forward_pair(const lt_mlp_desc* d0, const float* packed0, const float* x0, const lt_mlp_desc* d1, const float* packed1, const float* x1,
                         int64_t m, float* y0, float* y1, float* const* acts0, float* const* acts1, int acts_split, void* stream) {
-  if (!desc_ok(d0) || !desc_ok(d1) || !packed0 || !packed1 || !x0 || !x1 || !y0 || !y1 || !acts0 || !acts1 || m <= 0) {
-    lt_set_error("lt_mlp_forward_pair: invalid argument");
-    return LT_EINVAL;
-  }
+  if (!desc_ok(d0) || !desc_ok(d1) || !packed0 || !packed1 || !x0 || !x1 || !y0 || !y1 || !acts0 || !acts1 || m <= 0)
+    return einval("lt_mlp_forward_pair: invalid argument");
   DualArgs d = {};
   const lt_mlp_desc* ds[2] = {d0, d1};
   const float* pk[2] = {packed0, packed1};
@@ -1292,7 +1289,7 @@ int lt_mlp_forward_pair(const lt_mlp_desc* d0, const float* packed0, const float
     d.net[k].mode = MODE_FORWARD;
     d.net[k].packed = pk[k]; d.net[k].x = xs[k]; d.net[k].m = m; d.net[k].y = ys[k]; d.net[k].acts_split = acts_split != 0;
     for (int l = 0; l + 1 < ds[k]->num_layers; ++l) {
-      if (!as[k][l] || (ds[k]->dims[l + 1] & 3)) { lt_set_error("lt_mlp_forward_pair: hidden widths must be multiples of 4 and every activation buffer given"); return LT_EINVAL; }
+      if (!as[k][l] || (ds[k]->dims[l + 1] & 3)) return einval("lt_mlp_forward_pair: hidden widths must be multiples of 4 and every activation buffer given");
       d.net[k].act_out[l] = as[k][l];
     }
   }
@@ -1302,10 +1299,8 @@ int lt_mlp_forward_pair(const lt_mlp_desc* d0, const float* packed0, const float
 int lt_rollout_policy(const lt_mlp_desc* actor, const float* packed, const float* obs, int64_t n, uint64_t seed, const int64_t* step_counter,
                       int64_t step_offset, const float* std12, float* st_actions, float* st_mu, float* st_sigma, float* st_logp,
                       float* actions_out, void* stream) {
-  if (!policy_args_ok(actor, packed, obs, n, step_counter, std12, st_actions, st_mu, st_sigma, st_logp, actions_out)) {
-    lt_set_error("lt_rollout_policy: invalid argument (the policy head must have 12 outputs)");
-    return LT_EINVAL;
-  }
+  if (!policy_args_ok(actor, packed, obs, n, step_counter, std12, st_actions, st_mu, st_sigma, st_logp, actions_out))
+    return einval("lt_rollout_policy: invalid argument (the policy head must have 12 outputs)");
   DualArgs d = {};
   fill_policy(actor, packed, obs, n, seed, step_counter, step_offset, std12, st_actions, st_mu, st_sigma, st_logp, actions_out, d.net[0]);
   return launch(d, 1, (hipStream_t)stream);
@@ -1316,10 +1311,8 @@ int lt_rollout_policy_value(const lt_mlp_desc* actor, const float* actor_packed,
                             const int64_t* step_counter, int64_t step_offset, const float* std12, float* st_actions, float* st_mu,
                             float* st_sigma, float* st_logp, float* actions_out, void* stream) {
   if (!policy_args_ok(actor, actor_packed, obs, n, step_counter, std12, st_actions, st_mu, st_sigma, st_logp, actions_out) || !desc_ok(critic) ||
-      !critic_packed || !critic_obs || !values) {
-    lt_set_error("lt_rollout_policy_value: invalid argument");
-    return LT_EINVAL;
-  }
+      !critic_packed || !critic_obs || !values)
+    return einval("lt_rollout_policy_value: invalid argument");
   DualArgs d = {};
   fill_policy(actor, actor_packed, obs, n, seed, step_counter, step_offset, std12, st_actions, st_mu, st_sigma, st_logp, actions_out, d.net[0]);
   fill_args(critic, d.net[1]);
@@ -1376,20 +1369,20 @@ const char* lt_mlp_kernel_name(const lt_mlp_desc* d0, const lt_mlp_desc* d1, int
 // weight-gradient kernel lt_wgrad reads it) together with the per-workgroup max |dz_l| lt_wgrad scales by.
 int lt_mlp_backward_packed_floats(const lt_mlp_desc* fwd, size_t* floats) {
   lt_mlp_desc bd;
-  if (!fwd || !floats || !backward_desc(fwd, &bd)) { lt_set_error("lt_mlp_backward_packed_floats: needs an ELU network of >= 2 layers, hidden widths multiples of 8, <= 64 outputs"); return LT_EINVAL; }
+  if (!fwd || !floats || !backward_desc(fwd, &bd)) return einval("lt_mlp_backward_packed_floats: needs an ELU network of >= 2 layers, hidden widths multiples of 8, <= 64 outputs");
   *floats = (size_t)geometry(&bd).total_chunks * 256;
   return LT_OK;
 }
 
 int lt_mlp_pack_backward(const lt_mlp_desc* fwd, const float* const* weights, float* packed, void* stream) {
   lt_mlp_desc bd;
-  if (!fwd || !weights || !packed || !backward_desc(fwd, &bd)) { lt_set_error("lt_mlp_pack_backward: invalid argument"); return LT_EINVAL; }
+  if (!fwd || !weights || !packed || !backward_desc(fwd, &bd)) return einval("lt_mlp_pack_backward: invalid argument");
   const Geometry g = geometry(&bd);
   const int L = fwd->num_layers;
   long long bias_off = 0, most = 0;
   PackAll all = {};
   for (int j = 0; j < bd.num_layers; ++j) {
-    if (!weights[L - 1 - j]) { lt_set_error("lt_mlp_pack_backward: null layer pointer"); return LT_EINVAL; }
+    if (!weights[L - 1 - j]) return einval("lt_mlp_pack_backward: null layer pointer");
     PackArgs& p = all.layer[j];
     p.w = weights[L - 1 - j]; p.b = nullptr; p.K = bd.dims[j]; p.N = bd.dims[j + 1]; p.transposed = 1; p.packed = packed;
     for (int w = 0; w < NW; ++w) p.chunk_off[w] = g.layer_off[j][w];
@@ -1401,9 +1394,7 @@ int lt_mlp_pack_backward(const lt_mlp_desc* fwd, const float* const* weights, fl
     most = total > most ? total : most;
   }
   hipLaunchKernelGGL(lt_mlp_pack_kernel<PackAll>, dim3((unsigned)((most + 255) / 256), (unsigned)bd.num_layers), dim3(256), 0, (hipStream_t)stream, all);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 // workgroups per network of lt_mlp_backward_pair over m rows = entries of every amax array it writes
@@ -1429,7 +1420,7 @@ int lt_mlp_backward_pair(const lt_mlp_desc* fwd0, const float* bpacked0, const f
                          void* stream) {
   lt_mlp_desc bd[2];
   const float* ia[2] = {in_amax0, in_amax1};
-  if (dz_split && (!in_amax0 || !in_amax1 || !scales_out)) { lt_set_error("lt_mlp_backward_pair: a split dz needs the global input maxima and scales_out"); return LT_EINVAL; }
+  if (dz_split && (!in_amax0 || !in_amax1 || !scales_out)) return einval("lt_mlp_backward_pair: a split dz needs the global input maxima and scales_out");
   const lt_mlp_desc* fw[2] = {fwd0, fwd1};
   const float* pk[2] = {bpacked0, bpacked1};
   const float* dy[2] = {dy0, dy1};
@@ -1438,12 +1429,10 @@ int lt_mlp_backward_pair(const lt_mlp_desc* fwd0, const float* bpacked0, const f
   float* const* am[2] = {amax0, amax1};
   DualArgs d = {};
   for (int k = 0; k < 2; ++k) {
-    if (!fw[k] || !pk[k] || !dy[k] || !ac[k] || !dz[k] || !am[k] || m <= 0 || !backward_desc(fw[k], &bd[k])) {
-      lt_set_error("lt_mlp_backward_pair: invalid argument");
-      return LT_EINVAL;
-    }
+    if (!fw[k] || !pk[k] || !dy[k] || !ac[k] || !dz[k] || !am[k] || m <= 0 || !backward_desc(fw[k], &bd[k]))
+      return einval("lt_mlp_backward_pair: invalid argument");
     for (int l = 0; l + 1 < fw[k]->num_layers; ++l)
-      if (!ac[k][l] || !dz[k][l] || !am[k][l]) { lt_set_error("lt_mlp_backward_pair: null layer buffer"); return LT_EINVAL; }
+      if (!ac[k][l] || !dz[k][l] || !am[k][l]) return einval("lt_mlp_backward_pair: null layer buffer");
     fill_backward(&bd[k], fw[k]->num_layers, pk[k], dy[k], m, ac[k], dz[k], am[k], sat_count, d.net[k]);
     d.net[k].acts_split = acts_split != 0;
     d.net[k].in_amax = ia[k]; d.net[k].dz_split = dz_split != 0; d.net[k].scale_out = scales_out ? scales_out + k : nullptr;
@@ -1466,24 +1455,22 @@ int lt_mlp_pack_training(const lt_mlp_desc* d0, const float* const* weights0, co
   int n = 0;
   long long most = 0;
   for (int k = 0; k < 2; ++k) {
-    if (!desc_ok(ds[k]) || !ws[k] || !bs[k] || !pk[k]) { lt_set_error("lt_mlp_pack_training: invalid argument"); return LT_EINVAL; }
+    if (!desc_ok(ds[k]) || !ws[k] || !bs[k] || !pk[k]) return einval("lt_mlp_pack_training: invalid argument");
     for (int l = 0; l < ds[k]->num_layers; ++l)
-      if (!ws[k][l] || !bs[k][l]) { lt_set_error("lt_mlp_pack_training: null layer pointer"); return LT_EINVAL; }
+      if (!ws[k][l] || !bs[k][l]) return einval("lt_mlp_pack_training: null layer pointer");
     const long long m = fill_pack_forward(ds[k], ws[k], bs[k], pk[k], all.layer + n);
     most = m > most ? m : most;
     n += ds[k]->num_layers;
     if (bp[k]) {
       lt_mlp_desc bd;
-      if (!backward_desc(ds[k], &bd)) { lt_set_error("lt_mlp_pack_training: the network has no backward stream (lt_mlp_backward_packed_floats)"); return LT_EINVAL; }
+      if (!backward_desc(ds[k], &bd)) return einval("lt_mlp_pack_training: the network has no backward stream (lt_mlp_backward_packed_floats)");
       const long long mb = fill_pack_backward(ds[k], bd, ws[k], bp[k], all.layer + n);
       most = mb > most ? mb : most;
       n += bd.num_layers;
     }
   }
   hipLaunchKernelGGL(lt_mlp_pack_kernel<PackMany>, dim3((unsigned)((most + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, all);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 }  // extern "C"

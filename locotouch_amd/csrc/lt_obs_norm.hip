@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lt_device_prims.h"
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 namespace {
@@ -289,10 +290,7 @@ int nparts_of(int64_t n) { return (int)((n + STAT_ROWS - 1) / STAT_ROWS); }
 extern "C" {
 
 int lt_obs_norm_ws_floats(int64_t n, int d, size_t* floats) {
-  if (n <= 0 || n > INT32_MAX || d <= 0 || d > MAX_D || !floats) {
-    lt_set_error("lt_obs_norm_ws_floats: n must be in [1, 2^31) and d in [1, 1024]");
-    return LT_EINVAL;
-  }
+  if (n <= 0 || n > INT32_MAX || d <= 0 || d > MAX_D || !floats) return einval("lt_obs_norm_ws_floats: n must be in [1, 2^31) and d in [1, 1024]");
   *floats = (size_t)WS_HEAD + ((size_t)WS_FIXED + 4 * (size_t)nparts_of(n)) * dpad_of(d);
   return LT_OK;
 }
@@ -302,10 +300,7 @@ int lt_obs_norm_update(int64_t n, int merge, int64_t until, double eps,
                        const float* rows1, int d1, float* mean1, float* var1, float* std1, int64_t* count1, float* snap1, float* out1, float* ws1,
                        void* stream) {
   const int nets = d1 ? 2 : 1;
-  if (n <= 0 || n > INT32_MAX || !(eps > 0.0)) {
-    lt_set_error("lt_obs_norm_update: n must be in [1, 2^31) and eps positive");
-    return LT_EINVAL;
-  }
+  if (n <= 0 || n > INT32_MAX || !(eps > 0.0)) return einval("lt_obs_norm_update: n must be in [1, 2^31) and eps positive");
   Args a;
   a.n = n; a.until = until; a.eps = eps; a.merge = merge ? 1 : 0; a.nparts = nparts_of(n);
   const int64_t fr = (n + 63) / 64;  // at most 64 row blocks merge the partials again
@@ -321,11 +316,9 @@ int lt_obs_norm_update(int64_t n, int merge, int64_t until, double eps,
     Net& t = a.net[i];
     if (i >= nets) { t = a.net[0]; continue; }
     if (d[i] <= 0 || d[i] > MAX_D || !rows[i] || !mean[i] || !var[i] || !sd[i] || !count[i] || !snap[i] || (merge && !ws[i]) ||
-        (merge && (uintptr_t)ws[i] % 16)) {
-      lt_set_error("lt_obs_norm_update: d must be in [1, 1024]; rows, mean, var, std, count and snapshot non-null; the workspace "
-                   "non-null and 16-byte aligned when merging");
-      return LT_EINVAL;
-    }
+        (merge && (uintptr_t)ws[i] % 16))
+      return einval("lt_obs_norm_update: d must be in [1, 1024]; rows, mean, var, std, count and snapshot non-null; the workspace "
+                    "non-null and 16-byte aligned when merging");
     t.x = rows[i]; t.d = d[i]; t.dpad = dpad_of(d[i]); t.vec = vec_of(d[i], rows[i], out[i]);
     t.mean = mean[i]; t.var = var[i]; t.stdv = sd[i]; t.count = (long long*)count[i]; t.snap = snap[i]; t.out = out[i]; t.ws = ws[i];
     const int c = (d[i] / t.vec + CG - 1) / CG;
@@ -336,18 +329,14 @@ int lt_obs_norm_update(int64_t n, int merge, int64_t until, double eps,
     hipLaunchKernelGGL(lt_obs_norm_stats_kernel, dim3((unsigned)a.nparts, (unsigned)chunks, (unsigned)nets), dim3(TPB), 0, (hipStream_t)stream, a);
   const unsigned row_blocks = any_out ? (unsigned)((n + a.finish_rows - 1) / a.finish_rows) : 1u;
   hipLaunchKernelGGL(lt_obs_norm_finish_kernel, dim3(row_blocks, (unsigned)chunks, (unsigned)nets), dim3(TPB), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 int lt_obs_norm_apply(const float* rows, int64_t nrows, int d, const float* snaps, int64_t snap_stride, int64_t rows_per_snap, float* out,
                       void* stream) {
   if (!rows || !out || !snaps || nrows <= 0 || d <= 0 || d > MAX_D || rows_per_snap <= 0 || snap_stride < 0 ||
-      (nrows + APPLY_ROWS - 1) / APPLY_ROWS > INT32_MAX) {
-    lt_set_error("lt_obs_norm_apply: rows, snapshots and out non-null; nrows, rows_per_snap positive; d in [1, 1024]");
-    return LT_EINVAL;
-  }
+      (nrows + APPLY_ROWS - 1) / APPLY_ROWS > INT32_MAX)
+    return einval("lt_obs_norm_apply: rows, snapshots and out non-null; nrows, rows_per_snap positive; d in [1, 1024]");
   ApplyArgs a;
   a.x = rows; a.out = out; a.snaps = snaps; a.nrows = nrows; a.snap_stride = snap_stride; a.rows_per_snap = rows_per_snap; a.d = d;
   const int vec = vec_of(d, rows, out);
@@ -355,9 +344,7 @@ int lt_obs_norm_apply(const float* rows, int64_t nrows, int d, const float* snap
   if (vec == 4) hipLaunchKernelGGL(lt_obs_norm_apply_kernel<4>, grid, dim3(TPB), 0, (hipStream_t)stream, a);
   else if (vec == 2) hipLaunchKernelGGL(lt_obs_norm_apply_kernel<2>, grid, dim3(TPB), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(lt_obs_norm_apply_kernel<1>, grid, dim3(TPB), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 }  // extern "C"

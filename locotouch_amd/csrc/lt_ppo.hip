@@ -524,12 +524,10 @@ __global__ __launch_bounds__(64) void lt_ppo_lr_rule_kernel(const float* __restr
 
 extern "C" int lt_ppo_lr_rule(const float* kl_mean, float desired_kl, float lr_min, float lr_max, float factor, float* lr, float* stats,
                               const float* scalars, float* dstd_out, int num_actions, void* stream) {
-  if (!lr || factor <= 1.f || num_actions < 0 || num_actions > MAX_A) { lt_set_error("lt_ppo_lr_rule: invalid argument"); return LT_EINVAL; }
+  if (!lr || factor <= 1.f || num_actions < 0 || num_actions > MAX_A) return einval("lt_ppo_lr_rule: invalid argument");
   hipLaunchKernelGGL(lt_ppo_lr_rule_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kl_mean, desired_kl, lr_min, lr_max, factor, lr, stats, scalars,
                      dstd_out, num_actions);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 static int elu_backward_bias(const float* da, const float* a, int64_t M, int N, float alpha, float* dz, float* db, float* ws, float* amax, void* stream);
@@ -542,25 +540,19 @@ extern "C" int lt_elu_backward_bias2(const float* da, const float* a, int64_t M,
   return elu_backward_bias(da, a, M, N, alpha, dz, db, ws, amax_blocks, stream);
 }
 static int elu_backward_bias(const float* da, const float* a, int64_t M, int N, float alpha, float* dz, float* db, float* ws, float* amax, void* stream) {
-  if (!da || !a || !dz || !ws || M < 1 || N < 4 || (N & 3) || N > 1024) {
-    lt_set_error("lt_elu_backward_bias: invalid argument (N a multiple of 4, 4 <= N <= 1024)");
-    return LT_EINVAL;
-  }
+  if (!da || !a || !dz || !ws || M < 1 || N < 4 || (N & 3) || N > 1024)
+    return einval("lt_elu_backward_bias: invalid argument (N a multiple of 4, 4 <= N <= 1024)");
   const int nblk = (int)((M + EB_ROWS - 1) / EB_ROWS);
   hipLaunchKernelGGL(lt_elu_bwd_bias_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, da, a, (long long)M, N, alpha, dz, ws, amax);
   if (db) launch_one_sum(ws, nblk, (long long)N, N, N, db, nullptr, (hipStream_t)stream);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 extern "C" int64_t lt_head_wgrad_ws_floats(int64_t M, int n, int k) { return ((M + HW_ROWS - 1) / HW_ROWS) * ((int64_t)n * k + HW_MAX_N); }
 
 extern "C" int lt_head_wgrad(const float* dy, const float* x, int x_split, int64_t M, int n, int k, float* dw, float* db, float* ws, void* stream) {
-  if (!dy || !x || !ws || M < 1 || n < 1 || n > HW_MAX_N || k < 4 || (k & 3) || k > 1024) {
-    lt_set_error("lt_head_wgrad: invalid argument (1 <= n <= 16, k a multiple of 4, 4 <= k <= 1024)");
-    return LT_EINVAL;
-  }
+  if (!dy || !x || !ws || M < 1 || n < 1 || n > HW_MAX_N || k < 4 || (k & 3) || k > 1024)
+    return einval("lt_head_wgrad: invalid argument (1 <= n <= 16, k a multiple of 4, 4 <= k <= 1024)");
   const int nblk = (int)((M + HW_ROWS - 1) / HW_ROWS), k4 = k / 4, lanes = 256 / k4;
   const int nn = n <= 1 ? 1 : (n <= 4 ? 4 : (n <= 8 ? 8 : (n <= 12 ? 12 : 16)));
   const size_t lds = (size_t)lanes * nn * k4 * 16 + (size_t)lanes * nn * 4;
@@ -569,10 +561,7 @@ extern "C" int lt_head_wgrad(const float* dy, const float* x, int x_split, int64
     lt_set_error(hipGetErrorString((hipError_t)e));
     return LT_EHIP;
   }
-  if (lds > 72 * 1024) {
-    lt_set_error("lt_head_wgrad: n * k too large for one block's LDS partials");
-    return LT_EINVAL;
-  }
+  if (lds > 72 * 1024) return einval("lt_head_wgrad: n * k too large for one block's LDS partials");
   const dim3 g((unsigned)nblk), b(256);
   hipStream_t st = (hipStream_t)stream;
   switch (nn) {
@@ -583,9 +572,7 @@ extern "C" int lt_head_wgrad(const float* dy, const float* x, int x_split, int64
     default: hipLaunchKernelGGL(lt_head_wgrad_kernel<16>, g, b, lds, st, dy, x, x_split, (long long)M, n, k, ws); break;
   }
   if (dw) launch_one_sum(ws, nblk, (long long)n * k + HW_MAX_N, n * k + n, n * k, dw, db, st);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 // Partial-sum jobs in one launch: out0[j][e] = sum_b ws[j][b * stride[j] + e] for e < split[j], out1[j][e - split[j]] for split[j] <= e <
@@ -593,15 +580,13 @@ extern "C" int lt_head_wgrad(const float* dy, const float* x, int x_split, int64
 // lt_head_wgrad (dw == NULL: lt_head_wgrad_nblk(M) blocks of n * k + 16, split n * k) and of split-K GEMM slabs.
 extern "C" int lt_partial_sums(int njobs, const float* const* ws, const int* nblk, const int64_t* stride, const int* count, const int* split,
                                float* const* out0, float* const* out1, void* stream) {
-  if (njobs < 1 || njobs > SUM_MAX_JOBS || !ws || !nblk || !stride || !count || !split || !out0 || !out1) {
-    lt_set_error("lt_partial_sums: invalid argument (1 <= njobs <= 24)");
-    return LT_EINVAL;
-  }
+  if (njobs < 1 || njobs > SUM_MAX_JOBS || !ws || !nblk || !stride || !count || !split || !out0 || !out1)
+    return einval("lt_partial_sums: invalid argument (1 <= njobs <= 24)");
   SumJobs J = {};
   J.njobs = njobs;
   int blocks = 0;
   for (int j = 0; j < njobs; ++j) {
-    if (!ws[j] || !out0[j] || nblk[j] < 1 || count[j] < 1) { lt_set_error("lt_partial_sums: invalid job"); return LT_EINVAL; }
+    if (!ws[j] || !out0[j] || nblk[j] < 1 || count[j] < 1) return einval("lt_partial_sums: invalid job");
     J.ws[j] = ws[j]; J.out0[j] = out0[j]; J.out1[j] = out1[j]; J.stride[j] = stride[j];
     J.nblk[j] = nblk[j]; J.count[j] = count[j]; J.split[j] = split[j];
     J.first[j] = blocks;
@@ -610,24 +595,17 @@ extern "C" int lt_partial_sums(int njobs, const float* const* ws, const int* nbl
   }
   J.first[njobs] = blocks;
   hipLaunchKernelGGL(lt_partial_sums_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, J);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 extern "C" int lt_elu_backward_bias_nblk(int64_t M) { return (int)((M + EB_ROWS - 1) / EB_ROWS); }
 extern "C" int lt_head_wgrad_nblk(int64_t M) { return (int)((M + HW_ROWS - 1) / HW_ROWS); }
 
 extern "C" int lt_gae(const float* rewards, const uint8_t* dones, const float* values, const float* last_values, float gamma, float lam, int T,
                       int64_t N, float* returns, float* advantages, void* stream) {
-  if (!rewards || !dones || !values || !last_values || !returns || !advantages || T < 1 || N < 1) {
-    lt_set_error("lt_gae: invalid argument");
-    return LT_EINVAL;
-  }
+  if (!rewards || !dones || !values || !last_values || !returns || !advantages || T < 1 || N < 1) return einval("lt_gae: invalid argument");
   hipLaunchKernelGGL(lt_gae_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rewards, dones, values, last_values, gamma,
                      lam, T, (long long)N, returns, advantages);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 extern "C" int64_t lt_elu_backward_bias_ws_floats(int64_t M, int N) { return ((M + EB_ROWS - 1) / EB_ROWS) * (int64_t)N; }
@@ -642,24 +620,19 @@ extern "C" int lt_adam_clip_step(float* params, float* grads, float* exp_avg, fl
 
 extern "C" int lt_adam_clip_step_dev(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float max_norm, const float* lr_dev,
                                      float beta1, float beta2, float eps, float weight_decay, int64_t step, float* ws, float* grad_norm, void* stream) {
-  if (!lr_dev) { lt_set_error("lt_adam_clip_step_dev: null learning-rate pointer"); return LT_EINVAL; }
+  if (!lr_dev) return einval("lt_adam_clip_step_dev: null learning-rate pointer");
   return adam_clip_step(params, grads, exp_avg, exp_avg_sq, n, max_norm, 0.f, lr_dev, beta1, beta2, eps, weight_decay, step, ws, grad_norm, stream);
 }
 
 static int adam_clip_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float max_norm, float lr, const float* lr_dev,
                           float beta1, float beta2, float eps, float weight_decay, int64_t step, float* ws, float* grad_norm, void* stream) {
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !ws || n < 1 || step < 1) {
-    lt_set_error("lt_adam_clip_step: invalid argument");
-    return LT_EINVAL;
-  }
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !ws || n < 1 || step < 1) return einval("lt_adam_clip_step: invalid argument");
   const int nblk = (int)((n + AD_PER_BLOCK - 1) / AD_PER_BLOCK);
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(lt_sumsq_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, grads, (long long)n, ws);
   hipLaunchKernelGGL(lt_adam_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, (long long)n, ws, nblk,
                      max_norm, beta1, beta2, eps, weight_decay, (float)((double)lr / bc1), (float)sqrt(bc2), grad_norm, lr_dev, (float)(1.0 / bc1));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 extern "C" int64_t lt_adam_clip_step_ws_floats(int64_t n) { return (n + AD_PER_BLOCK - 1) / AD_PER_BLOCK; }
@@ -669,7 +642,7 @@ static int ppo_loss(const float* mu, const float* stdp, const float* value, cons
                     const float* adv, const float* returns, const float* old_values, const float* old_mu, const float* old_sigma,
                     const int64_t* idx, int64_t M, int A, float clip, float value_loss_coef, float entropy_coef, int use_clipped_value_loss,
                     int std_is_log, const float* adv_stats, float* dmu, float* dvalue, float* acc, float* out, void* stream) {
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * (4 + MAX_A + 4), (hipStream_t)stream);
+  const hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * (4 + MAX_A + 4), (hipStream_t)stream);
   if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
   const dim3 grid((unsigned)((M + 255) / 256));
 #define LT_PPO_LOSS_LAUNCH(LOG, NORM)                                                                                                      \
@@ -684,9 +657,7 @@ static int ppo_loss(const float* mu, const float* stdp, const float* value, cons
   if (out)
     hipLaunchKernelGGL(lt_ppo_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, stdp, A, 1.f / (float)M, value_loss_coef, entropy_coef,
                        std_is_log ? 1 : 0, out);
-  e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 extern "C" int lt_ppo_loss(const float* mu, const float* stdp, const float* value, const float* actions, const float* old_logp, const float* adv,
@@ -694,10 +665,8 @@ extern "C" int lt_ppo_loss(const float* mu, const float* stdp, const float* valu
                            int64_t M, int A, float clip, float value_loss_coef, float entropy_coef, int use_clipped_value_loss, float* dmu, float* dvalue,
                            float* acc, float* out, void* stream) {
   if (!mu || !stdp || !value || !actions || !old_logp || !adv || !returns || !old_values || !old_mu || !old_sigma || !dmu || !dvalue || !acc ||
-      M < 1 || A < 1 || A > MAX_A) {
-    lt_set_error("lt_ppo_loss: invalid argument (1 <= num_actions <= 16)");
-    return LT_EINVAL;
-  }
+      M < 1 || A < 1 || A > MAX_A)
+    return einval("lt_ppo_loss: invalid argument (1 <= num_actions <= 16)");
   return ppo_loss(mu, stdp, value, actions, old_logp, adv, returns, old_values, old_mu, old_sigma, idx, M, A, clip, value_loss_coef,
                   entropy_coef, use_clipped_value_loss, 0, nullptr, dmu, dvalue, acc, out, stream);
 }

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "lt_device_math.h"
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 using namespace lt;
@@ -108,10 +109,8 @@ int lt_rollout_act(int64_t n, int obs_dim, uint64_t seed, const int64_t* step_co
   const bool rows_ok = !obs || (critic_obs && st_obs && st_critic_obs);
   const bool value_ok = !value || st_values;
   if (n <= 0 || obs_dim <= 0 || (obs_dim & 1) || !step_counter || !mu || !std12 || !rows_ok || !value_ok || !st_actions || !st_mu ||
-      !st_sigma || !st_logp || !actions_out) {
-    lt_set_error("lt_rollout_act: invalid argument");
-    return LT_EINVAL;
-  }
+      !st_sigma || !st_logp || !actions_out)
+    return einval("lt_rollout_act: invalid argument");
   ActArgs a;
   a.n = n; a.obs_dim = obs_dim; a.seed = seed; a.step_counter = (const long long*)step_counter;
   a.mu = mu; a.std12 = std12; a.value = value; a.obs = obs; a.critic_obs = critic_obs;
@@ -120,22 +119,15 @@ int lt_rollout_act(int64_t n, int obs_dim, uint64_t seed, const int64_t* step_co
   const dim3 grid((unsigned)((n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK)), block(256);
   if (obs_dim % 4 == 0 && (ENVS_PER_BLOCK * obs_dim) % 4 == 0) hipLaunchKernelGGL(lt_rollout_act_kernel<4>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(lt_rollout_act_kernel<2>, grid, block, 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 int lt_rollout_record(int64_t n, float gamma, const float* reward, const int64_t* dones, const uint8_t* time_out, const float* values,
                       float* st_rewards, uint8_t* st_dones, float* st_values, int64_t* bump_counter, void* stream) {
-  if (n <= 0 || !reward || !dones || !time_out || !values || !st_rewards || !st_dones) {
-    lt_set_error("lt_rollout_record: invalid argument");
-    return LT_EINVAL;
-  }
+  if (n <= 0 || !reward || !dones || !time_out || !values || !st_rewards || !st_dones) return einval("lt_rollout_record: invalid argument");
   hipLaunchKernelGGL(lt_rollout_record_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long long)n, gamma,
                      reward, (const long long*)dones, time_out, values, st_rewards, st_dones, st_values, (long long*)bump_counter);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 }  // extern "C"

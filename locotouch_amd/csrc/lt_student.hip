@@ -26,6 +26,7 @@
 
 #include "lt_cnn_device.h"
 #include "lt_device_prims.h"
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 static_assert(LT_STUDENT_MAX_MLP_LAYERS == LT_MLP_MAX_LAYERS, "lt_student.h mirrors lt_env.h");
@@ -265,13 +266,6 @@ struct Layout : lt_cnn::Geometry {
   int S, cat_pad, gru_bytes, mlp_bytes;
 };
 
-int refuse(const char* what) {
-  char msg[256];
-  snprintf(msg, sizeof msg, "lt_student_desc: %s", what);
-  lt_set_error(msg);
-  return LT_EINVAL;
-}
-
 int check_mlp(const lt_mlp_desc& m, const char* name, int in_width, int max_in) {
   char msg[160];
   const char* bad = nullptr;
@@ -285,16 +279,16 @@ int check_mlp(const lt_mlp_desc& m, const char* name, int in_width, int max_in) 
       if (m.dims[l] < 1 || m.dims[l] > 512) bad = "dims[l + 1] must be in [1, 512] (lt_mlp_desc's limit)";
   if (!bad) return LT_OK;
   snprintf(msg, sizeof msg, "%s.%s", name, bad);
-  return refuse(msg);
+  return refuse("lt_student_desc", msg);
 }
 
 int layout_of(const lt_student_desc* d, Layout* L) {
-  if (!d) return refuse("desc is NULL");
-  if (d->rnn_type != LT_STUDENT_RNN_GRU) return refuse("rnn_type must be LT_STUDENT_RNN_GRU (an LSTM is not served)");
-  if (d->rnn_layers != 1) return refuse("rnn_layers must be 1");
-  if (const char* why = lt_cnn::geometry_of(d, L)) return refuse(why);
-  if (d->rnn_hidden < UT || d->rnn_hidden > 512 || d->rnn_hidden % UT) return refuse("rnn_hidden must be a multiple of LT_STUDENT_GRU_TILE (64), at most 512");
-  if (d->proprio_dim < 0 || d->proprio_dim > 512) return refuse("proprio_dim must be in [0, 512]");
+  if (!d) return refuse("lt_student_desc", "desc is NULL");
+  if (d->rnn_type != LT_STUDENT_RNN_GRU) return refuse("lt_student_desc", "rnn_type must be LT_STUDENT_RNN_GRU (an LSTM is not served)");
+  if (d->rnn_layers != 1) return refuse("lt_student_desc", "rnn_layers must be 1");
+  if (const char* why = lt_cnn::geometry_of(d, L)) return refuse("lt_student_desc", why);
+  if (d->rnn_hidden < UT || d->rnn_hidden > 512 || d->rnn_hidden % UT) return refuse("lt_student_desc", "rnn_hidden must be a multiple of LT_STUDENT_GRU_TILE (64), at most 512");
+  if (d->proprio_dim < 0 || d->proprio_dim > 512) return refuse("lt_student_desc", "proprio_dim must be in [0, 512]");
   if (const int rc = check_mlp(d->encoder, "encoder", d->rnn_hidden, 512)) return rc;
   const int enc_out = d->encoder.dims[d->encoder.num_layers];
   if (const int rc = check_mlp(d->backbone, "backbone", d->proprio_dim + enc_out, 512)) return rc;
@@ -329,15 +323,6 @@ int layout_of(const lt_student_desc* d, Layout* L) {
   return LT_OK;
 }
 
-int hip_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return LT_OK;
-  char msg[256];
-  snprintf(msg, sizeof msg, "%s: %s", what, hipGetErrorString(e));
-  lt_set_error(msg);
-  return LT_EHIP;
-}
-
 }  // namespace
 
 extern "C" {
@@ -350,7 +335,7 @@ int lt_student_validate(const lt_student_desc* desc) {
 int lt_student_packed_floats(const lt_student_desc* desc, size_t* floats) {
   Layout L;
   if (const int rc = layout_of(desc, &L)) return rc;
-  if (!floats) { lt_set_error("lt_student_packed_floats: floats is NULL"); return LT_EINVAL; }
+  if (!floats) return einval("lt_student_packed_floats: floats is NULL");
   *floats = L.total;
   return LT_OK;
 }
@@ -358,7 +343,7 @@ int lt_student_packed_floats(const lt_student_desc* desc, size_t* floats) {
 int lt_student_ws_floats(const lt_student_desc* desc, int64_t n, size_t* floats) {
   Layout L;
   if (const int rc = layout_of(desc, &L)) return rc;
-  if (!floats || n <= 0 || n > INT32_MAX) { lt_set_error("lt_student_ws_floats: floats non-null and n in [1, 2^31)"); return LT_EINVAL; }
+  if (!floats || n <= 0 || n > INT32_MAX) return einval("lt_student_ws_floats: floats non-null and n in [1, 2^31)");
   *floats = (size_t)n * (size_t)(desc->head_out + desc->rnn_hidden);
   return LT_OK;
 }
@@ -366,14 +351,14 @@ int lt_student_ws_floats(const lt_student_desc* desc, int64_t n, size_t* floats)
 int lt_student_step_launches(const lt_student_desc* desc, int64_t n) {
   Layout L;
   if (const int rc = layout_of(desc, &L)) return rc;
-  if (n <= 0 || n > INT32_MAX) { lt_set_error("lt_student_step_launches: n must be in [1, 2^31)"); return LT_EINVAL; }
+  if (n <= 0 || n > INT32_MAX) return einval("lt_student_step_launches: n must be in [1, 2^31)");
   return 3;
 }
 
 int lt_student_pack(const lt_student_desc* desc, const lt_student_params* p, float* packed, void* stream) {
   Layout L;
   if (const int rc = layout_of(desc, &L)) return rc;
-  if (!p || !packed || (uintptr_t)packed % 16) { lt_set_error("lt_student_pack: params and a 16-byte aligned packed buffer are required"); return LT_EINVAL; }
+  if (!p || !packed || (uintptr_t)packed % 16) return einval("lt_student_pack: params and a 16-byte aligned packed buffer are required");
   PackArgs a;
   a.nseg = 0;
   bool missing = false;
@@ -403,9 +388,9 @@ int lt_student_pack(const lt_student_desc* desc, const lt_student_params* p, flo
     seg(p->bb_w[l], L.bb_w[l], n, k, np, kp, kp, 0, 0);
     seg(p->bb_b[l], L.bb_b[l], 1, n, 1, np, np, 0, 0);
   }
-  if (missing) { lt_set_error("lt_student_pack: a parameter pointer the descriptor needs is NULL"); return LT_EINVAL; }
+  if (missing) return einval("lt_student_pack: a parameter pointer the descriptor needs is NULL");
   hipLaunchKernelGGL(lt_student_pack_kernel, dim3(64, (unsigned)a.nseg), dim3(TPB), 0, (hipStream_t)stream, a);
-  return hip_status("lt_student_pack");
+  return launch_status("lt_student_pack");
 }
 
 int lt_student_step(const lt_student_desc* desc, const float* packed, const float* proprio, int64_t proprio_row_stride, const float* tactile,
@@ -414,11 +399,9 @@ int lt_student_step(const lt_student_desc* desc, const float* packed, const floa
   if (const int rc = layout_of(desc, &L)) return rc;
   const int img = L.c[0] * L.h[0] * L.w[0];
   if (!packed || !tactile || !h || !actions_out || !ws || (desc->proprio_dim > 0 && !proprio) || n <= 0 || n > INT32_MAX ||
-      proprio_row_stride < desc->proprio_dim || tactile_row_stride < img || (uintptr_t)packed % 16 || (uintptr_t)h % 16 || (uintptr_t)ws % 16) {
-    lt_set_error("lt_student_step: packed, tactile, h, actions_out, ws (and proprio) non-null; packed, h and ws 16-byte aligned; n in [1, 2^31); "
-                 "row strides at least the row widths");
-    return LT_EINVAL;
-  }
+      proprio_row_stride < desc->proprio_dim || tactile_row_stride < img || (uintptr_t)packed % 16 || (uintptr_t)h % 16 || (uintptr_t)ws % 16)
+    return einval("lt_student_step: packed, tactile, h, actions_out, ws (and proprio) non-null; packed, h and ws 16-byte aligned; n in [1, 2^31); "
+                  "row strides at least the row widths");
   const int D = desc->head_out, H = desc->rnn_hidden;
   float* emb = ws;
   float* hnew = ws + (size_t)n * D;  // D % 16 == 0: aligned
@@ -459,7 +442,7 @@ int lt_student_step(const lt_student_desc* desc, const float* packed, const floa
   hipLaunchKernelGGL(lt_student_encoder_kernel, dim3((unsigned)((n + ET - 1) / ET)), dim3(TPB), (size_t)L.enc_bytes, (hipStream_t)stream, e);
   hipLaunchKernelGGL(lt_student_gru_kernel, dim3((unsigned)(H / UT), tiles), dim3(TPB), (size_t)L.gru_bytes, (hipStream_t)stream, g);
   hipLaunchKernelGGL(lt_student_mlp_kernel, dim3(tiles), dim3(MLP_TPB), (size_t)L.mlp_bytes, (hipStream_t)stream, m);
-  return hip_status("lt_student_step");
+  return launch_status("lt_student_step");
 }
 
 }  // extern "C"

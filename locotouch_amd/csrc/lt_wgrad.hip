@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "lt_env.h"
+#include "lt_host_check.h"
 #include "lt_internal.h"
 
 namespace {
@@ -266,15 +267,13 @@ extern "C" int64_t lt_wgrad_ws_floats(int64_t M, int N, int K) { return (int64_t
 
 extern "C" int lt_wgrad(const float* dz, int dz_split, const float* dz_scale, const float* x, int x_split, int64_t M, int N, int K, const float* amax_blocks,
                         int nblk_amax, float* slabs, float* db_slabs, void* stream) {
-  if (!dz || !x || !slabs || M < 1 || N < 4 || K < 4 || (N & 3) || (K & 3) || (amax_blocks && nblk_amax < 1) || (long long)M * (N > K ? N : K) * 4 >= (1ll << 32)) {
-    lt_set_error("lt_wgrad: invalid argument (N and K multiples of 4, each operand below 4 GiB)");
-    return LT_EINVAL;
-  }
+  if (!dz || !x || !slabs || M < 1 || N < 4 || K < 4 || (N & 3) || (K & 3) || (amax_blocks && nblk_amax < 1) || (long long)M * (N > K ? N : K) * 4 >= (1ll << 32))
+    return einval("lt_wgrad: invalid argument (N and K multiples of 4, each operand below 4 GiB)");
   WgradArgs a;
   a.dz = dz; a.x = x; a.M = M; a.N = N; a.K = K;
   a.amax = amax_blocks; a.nblk_amax = amax_blocks ? nblk_amax : 0;
   a.slabs = slabs; a.db = db_slabs; a.x_split = x_split != 0; a.dz_split = dz_split != 0; a.dz_scale = dz_scale;
-  if (a.dz_split && !dz_scale) { lt_set_error("lt_wgrad: a split dz needs its scale"); return LT_EINVAL; }
+  if (a.dz_split && !dz_scale) return einval("lt_wgrad: a split dz needs its scale");
   a.tiles_n = (N + 16 * TA - 1) / (16 * TA);
   a.tiles_k = (K + 16 * TB - 1) / (16 * TB);
   a.splits = pick_splits((long long)M, a.tiles_n * a.tiles_k);
@@ -283,9 +282,7 @@ extern "C" int lt_wgrad(const float* dz, int dz_split, const float* dz_scale, co
   else if (a.x_split) hipLaunchKernelGGL((lt_wgrad_kernel<false, true>), grid, dim3(64 * WG_WAVES), 0, (hipStream_t)stream, a);
   else if (a.dz_split) hipLaunchKernelGGL((lt_wgrad_kernel<true, false>), grid, dim3(64 * WG_WAVES), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL((lt_wgrad_kernel<false, false>), grid, dim3(64 * WG_WAVES), 0, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }
 
 // Rows in the split format (see unpack8): out[i] = f16 hi | f16 lo << 16 of clamp(x[i], +-LT_MLP_INPUT_CLAMP) - the observation rows of a
@@ -310,9 +307,7 @@ __global__ __launch_bounds__(256) void lt_split_rows_kernel(const float* __restr
 }  // namespace
 
 extern "C" int lt_split_rows(const float* x, void* out, int64_t count, void* stream) {
-  if (!x || !out || count < 4 || (count & 3)) { lt_set_error("lt_split_rows: invalid argument (count a multiple of 4)"); return LT_EINVAL; }
+  if (!x || !out || count < 4 || (count & 3)) return einval("lt_split_rows: invalid argument (count a multiple of 4)");
   hipLaunchKernelGGL(lt_split_rows_kernel, dim3((unsigned)((count / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (unsigned*)out, (long long)(count / 4));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
-  return LT_OK;
+  return launch_status();
 }

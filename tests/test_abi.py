@@ -305,3 +305,45 @@ def test_call_helper():
             _abi.call(name, 1, 2, 3)
     with pytest.raises(ValueError):  # a wrong argument count is an error, not a shifted call
         _abi.call("lt_env_destroy", h, None)
+
+
+# ---- the table of headers (_abi.HEADERS) is held to the tree ----
+def _declared(path):
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S))
+    return set(re.findall(r"^[ \t]*(?:const[ \t]+)?\w+[ \t*]+(lt_\w+)\s*\([^()]*\)\s*;", src, flags=re.M))  # a result type, a name, no body
+
+
+def test_header_table_matches_the_tree(tmp_path):
+    import glob
+
+    include = os.path.join(_abi.REPO, "include")
+    with_protos = sorted(os.path.basename(p) for p in glob.glob(os.path.join(include, "*.h")) if _declared(p))
+    assert sorted(row[1] for row in _abi.HEADERS) == with_protos  # every header that declares an entry point, each once
+    total, queries = 0, set()
+    for prefix, fname, _, row_queries, published in _abi.HEADERS:
+        p = prefix + "_" if prefix else ""
+        assert getattr(_abi, p + "HEADER") == os.path.join(include, fname)
+        sigs = getattr(_abi, p + "SIGNATURES")
+        assert set(sigs) == _declared(os.path.join(include, fname)) and sigs, fname
+        assert getattr(_abi, p + "VALUE_QUERIES") == frozenset(row_queries) <= set(sigs), fname
+        for c in published:
+            cls = getattr(_abi, "".join(w.capitalize() for w in c.split("_")))
+            assert issubclass(cls, ctypes.Structure) and ctypes.sizeof(cls) > 0, c
+        total += len(sigs)
+        queries |= set(row_queries)
+    assert len(_abi.ALL_SIGNATURES) == total and _abi.ALL_VALUE_QUERIES == queries  # no name of one header hides another's
+    _abi.load()
+    assert set(_abi._calls) == set(_abi.ALL_SIGNATURES) - queries  # `call` serves every status, and nothing that returns a value
+    # the loop refuses, by name: a repeated entry point, a value query its header does not declare, a result that is no int
+    (tmp_path / "a.h").write_text("int lt_one(int a);\nint lt_two(void);\n")
+    (tmp_path / "b.h").write_text("int lt_three(void);\nint lt_two(float x);\n")
+    (tmp_path / "c.h").write_text("float lt_four(void);\n")
+    rows = {n: (n.upper(), n + ".h", False, (), ()) for n in "abc"}
+    assert [set(b[3]) for b in _abi._bind((rows["a"],), str(tmp_path))] == [{"lt_one", "lt_two"}]
+    with pytest.raises(ImportError, match=r"b\.h.*lt_two"):
+        _abi._bind((rows["a"], rows["b"]), str(tmp_path))
+    with pytest.raises(ImportError, match=r"a\.h.*lt_gone"):
+        _abi._bind((("A", "a.h", False, ("lt_gone",), ()),), str(tmp_path))
+    with pytest.raises(ImportError, match=r"c\.h.*lt_four"):
+        _abi._bind((("C", "c.h", False, ("lt_four",), ()),), str(tmp_path))
+    assert _abi._bind((("", "c.h", False, ("lt_four",), ()),), str(tmp_path))[0][4] == {"lt_four"}  # lt_env.h's queries alone may
