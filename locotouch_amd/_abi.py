@@ -140,6 +140,7 @@ HEADERS = (
      ("lt_memory_gru_net", "lt_memory_gru_seq_net", "lt_memory_gru_seq_grad")),  # GRU memories, one rollout step and whole rollouts
     ("POLICY", "lt_policy.h", True, ("lt_policy_step_launches",), ("lt_policy_desc", "lt_policy_memory")),  # one inference step of a recurrent policy
     ("PPO_OPTS", "lt_ppo_opts.h", False, (), ()),  # the log-std policy and per-minibatch advantage statistics
+    ("MLP_DX", "lt_mlp_dx.h", True, (), ()),  # the input gradient of the actor and critic stacks (recurrent policies: the memories' dout)
 )
 
 

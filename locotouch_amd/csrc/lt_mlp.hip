@@ -61,6 +61,7 @@
 #include "lt_device_math.h"
 #include "lt_host_check.h"
 #include "lt_internal.h"
+#include "lt_mlp_dx.h"
 
 using namespace lt;
 
@@ -942,6 +943,7 @@ struct PackArgs {
   const float* w; const float* b;  // b == nullptr: zero biases
   int K, N;
   int transposed;           // element (n, k) is w[k * N + n] (the backward chain multiplies by W^T of a torch.nn.Linear weight [K][N])
+  int raw;                  // no stream: w [N][K] as it stands to packed + bias_float_off (the W_0 section of include/lt_mlp_dx.h)
   long long chunk_off[NW];  // first chunk of this layer in each wave's stream (absolute, in chunks)
   Plan plan;                // how the layer is dealt to the waves
   long long bias_float_off; // first float of this layer's (pad16(N)) bias slice
@@ -958,6 +960,10 @@ __global__ void lt_mlp_pack_kernel(const ALL all) {
   const int T = pl.T, G = pl.Gl, C = 2 * T;
   const int chunks = layer_chunks(pl), nact = pl.waves;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;  // (wave, chunk, lane)
+  if (p.raw) {  // (uniform)
+    if (idx < (long long)p.N * p.K) p.packed[p.bias_float_off + idx] = p.w[idx];
+    return;
+  }
   if (idx < pad16(p.N)) p.packed[p.bias_float_off + idx] = (idx < p.N && p.b) ? p.b[idx] : 0.f;
   if (idx >= (long long)nact * chunks * 64) return;
   const int lane = (int)(idx & 63);
@@ -1444,6 +1450,39 @@ int lt_mlp_backward_pair(const lt_mlp_desc* fwd0, const float* bpacked0, const f
 // Everything a training step needs packed, in ONE launch: the forward streams of both networks (lt_mlp_pack) and, where the network
 // qualifies (lt_mlp_backward_packed_floats), their transposed streams for lt_mlp_backward_pair (bpacked* may be NULL: forward only).
 // The optimizer moves the weights at every step, so this runs 20 times per PPO update: four launches of ~5 us were 3 % of a step.
+static int pack_training(const char* fn, bool dx, const lt_mlp_desc* const* ds, const float* const* const* ws, const float* const* const* bs,
+                         float* const* pk, float* const* bp, void* stream) {
+  PackMany all = {};
+  int n = 0;
+  long long most = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (!desc_ok(ds[k]) || !ws[k] || !bs[k] || !pk[k]) return refuse(fn, "invalid argument");
+    for (int l = 0; l < ds[k]->num_layers; ++l)
+      if (!ws[k][l] || !bs[k][l]) return refuse(fn, "null layer pointer");
+    const long long m = fill_pack_forward(ds[k], ws[k], bs[k], pk[k], all.layer + n);
+    most = m > most ? m : most;
+    n += ds[k]->num_layers;
+    if (bp[k]) {
+      lt_mlp_desc bd;
+      if (!backward_desc(ds[k], &bd)) return refuse(fn, "the network has no backward stream (lt_mlp_backward_packed_floats)");
+      const long long mb = fill_pack_backward(ds[k], bd, ws[k], bp[k], all.layer + n);
+      most = mb > most ? mb : most;
+      n += bd.num_layers;
+    }
+  }
+  for (int k = 0; dx && k < 2; ++k) {  // the W_0 sections behind the transposed streams (include/lt_mlp_dx.h): two more "layers" of the launch
+    lt_mlp_desc bd;
+    backward_desc(ds[k], &bd);
+    PackArgs& p = all.layer[n++];  // (2 (L + L - 1) + 2 <= 4 LT_MLP_MAX_LAYERS)
+    p.raw = 1; p.w = ws[k][0]; p.N = ds[k]->dims[1]; p.K = ds[k]->dims[0]; p.packed = bp[k];
+    p.bias_float_off = geometry(&bd).total_chunks * 256;
+    const long long count = (long long)p.N * p.K;
+    most = count > most ? count : most;
+  }
+  hipLaunchKernelGGL(lt_mlp_pack_kernel<PackMany>, dim3((unsigned)((most + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, all);
+  return launch_status();
+}
+
 int lt_mlp_pack_training(const lt_mlp_desc* d0, const float* const* weights0, const float* const* biases0, float* packed0, float* bpacked0,
                          const lt_mlp_desc* d1, const float* const* weights1, const float* const* biases1, float* packed1, float* bpacked1, void* stream) {
   const lt_mlp_desc* ds[2] = {d0, d1};
@@ -1451,26 +1490,35 @@ int lt_mlp_pack_training(const lt_mlp_desc* d0, const float* const* weights0, co
   const float* const* bs[2] = {biases0, biases1};
   float* pk[2] = {packed0, packed1};
   float* bp[2] = {bpacked0, bpacked1};
-  PackMany all = {};
-  int n = 0;
-  long long most = 0;
+  return pack_training("lt_mlp_pack_training", false, ds, ws, bs, pk, bp, stream);
+}
+
+// include/lt_mlp_dx.h: a bpacked buffer with the W_0 section behind the streams, and the training pack that fills it as well
+static bool dx_desc_ok(const lt_mlp_desc* fwd, lt_mlp_desc* bd) { return fwd && backward_desc(fwd, bd) && fwd->dims[0] % 8 == 0 && fwd->dims[0] <= 512; }
+
+int lt_mlp_backward_dx_packed_floats(const lt_mlp_desc* fwd, size_t* floats) {
+  lt_mlp_desc bd;
+  if (!floats) return refuse("lt_mlp_backward_dx_packed_floats", "", "floats", "non-null");
+  if (!dx_desc_ok(fwd, &bd))
+    return refuse("lt_mlp_backward_dx_packed_floats", "", "fwd", "a network with a backward stream (lt_mlp_backward_packed_floats) and dims[0] a multiple of 8, <= 512");
+  *floats = (size_t)geometry(&bd).total_chunks * 256 + (size_t)fwd->dims[1] * fwd->dims[0];
+  return LT_OK;
+}
+
+int lt_mlp_pack_training_dx(const lt_mlp_desc* d0, const float* const* weights0, const float* const* biases0, float* packed0, float* bpacked0,
+                            const lt_mlp_desc* d1, const float* const* weights1, const float* const* biases1, float* packed1, float* bpacked1, void* stream) {
+  const lt_mlp_desc* ds[2] = {d0, d1};
+  const float* const* ws[2] = {weights0, weights1};
+  const float* const* bs[2] = {biases0, biases1};
+  float* pk[2] = {packed0, packed1};
+  float* bp[2] = {bpacked0, bpacked1};
+  lt_mlp_desc bd;
   for (int k = 0; k < 2; ++k) {
-    if (!desc_ok(ds[k]) || !ws[k] || !bs[k] || !pk[k]) return einval("lt_mlp_pack_training: invalid argument");
-    for (int l = 0; l < ds[k]->num_layers; ++l)
-      if (!ws[k][l] || !bs[k][l]) return einval("lt_mlp_pack_training: null layer pointer");
-    const long long m = fill_pack_forward(ds[k], ws[k], bs[k], pk[k], all.layer + n);
-    most = m > most ? m : most;
-    n += ds[k]->num_layers;
-    if (bp[k]) {
-      lt_mlp_desc bd;
-      if (!backward_desc(ds[k], &bd)) return einval("lt_mlp_pack_training: the network has no backward stream (lt_mlp_backward_packed_floats)");
-      const long long mb = fill_pack_backward(ds[k], bd, ws[k], bp[k], all.layer + n);
-      most = mb > most ? mb : most;
-      n += bd.num_layers;
-    }
+    if (!dx_desc_ok(ds[k], &bd))
+      return refuse("lt_mlp_pack_training_dx", k ? "network 1: " : "network 0: ", "desc", "a network with a backward stream and dims[0] a multiple of 8, <= 512");
+    if (!bp[k]) return refuse("lt_mlp_pack_training_dx", k ? "network 1: " : "network 0: ", "bpacked", "non-null");
   }
-  hipLaunchKernelGGL(lt_mlp_pack_kernel<PackMany>, dim3((unsigned)((most + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, all);
-  return launch_status();
+  return pack_training("lt_mlp_pack_training_dx", true, ds, ws, bs, pk, bp, stream);
 }
 
 }  // extern "C"

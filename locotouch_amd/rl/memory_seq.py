@@ -26,6 +26,9 @@ checkpoints are unaffected), in two forms as rl/lstm.py:
     launches) - both cells on the one row-block kernel of csrc/lt_memory_tile.h.  What is not sequential stays outside the loop, one
     call each (`_finish`): the two weight gradients through rl/gru.py `_wgrad`, the bias gradients as column sums.
 The observations and the initial states carry no gradient: dX and the gradients of the initial states are not computed.
+
+`direct_forward` / `direct_backward` are the HIP form WITHOUT the autograd Function, for `PPO._direct_recurrent_update`: the records out,
+(dout_a, dout_c) in, the eight parameter gradients written in place into given views.
 """
 from __future__ import annotations
 
@@ -295,6 +298,49 @@ def hip_backward(cell, douts, dones, w_hhs, recs):
         dgs.append(dg)
     _abi.call(cell.seq_backward, nets[0], nets[1], dones, 0 if dones is None else dones.stride(0), T, E, H, _abi.stream(recs[0]["out"].device))
     return dgs
+
+
+def _wgrad_into(dst, dy2d, x2d) -> None:
+    """`dst` = rl/gru.py `_wgrad(dy2d, x2d)`, the same operations in the same order, the last of them writing in place."""
+    from .linear import pick_splits
+
+    m = dy2d.shape[0]
+    s = pick_splits(m) if dy2d.is_cuda else 1
+    if s > 1:
+        torch.sum(torch.bmm(dy2d.view(s, m // s, -1).transpose(1, 2), x2d.view(s, m // s, -1)), dim=0, out=dst)
+    else:
+        torch.mm(dy2d.t(), x2d, out=dst)
+
+
+def direct_forward(cell, memory_a, memory_c, x_a, x_c, dones, hc0_a, hc0_c):
+    """Both memories over a whole rollout of an env block WITHOUT an autograd graph (`PPO._direct_recurrent_update`): the cell's
+    `seq_forward` on the live parameters.  x_*: contiguous [T, E, I] f32 blocks; dones: what `_dones_bytes` gives, or None; hc0_*: as
+    `memory_rollout_sequence` takes them.  Returns the two forward records (`rec["out"]` [T, E, H] is the memory's output), which
+    `direct_backward` consumes."""
+    E = x_a.shape[1]
+    with torch.no_grad():
+        return hip_forward(cell, x_a, x_c, dones, (*_state(cell, hc0_a, E), *_state(cell, hc0_c, E)), (*_params(memory_a), *_params(memory_c)))
+
+
+def direct_backward(cell, memory_a, memory_c, x_a, x_c, dones, recs, douts, grad_of) -> None:
+    """From (dout_a, dout_c), each [T, E, H] (or [T * E, H]) contiguous f32, to the eight parameter gradients, written IN PLACE into
+    `grad_of[param]` (views of the flat gradient bucket; every element of each is written): the cell's `seq_backward`, then per network
+    what `_finish` does - dW_ih, dW_hh as split-K GEMMs, db_ih, db_hh as column sums - with the last operation of each writing its
+    view.  One code path for both cells, through the `Cell` table."""
+    with torch.no_grad():
+        T, E, H = recs[0]["out"].shape
+        mems = (memory_a, memory_c)
+        dgs = hip_backward(cell, tuple(d.view(T, E, H) for d in douts), dones, tuple(_params(m)[1] for m in mems), recs)
+        for mem, x, dg, rec in zip(mems, (x_a, x_c), dgs, recs):
+            w_ih, w_hh, b_ih, b_hh = _params(mem)
+            d_ih, d_hh = (dg[k].view(T * E, -1) for k in (cell.d_ih, cell.d_hh))
+            torch.sum(d_ih, dim=0, out=grad_of[b_ih])
+            if cell.d_hh == cell.d_ih:
+                grad_of[b_hh].copy_(grad_of[b_ih])
+            else:
+                torch.sum(d_hh, dim=0, out=grad_of[b_hh])
+            _wgrad_into(grad_of[w_ih], d_ih, x.reshape(T * E, -1))
+            _wgrad_into(grad_of[w_hh], d_hh, rec["h_prev"].view(T * E, H))
 
 
 class _SeqHip(torch.autograd.Function):

@@ -18,6 +18,7 @@ import torch.nn as nn
 from .. import _abi
 
 USE_FUSED_BACKWARD = os.environ.get("LT_FUSED_BACKWARD", "1") != "0"  # 0: dz @ W as library GEMMs + lt_elu_backward_bias per layer
+USE_DX_KERNEL = os.environ.get("LT_MLP_DX_KERNEL", "1") != "0"  # 0: the fused chain's input gradients as a library GEMM on the unsplit dz_0
 _ACT_IDS = {nn.ELU: "LT_ACT_ELU", nn.ReLU: "LT_ACT_RELU", nn.Tanh: "LT_ACT_TANH", nn.Identity: "LT_ACT_NONE"}
 
 
@@ -68,6 +69,7 @@ class PackedMLP:
         dev = self.linears[0].weight.device
         self.packed = torch.zeros(n.value, device=dev, dtype=torch.float32)
         self.bpacked = None  # the transposed streams of the fused backward pass (pack_backward / PackedPair.pack_training)
+        self.bpacked_dx = False  # ... with room for W_0 behind them (alloc_bpacked(dx=True))
         self.in_dtype = torch.float32
         self.out_features = self.linears[-1].out_features
         self.in_features = self.linears[0].in_features
@@ -90,11 +92,13 @@ class PackedMLP:
         n = ctypes.c_size_t()
         return self.lib.lt_mlp_backward_packed_floats(ctypes.byref(self.desc), ctypes.byref(n)) == 0
 
-    def alloc_bpacked(self) -> None:
-        if self.bpacked is None:
+    def alloc_bpacked(self, dx: bool = False) -> None:
+        """`dx`: with the W_0 section behind the streams (include/lt_mlp_dx.h); the streams' own layout is the same either way."""
+        if self.bpacked is None or (dx and not self.bpacked_dx):
             n = ctypes.c_size_t()
-            _abi.call("lt_mlp_backward_packed_floats", self.desc, ctypes.byref(n))
+            _abi.call("lt_mlp_backward_dx_packed_floats" if dx else "lt_mlp_backward_packed_floats", self.desc, ctypes.byref(n))
             self.bpacked = torch.zeros(n.value, device=self.packed.device, dtype=torch.float32)
+            self.bpacked_dx = dx
 
     def pack_backward(self) -> None:
         """The transposed weights in the kernel's stream layout (the backward chain multiplies by W^T); re-packed at every optimizer step."""
@@ -223,12 +227,13 @@ class SumJobs:
         self.after = []
 
 
-def backward_chain(weights, biases_out, weights_out, x, acts, dy, sums: SumJobs):
+def backward_chain(weights, biases_out, weights_out, x, acts, dy, sums: SumJobs, dx_out=None):
     """The backward pass of one Linear/ELU stack by hand, gradients written IN PLACE into the given tensors (views of the flat
     gradient bucket): `weights[l]` the layer's weight, `weights_out[l]` / `biases_out[l]` where dW_l / db_l go, `x` the stack's
     input rows, `acts[l]` the activations behind hidden layer l, `dy` the gradient w.r.t. the stack's output.  ELU' + per-block
     bias sums in one kernel (lt_elu_backward_bias), narrow-head gradients in one (lt_head_wgrad), split-K batched GEMMs for the
-    weight gradients, plain GEMMs for the input gradients; every ordered sum of partials is queued on `sums` (one launch later)."""
+    weight gradients, plain GEMMs for the input gradients; every ordered sum of partials is queued on `sums` (one launch later).
+    `dx_out` [m, in_features]: where the gradient w.r.t. `x` goes, one more of those GEMMs (None: it is not formed)."""
     from .linear import _head_wgrad_ok, pick_splits
 
     lib = _abi.load()
@@ -272,6 +277,8 @@ def backward_chain(weights, biases_out, weights_out, x, acts, dy, sums: SumJobs)
                 torch.sum(dz, dim=0, out=biases_out[l])
         if l > 0:
             g = dz @ w
+        elif dx_out is not None:
+            torch.mm(dz.detach(), w.detach(), out=dx_out)
 
 
 class PackedPair:
@@ -287,6 +294,8 @@ class PackedPair:
         self.domain_max: torch.Tensor | None = None
         self.acts_split = False           # format of the activations the last forward_raw wrote
         self._bpacked_fresh = False       # the transposed streams match the live weights (pack_training .. the next optimizer step)
+        self._dx_fresh = False            # ... and so do the W_0 sections behind them (pack_training(with_dx=True))
+        self.last_backward: str | None = None  # "fused" / "library": the path the last backward_raw took
         self._bwd_shapes_ok: bool | None = None
         self.sat: torch.Tensor | None = None  # device counter of the fused backward chain's saturated workgroups x layers
         for net in (self.a, self.b):
@@ -313,31 +322,48 @@ class PackedPair:
         self.domain_max = None
         return v >= float(_abi.CONSTS["LT_MLP_INPUT_CLAMP"])
 
-    def forward_raw(self, x0: torch.Tensor, x1: torch.Tensor, split: bool | None = None):
+    def forward_raw(self, x0: torch.Tensor, x1: torch.Tensor, split: bool | None = None, with_dx: bool = False):
         """The launch without autograd: ((mean, value), (activations of the actor, of the critic)); re-packs the live parameters.
         `split` (default: whenever the fused backward pass will consume them): the activations are written in the kernel's split
         format - one dword per element, f16 hi | f16 lo << 16, value = hi + lo / 64 (include/lt_env.h, lt_mlp_forward_pair) - which
-        the backward chain and the weight-gradient kernel read without converting; the tensors keep dtype float32 as a container."""
+        the backward chain and the weight-gradient kernel read without converting; the tensors keep dtype float32 as a container.
+        `with_dx`: the backward pass will be asked for the input gradients (`backward_raw(dx_out=...)`): the same pack launch leaves
+        W_0 of both stacks for that hop."""
         if split is None:
             split = self._fused_backward_possible(x0, x1)
         self.acts_split = bool(split)
-        self.pack_training(with_backward=self.acts_split)
+        self.pack_training(with_backward=self.acts_split, with_dx=with_dx and self.acts_split and self._dx_kernel_ok())
         ys, acts = _forward_pair((self.a, self.b), x0, x1, self.acts_split)
         if self.check_domain:
             hidden = [t.view(torch.float16)[:, 0::2] if self.acts_split else t for t in (*acts[0], *acts[1])]  # (the hi halves carry the magnitude)
             self._record_domain((x0, x1, *hidden))
         return ys, acts
 
-    def pack_training(self, with_backward: bool) -> None:
+    def pack_training(self, with_backward: bool, with_dx: bool = False) -> None:
         """The forward streams of both networks and (with_backward) their transposed streams for the fused backward pass, in ONE
-        launch (`lt_mlp_pack_training`): a training step re-packs everything, the optimizer has moved the weights."""
+        launch (`lt_mlp_pack_training`): a training step re-packs everything, the optimizer has moved the weights.  `with_dx`: and
+        W_0 of both behind those streams (`lt_mlp_pack_training_dx`, include/lt_mlp_dx.h), still one launch."""
+        with_backward = with_backward or with_dx
         args = []
         for net in (self.a, self.b):
             if with_backward:
-                net.alloc_bpacked()
+                net.alloc_bpacked(dx=with_dx)
             args += [net.desc, net.weight_ptrs(), net.bias_ptrs(), net.packed, net.bpacked if with_backward else None]
-        _abi.call("lt_mlp_pack_training", *args, _abi.stream())
+        _abi.call("lt_mlp_pack_training_dx" if with_dx else "lt_mlp_pack_training", *args, _abi.stream())
         self._bpacked_fresh = bool(with_backward)
+        self._dx_fresh = bool(with_dx)
+
+    def _dx_kernel_ok(self) -> bool:
+        """The input gradients of the fused backward pass come from the hop kernel (`lt_mlp_backward_pair_dx`): input widths that are
+        multiples of 8, <= 512, and USE_DX_KERNEL; else from the library GEMM on the unsplit dz_0 (`_dx_library`)."""
+        return USE_DX_KERNEL and all(net.in_features % 8 == 0 and net.in_features <= 512 for net in (self.a, self.b))
+
+    def _dx_library(self, dz, w, scale, dx_out) -> None:
+        """dx = dz_0 W_0 as a library GEMM behind the chain: dz_0 out of the split format (exact in f32) and its scale first."""
+        if scale is not None:
+            halves = dz.view(torch.float16).view(dz.shape[0], dz.shape[1], 2).float()
+            dz = (halves[..., 0] + halves[..., 1] * (1.0 / 64.0)) / scale
+        torch.mm(dz, w.detach(), out=dx_out)
 
     def split_rows(self, x: torch.Tensor) -> torch.Tensor:
         """Observation rows in the split format (lt_split_rows): converted once per PPO update for the first layer's weight gradient.
@@ -371,7 +397,7 @@ class PackedPair:
     def _fused_backward_ok(self, x0, x1, dy0, dy1) -> bool:
         return self._fused_backward_possible(x0, x1) and dy0.dtype == torch.float32 and dy1.dtype == torch.float32
 
-    def _backward_fused(self, x0, x1, acts, dy0, dy1, grad_of, sums, x_split_rows=None, after_first=None, dy_amax=None) -> None:
+    def _backward_fused(self, x0, x1, acts, dy0, dy1, grad_of, sums, x_split_rows=None, after_first=None, dy_amax=None, dx_out=None) -> None:
         """The backward pass as: two head launches (lt_head_wgrad), ONE launch for both stacks' chains of input gradients
         (lt_mlp_backward_pair: dz of every hidden layer, ELU' applied in the layer epilogue, per-workgroup max |dz|), six weight
         gradients on the matrix cores that also leave the bias gradients' partials (lt_wgrad), one launch of ordered sums."""
@@ -412,8 +438,18 @@ class PackedPair:
         dzsp = int(dy_amax is not None)
         scales = torch.empty(2, device=dev, dtype=torch.float32)
         in_amax = dy_amax if dzsp else (None, None)
-        _abi.call("lt_mlp_backward_pair", nets[0].desc, nets[0].bpacked, dys[0], *arrs[0], nets[1].desc, nets[1].bpacked, dys[1], *arrs[1],
-                  m, asp, in_amax[0], in_amax[1], dzsp, scales, self.sat, stream)
+        dx_kernel = dx_out is not None and self._dx_kernel_ok()
+        if dx_kernel and not self._dx_fresh:  # (forward_raw(with_dx=True) packs W_0 with everything else)
+            self.pack_training(with_backward=True, with_dx=True)
+        chain = (nets[0].desc, nets[0].bpacked, dys[0], *arrs[0], nets[1].desc, nets[1].bpacked, dys[1], *arrs[1],
+                 m, asp, in_amax[0], in_amax[1], dzsp, scales, self.sat)
+        if dx_kernel:  # the chain and, behind it, dx = dz_0 W_0 of both stacks (include/lt_mlp_dx.h)
+            _abi.call("lt_mlp_backward_pair_dx", *chain, dx_out[0], dx_out[1], stream)
+        else:
+            _abi.call("lt_mlp_backward_pair", *chain, stream)
+            if dx_out is not None:
+                for k, net in enumerate(nets):
+                    self._dx_library(dzs[k][0], net.linears[0].weight, scales[k] if dzsp else None, dx_out[k])
         for k, net in enumerate(nets):
             for l in range(len(net.linears) - 2, -1, -1):
                 inp = acts[k][l - 1] if l > 0 else xs[k]
@@ -436,29 +472,35 @@ class PackedPair:
                 if k == 0:
                     after_first()
         self._keep_bwd = (dzs, amaxs, dys, per_net, scales if dzsp else None)
-        self._bpacked_fresh = False  # the optimizer steps next
+        self._bpacked_fresh = self._dx_fresh = False  # the optimizer steps next
 
     def saturated(self) -> torch.Tensor | None:
         """Device counter of saturated workgroups of the fused backward chain (None: that path has not run)."""
         return self.sat
 
-    def backward_raw(self, x0, x1, acts, dy0, dy1, grad_of, x_split_rows=None, after_first=None, dy_amax=None) -> None:
+    def backward_raw(self, x0, x1, acts, dy0, dy1, grad_of, x_split_rows=None, after_first=None, dy_amax=None, dx_out=None) -> None:
         """Both stacks' backward passes, every parameter gradient written into `grad_of[param]` (the flat bucket's views).
         `x_split_rows`: (x0, x1) in the split format (`split_rows`), if the caller has them.  `dy_amax`: device scalars (max |dy0|,
         max |dy1|), if the producer of the gradients left them (lt_ppo_loss: acc[20], acc[21]) - the hidden-layer gradients then travel
         in the split format as well.  `after_first()`: called when every
-        gradient of the FIRST stack (the actor) has been enqueued - before the second stack's weight gradients are."""
+        gradient of the FIRST stack (the actor) has been enqueued - before the second stack's weight gradients are.
+        `dx_out`: (dx0, dx1), contiguous f32 [m, in_features] each: the gradients w.r.t. the rows x0 / x1 are written there (a recurrent
+        policy's memories take them as `dout`) - behind the fused chain by `lt_mlp_backward_pair_dx`, on the library path by one more GEMM.
+        `last_backward` names the path taken."""
         sums = SumJobs()
         if self._fused_backward_ok(x0, x1, dy0, dy1):
-            self._backward_fused(x0, x1, acts, dy0, dy1, grad_of, sums, x_split_rows, after_first, dy_amax)
+            self.last_backward = "fused"
+            self._backward_fused(x0, x1, acts, dy0, dy1, grad_of, sums, x_split_rows, after_first, dy_amax, dx_out)
             sums.launch()
             return
         if self.acts_split:
             raise RuntimeError("PackedPair.backward_raw: the activations are in the split format, which only the fused backward pass reads "
                                "(forward_raw(..., split=False) for the library path)")
-        for net, x, a, dy in ((self.a, x0, acts[0], dy0), (self.b, x1, acts[1], dy1)):
+        self.last_backward = "library"
+        for k, (net, x, a, dy) in enumerate(((self.a, x0, acts[0], dy0), (self.b, x1, acts[1], dy1))):
             ws = [lin.weight for lin in net.linears]
-            backward_chain(ws, [grad_of[lin.bias] for lin in net.linears], [grad_of[lin.weight] for lin in net.linears], x, a, dy, sums)
+            backward_chain(ws, [grad_of[lin.bias] for lin in net.linears], [grad_of[lin.weight] for lin in net.linears], x, a, dy, sums,
+                           dx_out=None if dx_out is None else dx_out[k])
         sums.launch()  # every ordered sum of partials of both stacks: one launch
 
     def __call__(self, x0: torch.Tensor, x1: torch.Tensor):

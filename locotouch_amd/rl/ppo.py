@@ -35,6 +35,20 @@ class PPO:
         self.fused_recurrent_update = bool(unused.get("fused_recurrent_update", False))
         # opt-in: `fused_recurrent_update` serves GRU memories as well (csrc/lt_memory_gru.hip); on its own it does nothing
         self.fused_gru_memories = bool(unused.get("fused_gru_memories", False))
+        # opt-in, on top of `fused_recurrent_update`: that update without an autograd graph and without a host read between its steps
+        # (_direct_recurrent_update); what it cannot serve is refused here and below, never run on another path
+        self.direct_recurrent_update = bool(unused.get("direct_recurrent_update", False))
+        if self.direct_recurrent_update:
+            if not self.fused_recurrent_update:
+                raise ValueError("direct_recurrent_update: it is a form of the whole-rollout update: set fused_recurrent_update=True as well")
+            if not on_gpu:
+                raise ValueError(f"direct_recurrent_update: the device is {device!r}: its kernels run on a GPU only")
+            if self.dist.world_size > 1:
+                raise ValueError(f"direct_recurrent_update: dist.world_size is {self.dist.world_size}: the collectives of this form are not "
+                                 "covered by a multi-rank test, it runs on one rank only")
+            why = self._recurrent_update_unsupported()
+            if why is not None:
+                raise ValueError(f"direct_recurrent_update: {why}")
         if self.fused_recurrent_update:
             why = self._recurrent_update_unsupported()
             if why is not None:
@@ -68,6 +82,10 @@ class PPO:
 
             self._flat_adam = FlatAdam(self.optimizer)
             self._flat_grad = self._flat_adam.flat_g  # also the all-reduce bucket of a multi-rank job
+        if self.direct_recurrent_update:
+            why = self._direct_recurrent_unsupported()
+            if why is not None:
+                raise ValueError(f"direct_recurrent_update: {why}")
 
     # ---- data-parallel plumbing ------------------------------------------------------------------
     def _make_flat_grad_bucket(self) -> None:
@@ -329,9 +347,140 @@ class PPO:
             group["lr"] = self.learning_rate
 
     def update(self):
+        if self.direct_recurrent_update:
+            return self._direct_recurrent_update()
         if self.fused_recurrent_update:
             return self._recurrent_update()
         return self._eager_update()
+
+    def _direct_recurrent_unsupported(self) -> str | None:
+        """What `_direct_recurrent_update` needs beyond `_recurrent_update_unsupported`, a GPU and one rank (None: it is all there)."""
+        from .fused_loss import std_param
+        from .mlp import PackedPair, describe
+
+        ac = self.actor_critic
+        if self._flat_adam is None:
+            return "there is no FlatAdam (fused_adam=False): the gradients are written in place into its flat bucket"
+        if not self.packed_forward:
+            return "packed_forward is off: the two MLPs run through rl/mlp.py PackedPair"
+        for name, seq in (("actor", ac.actor), ("critic", ac.critic)):
+            if describe(seq) is None:
+                return f"the MLP kernel does not serve the {name} stack (rl/mlp.py describe: Linear/activation stack, hidden widths <= 512)"
+        try:
+            self._pair = PackedPair(ac.actor, ac.critic)
+        except ValueError as e:
+            return str(e)
+        if self._pair.a.out_features > 16:
+            return f"the action width is {self._pair.a.out_features}: the loss kernel serves at most 16"
+        std_p, _ = std_param(ac)
+        if not std_p.requires_grad:
+            return "std has no gradient: the learning-rate launch writes d loss / d std into its slot of the bucket"
+        written = {id(std_p)} | {id(p) for seq in (ac.actor, ac.critic) for p in seq.parameters()}
+        written |= {id(p) for mem in (ac.memory_a, ac.memory_c) for p in (mem.rnn.weight_ih_l0, mem.rnn.weight_hh_l0, mem.rnn.bias_ih_l0, mem.rnn.bias_hh_l0)}
+        for name, p in ac.named_parameters():
+            if p.requires_grad and id(p) not in written:
+                return f"the parameter {name} has a gradient this form does not write"
+        return None
+
+    @staticmethod
+    def _block_row_index(T: int, N: int, num_mini_batches: int, device=None) -> torch.Tensor:
+        """int64 [num_mini_batches, T * per]: idx[i, t * per + j] = t * N + i * per + j, the row of the flattened storage behind row
+        t * per + j of env block i (per = N // num_mini_batches; the leftover envs belong to no block, as in the reference's dealing)."""
+        per = N // num_mini_batches
+        ar = lambda n, *shape: torch.arange(n, device=device, dtype=torch.int64).view(*shape)  # noqa: E731
+        return (ar(T, 1, T, 1) * N + ar(num_mini_batches, num_mini_batches, 1, 1) * per + ar(per, 1, 1, per)).reshape(num_mini_batches, T * per)
+
+    def _direct_recurrent_update(self):
+        """`_recurrent_update` with NO autograd graph and NO host read between its steps, as `_direct_update` is to `_fused_update`.
+        Once per update: the env blocks' observation rows laid out contiguously, their states at step 0, the row index of every block
+        into the flattened storage, [`lt_adv_stats` on those indices], the device state [lr, 3 sums].  Per optimizer step: the cell's
+        `seq_forward` (rl/memory_seq.py `direct_forward`), the packed forward of both stacks on the [T * per, H] outputs, ONE loss launch
+        that reads the small per-row tensors through the block's index and writes d loss / d (mu, value, std) (csrc/lt_ppo.hip), the
+        learning-rate rule on the device scalar, both stacks' backward chains with the gradient w.r.t. their input rows
+        (`PackedPair.backward_raw(dx_out=...)`, include/lt_mlp_dx.h), the cell's `seq_backward` from those rows and the memories' eight
+        parameter gradients (`direct_backward`) - every gradient written in place into the flat bucket - and clip + Adam from the device
+        learning rate.  One host read at the end: lr, the three statistics, the saturation count and the domain record."""
+        why = self._recurrent_update_unsupported()  # (with the storage now: the observation rows' dtype)
+        if why is not None:
+            raise ValueError(f"direct_recurrent_update: {why}")
+        from .fused_loss import adv_stats, std_param
+        from .memory_seq import _dones_bytes, cell_of, direct_backward, direct_forward
+
+        ac, st, fa, pair = self.actor_critic, self.storage, self._flat_adam, self._pair
+        if st.saved_hidden_states_a is None or st.saved_hidden_states_c is None:
+            raise ValueError("direct_recurrent_update: the storage holds no saved hidden states (no rollout of a recurrent policy filled it)")
+        T, N, nmb = st.num_steps, st.num_envs, self.num_mini_batches
+        per = N // nmb
+        m = T * per
+        if per < 1 or (self.normalize_advantage_per_mini_batch and m < 2):
+            raise ValueError(f"direct_recurrent_update: {nmb} minibatches of {N} envs x {T} steps leave a block of {m} rows")
+        dev = st.observations.device
+        cell = cell_of(ac.memory_a, self.fused_gru_memories)
+        H = ac.memory_a.rnn.hidden_size
+        _, _, small = self._flat_storage()
+        small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
+        a_dim = small[0].shape[1]
+        if a_dim > 16:
+            raise ValueError(f"direct_recurrent_update: the action width is {a_dim}: the loss kernel serves at most 16")
+        idx_all = self._block_row_index(T, N, nmb, dev)
+        mb_stats = adv_stats(small[2], idx_all.view(-1), m, nmb) if self.normalize_advantage_per_mini_batch else None
+        dones = _dones_bytes(st.dones.view(T, N))
+        blocks = []
+        for i in range(nmb):
+            sl = (slice(None), slice(i * per, (i + 1) * per))
+            states = [tuple(h[0][sl].reshape(per, H) for h in hs) for hs in (st.saved_hidden_states_a, st.saved_hidden_states_c)]
+            blocks.append((st.observations[sl].contiguous(), st.privileged_observations[sl].contiguous(), dones[sl], *states))
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        state = torch.zeros(4, device=dev)  # [0] learning rate, [1..3] sums of (value loss, surrogate, entropy)
+        state[0] = self.learning_rate
+        lr_dev, stats = state[:1], state[1:]
+        grad_of = fa.grad_views()
+        std_p, std_is_log = std_param(ac)
+        std_c = std_p.detach()
+        pair.arm_domain_check()
+        stream = _abi.stream(dev)
+        n_steps = self.num_learning_epochs * nmb
+        for step_i in range(n_steps):
+            i = step_i % nmb
+            obs, cobs, d, hc_a, hc_c = blocks[i]
+            recs = direct_forward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, hc_a, hc_c)
+            x_a, x_c = recs[0]["out"].view(m, H), recs[1]["out"].view(m, H)
+            (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
+            dmu = torch.empty_like(mu)
+            dvalue = torch.empty(m, 1, device=dev, dtype=torch.float32)
+            acc = torch.empty(24, device=dev, dtype=torch.float32)
+            out = torch.empty(24, device=dev, dtype=torch.float32)
+            if std_is_log or mb_stats is not None:
+                _abi.call("lt_ppo_loss_opts", mu, std_c, value, *small, idx_all[i], m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
+                          None if mb_stats is None else mb_stats[i], dmu, dvalue, acc, out, stream)
+            else:
+                _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx_all[i], m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
+            _abi.call("lt_ppo_lr_rule", out[4:5] if adaptive else None, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out,
+                      grad_of[std_p], a_dim, stream)
+            dx = (torch.empty_like(x_a), torch.empty_like(x_c))
+            pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
+            direct_backward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, recs, dx, grad_of)
+            fa.step_dev(self.max_grad_norm, lr_dev)
+        sat, dom = pair.saturated(), pair.domain_max
+        pair.domain_max = None
+        zero = state.new_zeros(1)
+        lr, sv, ss, se, nsat, dmax = torch.cat((state, zero if sat is None else sat, zero if dom is None else dom.view(1))).tolist()  # the update's only host read
+        if nsat > 0:
+            import warnings
+
+            sat.zero_()
+            warnings.warn(f"lt_mlp_backward_pair_dx: {int(nsat)} workgroup-layers of the gradient chain reached the f16 image's bound "
+                          "(a gradient grew by more than 500x through the layers): those rows were saturated; set LT_FUSED_BACKWARD=0 "
+                          "to run the chain as f32 library GEMMs")
+        self.learning_rate = lr
+        for group in self.optimizer.param_groups:
+            group["lr"] = lr
+        if dmax >= float(_abi.CONSTS["LT_MLP_INPUT_CLAMP"]):
+            self._warn_mlp_domain()
+        st.clear()
+        return sv / n_steps, ss / n_steps, se / n_steps, None, None
 
     def _recurrent_update_unsupported(self) -> str | None:
         """Why `_recurrent_update` does not serve this policy / storage (None: it does)."""

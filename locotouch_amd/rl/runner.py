@@ -42,6 +42,8 @@ class OnPolicyRunner:
             self.alg_cfg["fused_recurrent_update"] = bool(self.cfg["fused_recurrent_update"])
         if "fused_gru_memories" in self.cfg:  # opt-in: the two switches above / below also serve GRU memories (csrc/lt_memory_gru.hip)
             self.alg_cfg["fused_gru_memories"] = bool(self.cfg["fused_gru_memories"])
+        if "direct_recurrent_update" in self.cfg:  # opt-in on top of `fused_recurrent_update` (rl/ppo.py `_direct_recurrent_update`)
+            self.alg_cfg["direct_recurrent_update"] = bool(self.cfg["direct_recurrent_update"])
         self.alg = PPO(ac, device=device, dist=self.dist, **self.alg_cfg)
         self.num_steps_per_env = int(self.cfg["num_steps_per_env"])
         self.save_interval = int(self.cfg.get("save_interval", 50))

@@ -54,6 +54,9 @@ def main() -> None:
                     help="recurrent (LSTM) policies: update on whole rollouts of env blocks, without padding (rl/ppo.py `_recurrent_update`)")
     ap.add_argument("--fused_gru_memories", action="store_true",
                     help="the two switches above also serve GRU memories (csrc/lt_memory_gru.hip); on its own it does nothing")
+    ap.add_argument("--direct_recurrent_update", action="store_true",
+                    help="with --fused_recurrent_update: that update without an autograd graph or a host read between its steps "
+                         "(rl/ppo.py `_direct_recurrent_update`)")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -76,6 +79,8 @@ def main() -> None:
         cfg["fused_recurrent_update"] = True
     if args.fused_gru_memories:
         cfg["fused_gru_memories"] = True
+    if args.direct_recurrent_update:
+        cfg["direct_recurrent_update"] = True
     device = f"cuda:{dist.local_rank}"
     torch.cuda.set_device(device)
     torch.manual_seed(cfg["seed"])

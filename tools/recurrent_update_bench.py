@@ -15,7 +15,12 @@ no counters in it).  A gain is claimed only where the legs' [min, max] intervals
 `update_ms` is the figure that compares), the off leg updates through `nn.GRU` on padded trajectories, the on leg through
 csrc/lt_memory_gru.hip, and the file is profiles/recurrent_update_gru_<n>.json.
 
-    python tools/recurrent_update_bench.py [--envs 4096] [--rounds 7] [--rnn_type lstm] [--off-result FILE] [--out profiles/recurrent_update_4096.json]
+`--direct`: the third leg, `direct_recurrent_update` on top of `fused_recurrent_update` (rl/ppo.py `_direct_recurrent_update`).  The legs are
+then `on` (this tree, the key off) and `direct` (the key on), the baseline is `--mode on` run in a checkout of the parent commit and handed
+to `--off-result`, the trace run is of the direct leg and records the dx hop's kernel (csrc/lt_mlp_dx.hip) with its share of all kernel
+time, and the file is profiles/recurrent_update_direct_[gru_]<n>.json.
+
+    python tools/recurrent_update_bench.py [--envs 4096] [--rounds 7] [--rnn_type lstm] [--direct] [--off-result FILE] [--out profiles/recurrent_update_4096.json]
 """
 from __future__ import annotations
 
@@ -35,7 +40,7 @@ sys.path.insert(0, REPO)
 TASK = "Isaac-RandCylinderTransportTeacher-LocoTouch-v1"
 HIDDEN = 256
 # (one set of kernel templates serves both cells, csrc/lt_memory_tile.h: the cell is a template argument in the traced name)
-KERNELS = {rnn: ("lt_memory_step_kernel", "lt_memory_seq_bwd_kernel", "lt_memory_seq_bwd_open_kernel") for rnn in ("lstm", "gru")}
+KERNELS = {rnn: ("lt_memory_step_kernel", "lt_memory_seq_bwd_kernel", "lt_memory_seq_bwd_open_kernel", "lt_mlp_dx_kernel") for rnn in ("lstm", "gru")}
 
 
 def stats(xs: list[float]) -> dict:
@@ -49,7 +54,7 @@ def tree() -> str | None:
         return None
 
 
-def make_runner(envs: int, on: bool, rnn_type: str = "lstm"):
+def make_runner(envs: int, on: bool, rnn_type: str = "lstm", direct: bool = False):
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.env import make
     from locotouch_amd.rl import OnPolicyRunner
@@ -57,16 +62,19 @@ def make_runner(envs: int, on: bool, rnn_type: str = "lstm"):
     cfg = dict(train_cfg(TASK), fused_recurrent_rollout=True, fused_recurrent_update=on)
     if rnn_type == "gru":
         cfg["fused_gru_memories"] = True
+    if direct:
+        cfg["direct_recurrent_update"] = True
     cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type=rnn_type, rnn_hidden_size=HIDDEN, rnn_num_layers=1)
     return OnPolicyRunner(make(TASK, num_envs=envs, device="cuda:0", seed=1), cfg, log_dir=None, device="cuda:0")
 
 
 def measure(mode: str, envs: int, rounds: int, warmup: int, rnn_type: str = "lstm") -> dict:
-    runner = make_runner(envs, mode != "off", rnn_type)
+    runner = make_runner(envs, mode != "off", rnn_type, direct=mode in ("direct", "trace_direct"))
     alg = runner.alg
-    out = {"mode": mode, "tree": tree(), "switch": bool(getattr(alg, "fused_recurrent_update", False)), "steps": runner.num_steps_per_env,
+    out = {"mode": mode, "tree": tree(), "switch": bool(getattr(alg, "fused_recurrent_update", False)),
+           "direct": bool(getattr(alg, "direct_recurrent_update", False)), "steps": runner.num_steps_per_env,
            "num_mini_batches": alg.num_mini_batches, "num_learning_epochs": alg.num_learning_epochs}
-    if mode == "trace":
+    if mode in ("trace", "trace_direct"):
         runner.learn(2)
         return out
     runner.learn(warmup + rounds)
@@ -76,24 +84,28 @@ def measure(mode: str, envs: int, rounds: int, warmup: int, rnn_type: str = "lst
     return out
 
 
-def kernel_trace(envs: int, rnn_type: str = "lstm") -> dict:
-    """Per-launch time of the sequence kernels: a `rocprofv3 --kernel-trace --stats` run of two iterations, nothing else traced."""
+def kernel_trace(envs: int, rnn_type: str = "lstm", mode: str = "trace") -> dict:
+    """Per-launch time of the sequence kernels (`trace_direct`: and of the dx hop, with each kernel's share of all kernel time): a
+    `rocprofv3 --kernel-trace --stats` run of two iterations, nothing else traced."""
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return {"error": "rocprofv3 not found"}
     tmp = tempfile.mkdtemp(prefix="recurrent_update_trace_")
     try:
         p = subprocess.run([exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "trace", "--", sys.executable,
-                            os.path.abspath(__file__), "--mode", "trace", "--envs", str(envs), "--rnn_type", rnn_type], capture_output=True, text=True,
+                            os.path.abspath(__file__), "--mode", mode, "--envs", str(envs), "--rnn_type", rnn_type], capture_output=True, text=True,
                            timeout=600)
         if p.returncode != 0:
             return {"error": f"rocprofv3 exit {p.returncode}: {p.stderr[-500:]}"}
-        rows = {}
+        rows, total_ns = {}, 0.0
         for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(path)):
+                total_ns += int(row["Calls"]) * float(row["AverageNs"])
                 if any(k in row.get("Name", "") for k in KERNELS[rnn_type]):
                     rows[row["Name"]] = {"calls": int(row["Calls"]), "average_us": float(row["AverageNs"]) / 1e3,
                                          "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
+        for r in rows.values():  # of the whole traced run (two iterations, rollouts included)
+            r["share_of_kernel_time"] = r["calls"] * r["average_us"] * 1e3 / total_ns
         return rows or {"error": "no sequence-kernel row in the kernel statistics"}
     except (OSError, subprocess.TimeoutExpired, KeyError, ValueError) as exc:
         return {"error": f"{type(exc).__name__}: {exc}"}
@@ -111,20 +123,22 @@ def main() -> None:
     ap.add_argument("--commit", help="what to record as measured_on_commit (default: git rev-parse --short HEAD, null outside a checkout)")
     ap.add_argument("--off-result", help="file holding the RESULT line of `--mode off` run in a checkout of the parent commit")
     ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
-    ap.add_argument("--mode", choices=["off", "on", "trace"], help="(internal) measure one leg and print it")
+    ap.add_argument("--direct", action="store_true", help="compare `direct_recurrent_update` on with it off (baseline: the parent's `--mode on`)")
+    ap.add_argument("--mode", choices=["off", "on", "direct", "trace", "trace_direct"], help="(internal) measure one leg and print it")
     args = ap.parse_args()
     if args.rounds < 5:
         sys.exit("--rounds must be at least 5")
     if args.mode:
         print("RESULT " + json.dumps(measure(args.mode, args.envs, args.rounds, args.warmup, args.rnn_type)))
         return
+    base, new = ("on", "direct") if args.direct else ("off", "on")  # the leg a gain is measured against, and the leg that is new
     legs = {}
     if args.off_result:
         line = [l for l in open(args.off_result).read().splitlines() if l.startswith("RESULT ")]
         if not line:
             sys.exit(f"{args.off_result}: no RESULT line")
-        legs["off"] = json.loads(line[-1][7:])
-    for mode in ("off", "on"):  # a fresh process each: no allocator state carried from one to the next
+        legs["baseline" if args.direct else "off"] = json.loads(line[-1][7:])
+    for mode in (base, new):  # a fresh process each: no allocator state carried from one to the next
         if mode in legs:
             continue
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--envs", str(args.envs), "--rounds", str(args.rounds),
@@ -133,22 +147,29 @@ def main() -> None:
         if p.returncode != 0 or not line:
             sys.exit(f"{mode}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
         legs[mode] = json.loads(line[-1][7:])
-    if legs["off"]["switch"] or not legs["on"]["switch"]:
+    if (not args.direct and legs["off"]["switch"]) or not legs["on"]["switch"]:
         sys.exit("the off leg ran with the switch on, or the on leg without it")
+    if args.direct and (legs["on"].get("direct") or not legs["direct"]["direct"] or legs.get("baseline", legs["on"]).get("direct")):
+        sys.exit("the direct leg ran without its key, or another leg with it")
 
-    def faster(key):  # on is faster by MORE than the spread of either leg: the intervals [min, max] do not even touch
-        return legs["on"][key]["max"] < legs["off"][key]["min"]
+    def faster(key, than=base):  # faster by MORE than the spread of either leg: the intervals [min, max] do not even touch
+        return legs[new][key]["max"] < legs[than][key]["min"]
 
     res = {"task": TASK, "envs": args.envs, "hidden": HIDDEN, "rnn_type": args.rnn_type, "measured_on_commit": args.commit or tree(),
            "notes": {"off": "the parent commit's tree where `tree` differs from the on leg's; else this tree with the switch off",
                      "update_ms": "runner wall clock of alg.update() (it ends in a host read)",
                      "iteration_ms": "runner wall clock, collection + learning",
                      "spread": "min and max over the rounds, beside the median"},
-           **legs, "kernels": None if args.no_trace else kernel_trace(args.envs, args.rnn_type),
-           "off_over_on_update": legs["off"]["update_ms"]["median"] / legs["on"]["update_ms"]["median"],
-           "off_over_on_iteration": legs["off"]["iteration_ms"]["median"] / legs["on"]["iteration_ms"]["median"],
-           "on_faster_than_the_spread": {"update": faster("update_ms"), "iteration": faster("iteration_ms")}}
-    out = args.out or os.path.join(REPO, "profiles", f"recurrent_update_{'gru_' if args.rnn_type == 'gru' else ''}{args.envs}.json")
+           **legs, "kernels": None if args.no_trace else kernel_trace(args.envs, args.rnn_type, "trace_direct" if args.direct else "trace"),
+           f"{base}_over_{new}_update": legs[base]["update_ms"]["median"] / legs[new]["update_ms"]["median"],
+           f"{base}_over_{new}_iteration": legs[base]["iteration_ms"]["median"] / legs[new]["iteration_ms"]["median"],
+           f"{new}_faster_than_the_spread": {"update": faster("update_ms"), "iteration": faster("iteration_ms")}}
+    if args.direct:
+        res["notes"]["baseline"] = "`--mode on` (fused_recurrent_update alone) in a checkout of the parent commit, through --off-result; absent: not measured"
+        if "baseline" in legs:
+            res["direct_faster_than_the_baseline_spread"] = {k: faster(k + "_ms", "baseline") for k in ("update", "iteration")}
+    name = "recurrent_update_direct_" if args.direct else "recurrent_update_"
+    out = args.out or os.path.join(REPO, "profiles", f"{name}{'gru_' if args.rnn_type == 'gru' else ''}{args.envs}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
