@@ -141,6 +141,7 @@ HEADERS = (
     ("POLICY", "lt_policy.h", True, ("lt_policy_step_launches",), ("lt_policy_desc", "lt_policy_memory")),  # one inference step of a recurrent policy
     ("PPO_OPTS", "lt_ppo_opts.h", False, (), ()),  # the log-std policy and per-minibatch advantage statistics
     ("MLP_DX", "lt_mlp_dx.h", True, (), ()),  # the input gradient of the actor and critic stacks (recurrent policies: the memories' dout)
+    ("PPO_SYM", "lt_ppo_sym.h", False, (), ()),  # the mirror-symmetric PPO update: table pack, row gather, the augmented batch's loss
 )
 
 

@@ -14,18 +14,9 @@
 #include "lt_env.h"
 #include "lt_host_check.h"
 #include "lt_internal.h"
+#include "lt_ppo_device.h"
 
 namespace {
-
-constexpr int MAX_A = 16;
-constexpr float kHalfLog2Pi = 0.91893853320467274178f;
-
-// sigma of a log-std policy (actor_critic.py:109-112).  The ONE exponential of lt_std_from_log (what a rollout stores as sigma) and of
-// the loss kernel (what it compares that sigma against): the same bits from the same log_std.  Formed in float64 and rounded once: an
-// error in sigma is the same in every row and enters a row's log-prob times z^2 (64 at |z| = 8), so the ulp an f32 exponential may be
-// off by showed as 6.5e-6 of max |dmu| against float64 where the nearest float32 sigma gives 1e-6 (tests/test_hip_ppo_opts_f64.py).
-// A workgroup forms its A sigmas once (the loss kernel keeps them in LDS).
-__device__ __forceinline__ float lt_sigma_of_log(float log_std) { return (float)exp((double)log_std); }
 
 // acc layout: [0] sum surrogate, [1] sum value loss, [2] sum kl, [3] unused, [4 .. 4 + A) sum over rows of d surrogate / d sigma_a,
 // [20] max |dmu|, [21] max |dvalue| (bit patterns of non-negative floats, merged with an integer atomicMax: order-independent) - the
@@ -63,26 +54,14 @@ __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restric
         const float om = old_mu[src * A + a], os = old_sigma[src * A + a];
         isg[a] = 1.f / sg;
         z[a] = (x - m) * isg[a];
-        if constexpr (LOG) logp += -0.5f * z[a] * z[a] - stdp[a] - kHalfLog2Pi;  // log sigma is the parameter itself
-        else logp += -0.5f * z[a] * z[a] - __logf(sg) - kHalfLog2Pi;
-        {
-          // The two sigmas are state-independent, so an error in sg / os is the SAME in every row and does not average out over the
-          // minibatch, and each action's KL is a small difference of terms ~0.1: with the library's -freciprocal-math quotients and
-          // __logf the mean KL sat 2 - 8 times further from float64 than plain float32 does (tests/test_hip_ppo_f64.py).  True
-          // divisions and logf here; the kernel waits on memory either way.
-#pragma clang fp reciprocal(off)
-          kl += logf(sg / os + 1.0e-5f) + (os * os + (om - m) * (om - m)) / (2.f * sg * sg) - 0.5f;
-        }
+        logp += lt_ppo_logp_term<LOG>(z[a], sg, stdp[a]);
+        kl += lt_ppo_kl_term(sg, os, om, m);
       }
     }
     float advr = adv[src];
     if constexpr (NORM) advr = (advr - adv_stats[0]) * adv_stats[1];
     const float ratio = __expf(logp - old_logp[src]);
-    const float s1 = -advr * ratio;
-    const float rc = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip);
-    const float s2 = -advr * rc;
-    const bool inside = ratio >= 1.f - clip && ratio <= 1.f + clip;
-    const float dsurr_dratio = (s1 > s2 || inside) ? -advr : 0.f;
+    LT_PPO_SURROGATE(advr, ratio, clip, s1, s2, dsurr_dratio)
     const float dlogp = dsurr_dratio * ratio * inv_m;
 #pragma unroll
     for (int a = 0; a < MAX_A; ++a) {
@@ -95,74 +74,20 @@ __global__ __launch_bounds__(256) void lt_ppo_loss_kernel(const float* __restric
     }
     const float v = value[row], R = returns[src];
     float vl, dv;
-    if (clipped_value) {
-      const float ov = old_values[src];
-      const float dcl = fminf(fmaxf(v - ov, -clip), clip);
-      const float vc = ov + dcl;
-      const float l1 = (v - R) * (v - R), l2 = (vc - R) * (vc - R);
-      const bool in_v = (v - ov) >= -clip && (v - ov) <= clip;
-      vl = fmaxf(l1, l2);
-      dv = (l1 > l2 || in_v) ? 2.f * (v - R) : 0.f;  // outside the clip range the clipped branch has no derivative
-    } else {
-      vl = (R - v) * (R - v);
-      dv = 2.f * (v - R);
-    }
+    LT_PPO_VALUE_LOSS(v, R, old_values, src, clip, clipped_value, vl, dv)
     dvalue[row] = vcoef * dv * inv_m;
     amax_v = fabsf(vcoef * dv * inv_m);
     part[0] = fmaxf(s1, s2);
     part[1] = vl;
     part[2] = kl;
   }
-  // block reduction (wave butterflies, then 4 partials through LDS), one atomic per block and slot
-  __shared__ float red[4][4 + MAX_A];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 4 + MAX_A; ++i) {
-    float v = part[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[wave][i] = v;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    amax_mu = fmaxf(amax_mu, __shfl_xor(amax_mu, off, 64));
-    amax_v = fmaxf(amax_v, __shfl_xor(amax_v, off, 64));
-  }
-  __shared__ float redm[4][2];
-  if (lane == 0) { redm[wave][0] = amax_mu; redm[wave][1] = amax_v; }
-  __syncthreads();
-  if (threadIdx.x < 4 + A && threadIdx.x != 3) {
-    const int i = threadIdx.x;
-    atomicAdd(acc + i, red[0][i] + red[1][i] + red[2][i] + red[3][i]);
-  } else if (threadIdx.x >= 64 && threadIdx.x < 66) {  // (another wave: one atomic per block and maximum)
-    const int j = threadIdx.x - 64;
-    atomicMax((unsigned*)acc + 20 + j, __float_as_uint(fmaxf(fmaxf(redm[0][j], redm[1][j]), fmaxf(redm[2][j], redm[3][j]))));
-  }
+  LT_PPO_BLOCK_REDUCE(part, amax_mu, amax_v, A, acc, false)
 }
 
-// The scalars of the minibatch loss from the sums of lt_ppo_loss_kernel (one wave, behind it on the stream): out[0] loss, [1] mean
-// surrogate, [2] mean value loss, [3] entropy, [4] mean KL, [8 + a] d loss / d sigma_a.  In PyTorch ops this was a dozen launches on
-// 12-float tensors.  entropy = sum_a (0.5 + 0.5 log 2 pi + log sigma_a) (the same in every row: the std is state-independent).
-// std_is_log (uniform): stdp is log sigma - the entropy's summand is the parameter itself, and its share of d loss / d log sigma_a is
-// -ecoef.
+// The scalars of the minibatch loss from the sums of lt_ppo_loss_kernel (one wave, behind it on the stream; lt_ppo_device.h has the slots)
 __global__ __launch_bounds__(64) void lt_ppo_finalize_kernel(const float* __restrict__ acc, const float* __restrict__ stdp, int A, float inv_m,
                                                              float vcoef, float ecoef, int std_is_log, float* __restrict__ out) {
-  const int a = threadIdx.x;
-  float e = 0.f;
-  if (a < A && std_is_log) {
-    e = 0.5f + kHalfLog2Pi + stdp[a];
-    out[8 + a] = acc[4 + a] - ecoef;
-  } else if (a < A) {
-    const float sg = stdp[a];
-    e = 0.5f + kHalfLog2Pi + logf(sg);
-    out[8 + a] = acc[4 + a] - ecoef / sg;
-  }
-  for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off, 64);
-  if (a == 0) {
-    const float surr = acc[0] * inv_m, vl = acc[1] * inv_m;
-    out[0] = surr + vcoef * vl - ecoef * e;
-    out[1] = surr; out[2] = vl; out[3] = e; out[4] = acc[2] * inv_m;
-  }
+  lt_ppo_finalize(acc, stdp, A, inv_m, vcoef, ecoef, std_is_log, out);
 }
 
 // ---- ELU backward fused with the bias gradient ---------------------------------------------------------------------------------

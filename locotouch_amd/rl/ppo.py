@@ -2,8 +2,9 @@
 
 Behavioural twin of the reference's `PPO` (loco_rl/loco_rl/algorithms/ppo.py:19-385) for the feed-forward
 ActorCritic path the LocoTouch agents use (agents/rsl_rl_ppo_cfg.py:11-30: clip 0.2, gamma 0.99, lam 0.95, lr 1e-3
-adaptive, desired KL 0.01, entropy 0.01, value coef 1.0, grad-norm 1.0, 5 epochs x 4 minibatches); the RND and
-symmetry branches of the reference are never enabled by those configs and are out of scope.
+adaptive, desired KL 0.01, entropy 0.01, value coef 1.0, grad-norm 1.0, 5 epochs x 4 minibatches), with the reference's `symmetry_cfg`
+branch (mirrored data augmentation and / or a mirror loss: `_symmetry_update`; with augmentation on the GPU inside `_direct_update`,
+include/lt_ppo_sym.h).  The RND branch is not built: a `rnd_cfg` is refused.
 
 Data parallelism (new): gradients live in one flat fp32 bucket that is all-reduced (mean) between
 `backward()` and the gradient clip, and the KL estimate is all-reduced before the learning-rate decision.
@@ -23,7 +24,13 @@ class PPO:
     def __init__(self, actor_critic: ActorCritic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998,
                  lam=0.95, value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu",
-                 normalize_advantage_per_mini_batch=False, dist: Dist | None = None, **unused):
+                 normalize_advantage_per_mini_batch=False, dist: Dist | None = None, rnd_cfg: dict | None = None,
+                 symmetry_cfg: dict | None = None, **unused):
+        if rnd_cfg is not None:
+            raise NotImplementedError("rnd_cfg: random network distillation is not built (DESIGN.md §7: it needs an `rnd_state` observation "
+                                      "group no env here produces); pass rnd_cfg=None")
+        self.symmetry = self._resolve_symmetry(symmetry_cfg, actor_critic)
+        self._sym_tables = None  # the packed device tables of `_direct_update` (include/lt_ppo_sym.h), built at the first symmetric update
         self.device = device
         self.dist = dist or Dist()
         self.actor_critic = actor_critic.to(device)
@@ -86,6 +93,34 @@ class PPO:
             why = self._direct_recurrent_unsupported()
             if why is not None:
                 raise ValueError(f"direct_recurrent_update: {why}")
+
+    @staticmethod
+    def _resolve_symmetry(symmetry_cfg, actor_critic):
+        """The reference's `symmetry_cfg` (ppo.py:66-84) as a dict of its own with every key present, or None.  Keys: use_data_augmentation,
+        use_mirror_loss, mirror_loss_coeff, data_augmentation_func (callable or 'module:function'), _env (the runner sets it)."""
+        if symmetry_cfg is None:
+            return None
+        known = ("use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff", "data_augmentation_func", "_env")
+        other = sorted(set(symmetry_cfg) - set(known))
+        if other:
+            raise ValueError(f"symmetry_cfg: unknown keys {other} (known: {list(known)})")
+        if getattr(actor_critic, "is_recurrent", False):
+            raise ValueError("symmetry_cfg: the policy is recurrent: its hidden states have no mirror (the reference does not support it either)")
+        sym = dict(use_data_augmentation=False, use_mirror_loss=False, mirror_loss_coeff=0.0, data_augmentation_func=None, _env=None)
+        sym.update(symmetry_cfg)
+        sym["use_data_augmentation"], sym["use_mirror_loss"] = bool(sym["use_data_augmentation"]), bool(sym["use_mirror_loss"])
+        sym["mirror_loss_coeff"] = float(sym["mirror_loss_coeff"] or 0.0)
+        if not (sym["use_data_augmentation"] or sym["use_mirror_loss"]):
+            import warnings
+
+            warnings.warn("Symmetry not used for learning. We will use it for logging instead.")
+        if isinstance(sym["data_augmentation_func"], str):
+            from .symmetry import string_to_callable
+
+            sym["data_augmentation_func"] = string_to_callable(sym["data_augmentation_func"])
+        if not callable(sym["data_augmentation_func"]):
+            raise ValueError(f"symmetry_cfg: data_augmentation_func is not callable: {sym['data_augmentation_func']!r}")
+        return sym
 
     # ---- data-parallel plumbing ------------------------------------------------------------------
     def _make_flat_grad_bucket(self) -> None:
@@ -242,9 +277,10 @@ class PPO:
         dev = obs.device
         adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         a_dim = small[0].shape[1]
-        state = torch.zeros(4, device=dev)  # [0] learning rate, [1..3] sums of (value loss, surrogate, entropy)
+        sym = self.symmetry
+        state = torch.zeros(4 if sym is None else 5, device=dev)  # [0] learning rate, [1..3] sums of (value loss, surrogate, entropy), [4] of the symmetry loss
         state[0] = self.learning_rate
-        lr_dev, stats = state[:1], state[1:]
+        lr_dev, stats = state[:1], state[1:4]
         grad_of = fa.grad_views()
         std_p, std_is_log = std_param(ac)
         std_c = std_p.detach()
@@ -257,24 +293,37 @@ class PPO:
         critic_at = fa.offset_of(next(iter(ac.critic.parameters())))
         two_buckets = split_buckets and 0 < critic_at < self._flat_grad.numel()
         perm, m = st.mini_batch_permutation(self.num_mini_batches)
-        perm_o, perm_co = obs[perm], cobs[perm]
         mb_stats = adv_stats(small[2], perm, m, self.num_mini_batches) if self.normalize_advantage_per_mini_batch else None
-        if perm_o.dtype != torch.float32:  # bf16 observation storage (BASELINE config 5): the update computes in f32
-            perm_o, perm_co = perm_o.float(), perm_co.float()
+        if sym is None:
+            rows = m
+            perm_o, perm_co = obs[perm], cobs[perm]
+            if perm_o.dtype != torch.float32:  # bf16 observation storage (BASELINE config 5): the update computes in f32
+                perm_o, perm_co = perm_o.float(), perm_co.float()
+        else:
+            # the mirror-augmented update (include/lt_ppo_sym.h): ONE gather per network writes every minibatch as 2 m contiguous f32 rows
+            # [original; mirrored]; the statistics above are those of the original rows (ppo.py:223-225 runs before the repeat)
+            rows = 2 * m
+            tab_o, tab_co, tab_a = self._symmetry_tables(dev, obs.shape[1], cobs.shape[1], a_dim)
+            perm_o, perm_co = (self._symmetry_gather(x, perm, m, t) for x, t in ((obs, tab_o), (cobs, tab_co)))
+            mirror_coeff = float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0
         # the same rows in the MLP kernels' split format (f16 hi | f16 lo): what the first layer's weight gradient multiplies, 20 times
-        split_o = (pair.split_rows(perm_o), pair.split_rows(perm_co)) if pair._fused_backward_possible(perm_o[:m], perm_co[:m]) else None
+        split_o = (pair.split_rows(perm_o), pair.split_rows(perm_co)) if pair._fused_backward_possible(perm_o[:rows], perm_co[:rows]) else None
         for step_i in range(self.num_learning_epochs * self.num_mini_batches):
             i = step_i % self.num_mini_batches
             idx = perm[i * m:(i + 1) * m]
-            o, co = perm_o[i * m:(i + 1) * m], perm_co[i * m:(i + 1) * m]
-            xs = (split_o[0][i * m:(i + 1) * m], split_o[1][i * m:(i + 1) * m]) if split_o is not None else None
+            o, co = perm_o[i * rows:(i + 1) * rows], perm_co[i * rows:(i + 1) * rows]
+            xs = (split_o[0][i * rows:(i + 1) * rows], split_o[1][i * rows:(i + 1) * rows]) if split_o is not None else None
             (mu, value), acts = pair.forward_raw(o, co)
             dmu = torch.empty_like(mu)
-            dvalue = torch.empty(m, 1, device=dev, dtype=torch.float32)
+            dvalue = torch.empty(rows, 1, device=dev, dtype=torch.float32)
             acc = torch.empty(24, device=dev, dtype=torch.float32)
             out = torch.empty(24, device=dev, dtype=torch.float32)
             stream = _abi.stream(dev)
-            if std_is_log or mb_stats is not None:
+            if sym is not None:
+                _abi.call("lt_ppo_loss_sym", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
+                          None if mb_stats is None else mb_stats[i], tab_a, mirror_coeff, dmu, dvalue, acc, out, state[4:5], stream)
+            elif std_is_log or mb_stats is not None:
                 _abi.call("lt_ppo_loss_opts", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
                           float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
                           None if mb_stats is None else mb_stats[i], dmu, dvalue, acc, out, stream)
@@ -304,7 +353,8 @@ class PPO:
             fa.step_dev(self.max_grad_norm, lr_dev)
             n_steps += 1
         sat = pair.saturated()
-        lr, sv, ss, se, nsat = torch.cat((state, sat if sat is not None else state[:0].new_zeros(1))).tolist()  # the update's only host read
+        read = torch.cat((state, sat if sat is not None else state[:0].new_zeros(1))).tolist()  # the update's only host read
+        (lr, sv, ss, se), nsat = read[:4], read[-1]
         if nsat > 0:
             import warnings
 
@@ -318,7 +368,110 @@ class PPO:
         if pair.domain_violated():
             self._warn_mlp_domain()
         st.clear()
-        return sv / n_steps, ss / n_steps, se / n_steps, None, None
+        return sv / n_steps, ss / n_steps, se / n_steps, None, None if sym is None else read[4] / n_steps
+
+    def _symmetry_tables(self, dev, obs_dim: int, critic_obs_dim: int, a_dim: int):
+        """The packed device tables (policy rows, critic rows, actions) of the env's mirror map, checked on the host by
+        `lt_sym_table_pack` and built once per PPO object."""
+        if self._sym_tables is None:
+            from .symmetry import mirror_tables
+
+            tables = mirror_tables(self.symmetry["_env"])
+            packed = []
+            for kind, width in (("policy", obs_dim), ("critic", critic_obs_dim), ("action", a_dim)):
+                src, sign = tables.of(kind)
+                if src.numel() != width:
+                    raise ValueError(f"symmetry_cfg: the env's {kind} mirror table covers {src.numel()} columns, the storage's rows have {width}")
+                buf = torch.empty(width, device=dev, dtype=torch.int32)
+                _abi.call("lt_sym_table_pack", src.contiguous(), sign.contiguous(), width, buf, _abi.stream(dev))
+                packed.append(buf)
+            self._sym_tables = tuple(packed)
+        return self._sym_tables
+
+    @staticmethod
+    def _symmetry_gather(storage_rows, perm, m: int, table):
+        """f32 [nmb * 2 * m, D]: minibatch b as rows [2 b m, 2 (b + 1) m) = [its m storage rows; their mirror images] (`lt_sym_gather_rows`)."""
+        R, D = storage_rows.shape
+        nmb = perm.numel() // m
+        if storage_rows.dtype not in (torch.float32, torch.bfloat16) or not storage_rows.is_contiguous():
+            raise ValueError(f"symmetry_cfg: observation rows are {storage_rows.dtype}, contiguous={storage_rows.is_contiguous()}: f32 or bf16 rows are served")
+        out = torch.empty(nmb * 2 * m, D, device=storage_rows.device, dtype=torch.float32)
+        _abi.call("lt_sym_gather_rows", storage_rows, int(storage_rows.dtype == torch.bfloat16), R, D, perm, nmb, m, table, out,
+                  _abi.stream(storage_rows.device))
+        return out
+
+    def _symmetry_direct_ok(self) -> bool:
+        """Whether `_direct_update` serves this symmetric update: augmentation by this package's `mirror_go1` (the kernels mirror through
+        its tables) on the conditions the direct update has without symmetry, on one rank.  Everything else runs `_symmetry_update`."""
+        from .fused_loss import std_param
+        from .symmetry import mirror_go1
+
+        sym = self.symmetry
+        if not (sym["use_data_augmentation"] and sym["data_augmentation_func"] is mirror_go1 and self.dist.world_size == 1):
+            return False
+        if not (self.direct_update and self._flat_adam is not None and self._fused_loss_ok(None) and std_param(self.actor_critic)[0].requires_grad):
+            return False
+        if self.normalize_advantage_per_mini_batch and (self.storage.num_envs * self.storage.num_steps) // self.num_mini_batches < 2:
+            return False
+        return self._packed_pair() is not None
+
+    def _symmetry_update(self):
+        """The reference's update with its `symmetry_cfg` branch as a chain of torch ops (ppo.py:216-337), on any device: per-minibatch
+        advantage normalisation BEFORE the repeat; observations and actions augmented by `data_augmentation_func` ([original; mirrored]);
+        old log-prob, advantages, returns and target values repeated; entropy, mu, sigma and the KL of the learning-rate rule on the first
+        B rows; surrogate and value loss as means over all num_aug * B rows; the symmetry loss MSE(mean_actions[B:],
+        mirror(mean_actions[:B]).detach()[B:]), part of the loss with `mirror_loss_coeff` under `use_mirror_loss`, else detached for the log.
+        sigma is not permuted: the mirrored actions are scored under Normal(mu(mirrored obs), std) with std in its own order."""
+        ac, sym = self.actor_critic, self.symmetry
+        func, env = sym["data_augmentation_func"], sym["_env"]
+        sums = [0.0, 0.0, 0.0, 0.0]
+        for b in self.storage.mini_batches(self.num_mini_batches, self.num_learning_epochs):
+            B = b.obs.shape[0]
+            obs, critic_obs, actions = b.obs, b.critic_obs, b.actions
+            old_log_prob, adv, returns, target_values = b.log_prob, b.advantages, b.returns, b.values
+            num_aug = 1
+            if self.normalize_advantage_per_mini_batch:
+                with torch.no_grad():
+                    adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            if sym["use_data_augmentation"]:
+                obs, actions = func(obs=obs, actions=actions, env=env, is_critic=False)
+                critic_obs, _ = func(obs=critic_obs, actions=None, env=env, is_critic=True)
+                num_aug = int(obs.shape[0] / B)
+                old_log_prob, target_values = old_log_prob.repeat(num_aug, 1), target_values.repeat(num_aug, 1)
+                adv, returns = adv.repeat(num_aug, 1), returns.repeat(num_aug, 1)
+            ac.act(obs)
+            log_prob = ac.get_actions_log_prob(actions)
+            value = ac.evaluate(critic_obs)
+            mu, sigma, entropy = ac.action_mean[:B], ac.action_std[:B], ac.entropy[:B]
+            if self.desired_kl is not None and self.schedule == "adaptive":
+                self._adapt_learning_rate(mu, sigma, b.mu, b.sigma)
+            ratio = torch.exp(log_prob - torch.squeeze(old_log_prob))
+            a = torch.squeeze(adv)
+            surrogate_loss = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
+            if self.use_clipped_value_loss:
+                clipped = target_values + (value - target_values).clamp(-self.clip_param, self.clip_param)
+                value_loss = torch.max((value - returns).pow(2), (clipped - returns).pow(2)).mean()
+            else:
+                value_loss = (returns - value).pow(2).mean()
+            loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+            if not sym["use_data_augmentation"]:
+                obs, _ = func(obs=obs, actions=None, env=env, is_critic=False)
+                num_aug = int(obs.shape[0] / B)
+            mean_actions = ac.act_inference(obs.detach().clone())
+            _, mirrored = func(obs=None, actions=mean_actions[:B], env=env, is_critic=False)
+            symmetry_loss = torch.nn.functional.mse_loss(mean_actions[B:], mirrored.detach()[B:])
+            if sym["use_mirror_loss"]:
+                loss = loss + sym["mirror_loss_coeff"] * symmetry_loss
+            else:
+                symmetry_loss = symmetry_loss.detach()
+            self._zero_grad()
+            loss.backward()
+            self._optim_step()
+            for k, v in enumerate((value_loss, surrogate_loss, entropy.mean(), symmetry_loss)):
+                sums[k] += v.item()
+        n = self.num_learning_epochs * self.num_mini_batches
+        self.storage.clear()
+        return sums[0] / n, sums[1] / n, sums[2] / n, None, sums[3] / n
 
     def _warn_mlp_domain(self) -> None:
         import warnings
@@ -570,6 +723,8 @@ class PPO:
 
     def _eager_update(self):
         ac = self.actor_critic
+        if self.symmetry is not None:  # (never a recurrent policy: refused at construction)
+            return self._direct_update(self._packed_pair()) if self._symmetry_direct_ok() else self._symmetry_update()
         sum_value = sum_surr = sum_ent = 0.0
         stats = None
         recurrent = getattr(ac, "is_recurrent", False)

@@ -44,6 +44,11 @@ class OnPolicyRunner:
             self.alg_cfg["fused_gru_memories"] = bool(self.cfg["fused_gru_memories"])
         if "direct_recurrent_update" in self.cfg:  # opt-in on top of `fused_recurrent_update` (rl/ppo.py `_direct_recurrent_update`)
             self.alg_cfg["direct_recurrent_update"] = bool(self.cfg["direct_recurrent_update"])
+        sym = self.alg_cfg.get("symmetry_cfg")
+        if sym is not None:  # on_policy_runner.py:60-63: the augmentation function is handed the env; PPO takes a plain dict
+            sym = sym.to_dict() if hasattr(sym, "to_dict") else (dict(sym) if isinstance(sym, dict) else dict(vars(sym)))
+            sym["_env"] = env
+            self.alg_cfg["symmetry_cfg"] = sym
         self.alg = PPO(ac, device=device, dist=self.dist, **self.alg_cfg)
         self.num_steps_per_env = int(self.cfg["num_steps_per_env"])
         self.save_interval = int(self.cfg.get("save_interval", 50))
@@ -119,7 +124,7 @@ class OnPolicyRunner:
             if hasattr(env, "curriculum_sync"):  # multi-rank: one all-reduce of the curriculum sums per rollout
                 env.curriculum_sync(self.dist, self.num_steps_per_env)
             t1 = time.time()
-            value_loss, surrogate_loss, entropy, _, _ = alg.update()
+            value_loss, surrogate_loss, entropy, _, symmetry_loss = alg.update()
             t2 = time.time()
             # one host read per iteration for the episode statistics
             if fin_rew:
@@ -138,6 +143,8 @@ class OnPolicyRunner:
                    "Policy/mean_noise_std": float(alg.actor_critic.action_std.detach().mean()),
                    "Train/mean_reward": (sum(rewbuffer) / len(rewbuffer)) if rewbuffer else None,
                    "Train/mean_episode_length": (sum(lenbuffer) / len(lenbuffer)) if lenbuffer else None}
+            if alg.symmetry is not None:  # on_policy_runner.py:284-285; records of other runs keep their keys
+                rec["Loss/symmetry"] = symmetry_loss
             if hasattr(env, "episode_log"):
                 rec.update(env.episode_log())
                 if fused is not None:  # the env's own per-episode accumulators stand in for rewbuffer / lenbuffer

@@ -57,6 +57,11 @@ def main() -> None:
     ap.add_argument("--direct_recurrent_update", action="store_true",
                     help="with --fused_recurrent_update: that update without an autograd graph or a host read between its steps "
                          "(rl/ppo.py `_direct_recurrent_update`)")
+    ap.add_argument("--symmetry_augmentation", action="store_true",
+                    help="PPO's mirrored data augmentation (rl/symmetry.py `mirror_go1`): every minibatch with its left-right mirror image; "
+                         "on the GPU inside the fused update (include/lt_ppo_sym.h)")
+    ap.add_argument("--mirror_loss_coeff", type=float, default=None, metavar="FLOAT",
+                    help="PPO's mirror loss with this coefficient (the symmetry loss is logged as Loss/symmetry either way)")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
@@ -81,6 +86,12 @@ def main() -> None:
         cfg["fused_gru_memories"] = True
     if args.direct_recurrent_update:
         cfg["direct_recurrent_update"] = True
+    if args.symmetry_augmentation or args.mirror_loss_coeff is not None:
+        from locotouch_amd.rl.symmetry import MIRROR_GO1
+
+        cfg["algorithm"] = dict(cfg["algorithm"], symmetry_cfg=dict(
+            use_data_augmentation=bool(args.symmetry_augmentation), use_mirror_loss=args.mirror_loss_coeff is not None,
+            mirror_loss_coeff=float(args.mirror_loss_coeff or 0.0), data_augmentation_func=MIRROR_GO1))
     device = f"cuda:{dist.local_rank}"
     torch.cuda.set_device(device)
     torch.manual_seed(cfg["seed"])
