@@ -1,0 +1,342 @@
+// The encoder in front of an ActorCriticEncoder's stacks (include/lt_encoder.h): out[r] = [ obs[r, :flat_dim] | enc(obs[r, -enc_in:]) ]
+// for one or two networks in ONE launch.
+//
+// Shape: n = num_envs rows in the rollout (4096), a minibatch's rows in the update (some 24 k); the reference encoder is
+// 78 -> 256 -> 128 -> 64 -> 64, 65 k MACs per row, 260 KB of weights - more than a CU's LDS.  A workgroup of four waves owns a ROW BLOCK
+// of RB rows (64, 32 or 16) and walks the layers:
+//   1. the head columns of its rows go to `out`, the tail columns into activation buffer A in LDS (zeros behind enc_in up to the next
+//      multiple of 16; rows are only 4-byte aligned, so scalar accesses);
+//   2. per layer, the weights pass through LDS a PANEL at a time: PM (64, 32 or 16) output features x the layer's input width.  A wave
+//      takes 16 x 16 tiles (16 features x 16 rows) of the panel's PM / 16 x RB / 16: the A operand (weights) and the B operand (the
+//      block's activations) are one ds_read_b128 each per 16-wide k block;
+//   3. the epilogue adds the bias, applies the activation and writes the tile into the OTHER activation buffer (and, in the training
+//      form, into acts[l]); the last layer writes the embedding behind the head columns of `out` instead.
+// The activations of the row block never leave LDS between layers.  grid (ceil(n / RB), networks), block 256.
+//
+// Arithmetic: v_mfma_f32_16x16x4_f32, exact f32 products, f32 accumulation, k blocks in index order dealt to four partial sums (block b
+// to chain b % 4) that are added pairwise, then the bias.  RB and PM move work between workgroups and waves, never a sum's order: a
+// row's bits depend on the row and the parameters alone.  Operand trick as lt_memory_tile.h: MFMA step s of a 16-wide k block consumes
+// the k-set {16 b + 4 q + s}, so lane (i, q) supplies component s of ONE 16-byte LDS read for either operand.
+//
+// LDS strides (rows of both activation buffers and of the panel) are round_up(width, 16) + 8 floats, an odd multiple of 8: the 16 lanes
+// of a ds_read_b128 lane group start at 16 distinct multiples of 4 banks.
+#include "lt_encoder.h"
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "lt_device_prims.h"
+#include "lt_env.h"
+#include "lt_host_check.h"
+#include "lt_internal.h"
+
+static_assert(LT_ENCODER_MAX_LAYERS == LT_MLP_MAX_LAYERS, "lt_encoder.h states its layer limit as lt_mlp's");
+
+namespace {
+
+using lt::f32x4;
+
+constexpr int kMaxL = LT_ENCODER_MAX_LAYERS;
+constexpr int kLdsBytes = 160 * 1024;
+
+struct EncNet {
+  const float* obs; long long obs_stride;
+  const float* w[kMaxL]; const float* b[kMaxL];
+  float* out; float* acts[kMaxL];
+  int obs_dim, flat_dim, L;
+  int dims[kMaxL + 1];  // dims[0] = enc_in, dims[l + 1] = outputs of layer l
+  int act, final_act;
+  int stride[2];        // LDS row strides of activation buffers A (inputs of even layers) and B (of odd layers)
+};
+struct EncArgs { EncNet net[2]; int n, RB, PM, off_b, off_panel; };  // off_*: float offsets of buffer B and the panel in LDS
+
+__host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+__host__ __device__ inline int lds_stride(int width) { return round_up(width, 16) + 8; }
+
+__device__ __forceinline__ float activate(int kind, float x) {
+  if (kind == LT_ACT_ELU) return x > 0.f ? x : expm1f(x);
+  if (kind == LT_ACT_RELU) return x > 0.f ? x : 0.f;
+  if (kind == LT_ACT_TANH) return tanhf(x);
+  return x;
+}
+
+// floor(2^32 / d) + 1 (d a power of two: 2^32 / d): __umulhi(i, .) is i / d exactly while i * d < 2^32 - here i < 64 * 512, d <= 512
+__device__ __forceinline__ unsigned div_magic(int d) { return 0xFFFFFFFFu / (unsigned)d + 1u; }
+
+// Stages a [rows][cols] tile (elements of type V: float, or f32x4 where the source allows 16-byte loads; cols in elements) into LDS rows
+// of dst_stride FLOATS: element (r, c) from src + r * src_stride floats where r < rows_ok and c < cols_ok, else zeros.  The loads of a
+// thread are independent and U of them are in flight before the first LDS write: a load per loop trip would expose the whole
+// global-memory latency once per element (measured: 110 us of a 112 us launch at 4096 rows).
+template <int U, class V>
+__device__ __forceinline__ void stage(const float* __restrict__ src, long long src_stride, int rows_ok, int cols_ok, float* __restrict__ dst,
+                                      int dst_stride, int rows, int cols, int tid) {
+  constexpr int VW = sizeof(V) / sizeof(float);
+  const int total = rows * cols;
+  const unsigned magic = div_magic(cols);
+  for (int base = 0; base < total; base += 256 * U) {
+    V v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = base + 256 * u + tid;
+      const int r = (int)__umulhi((unsigned)idx, magic), c = idx - r * cols;
+      v[u] = V{};
+      if (idx < total && r < rows_ok && c < cols_ok) v[u] = *(const V*)(src + (long long)r * src_stride + VW * c);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = base + 256 * u + tid;
+      const int r = (int)__umulhi((unsigned)idx, magic), c = idx - r * cols;
+      if (idx < total) *(V*)(dst + r * dst_stride + VW * c) = v[u];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void lt_encoder_kernel(const EncArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const EncNet& p = a.net[blockIdx.y];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = lane & 15, q = lane >> 4;
+  const int RB = a.RB, PM = a.PM;
+  const int r0 = blockIdx.x * RB;
+  const int rows = min(RB, a.n - r0);
+  const int nsub = (rows + 15) / 16;
+  const int E = p.dims[p.L], ow = p.flat_dim + E;
+  float* buf[2] = {lds, lds + a.off_b};
+  float* panel = lds + a.off_panel;
+
+  // ---- 1. head columns -> out (copies), tail columns -> buffer A (whole 16-row sub-tiles and 16-wide k blocks; zeros where there is no
+  // row or no column)
+  for (int base = 0; base < rows * p.flat_dim; base += 256 * 8) {  // (eight independent loads in flight, as in `stage`)
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = base + 256 * u + tid, r = idx / p.flat_dim, c = idx - r * p.flat_dim;
+      v[u] = idx < rows * p.flat_dim ? p.obs[(long long)(r0 + r) * p.obs_stride + c] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int idx = base + 256 * u + tid, r = idx / p.flat_dim, c = idx - r * p.flat_dim;
+      if (idx < rows * p.flat_dim) p.out[(long long)(r0 + r) * ow + c] = v[u];
+    }
+  }
+  {
+    const int K = p.dims[0];
+    stage<16, float>(p.obs + (long long)r0 * p.obs_stride + (p.obs_dim - K), p.obs_stride, rows, K, buf[0], p.stride[0], 16 * nsub, round_up(K, 16), tid);
+  }
+
+  // ---- 2. the layers
+  for (int l = 0; l < p.L; ++l) {
+    const int K = p.dims[l], K16 = round_up(K, 16), O = p.dims[l + 1], kp = K16 + 8, nblk = K16 / 16;
+    const bool last = l == p.L - 1;
+    const float* in = buf[l & 1];
+    float* dst = buf[(l + 1) & 1];
+    const int sin = p.stride[l & 1], sd = p.stride[(l + 1) & 1];
+    const float* __restrict__ w = p.w[l];
+    const float* __restrict__ bias = p.b[l];
+    float* actl = p.acts[l];
+    const int kind = last ? p.final_act : p.act;
+    for (int p0 = 0; p0 < O; p0 += PM) {
+      // the panel: rows p0 .. p0 + pm16 - 1 of W_l (zeros behind O and behind K).  The barrier in front keeps it until every wave has
+      // left the previous panel - and, for a layer's first panel, until the previous layer's activations are all written
+      const int pm16 = min(PM, round_up(O - p0, 16)), mtiles = pm16 / 16;
+      __syncthreads();
+      if ((K & 3) == 0 && ((uintptr_t)w & 15) == 0)
+        stage<8, f32x4>(w + (long long)p0 * K, K, O - p0, K / 4, panel, kp, pm16, K16 / 4, tid);
+      else
+        stage<16, float>(w + (long long)p0 * K, K, O - p0, K, panel, kp, pm16, K16, tid);
+      __syncthreads();
+      for (int tile = wave; tile < mtiles * nsub; tile += 4) {
+        const int mt = tile % mtiles, s = tile / mtiles;
+        const float* ap = panel + (16 * mt + i) * kp + 4 * q;
+        const float* bp = in + (16 * s + i) * sin + 4 * q;
+        f32x4 acc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int b0 = 0; b0 < nblk; b0 += 4) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (b0 + u < nblk) {
+              const f32x4 wv = *(const f32x4*)(ap + 16 * (b0 + u));
+              const f32x4 xv = *(const f32x4*)(bp + 16 * (b0 + u));
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[u] = lt::mfma_16x16x4(wv[e], xv[e], acc[u]);
+            }
+          }
+        }
+        // epilogue: sum[v] of lane (i, q) is D[4 q + v][i] = feature f0 + v of row 16 s + i
+        const f32x4 sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        const int f0 = p0 + 16 * mt + 4 * q, row = 16 * s + i;
+        const bool row_ok = row < rows;
+        const long long gr = r0 + row;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (f0 < O) {  // (O is a multiple of 8 and f0 of 4: all four features or none)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = sum[e] + bias[f0 + e];
+          if (last && actl && row_ok) {  // the pre-activation embedding
+#pragma unroll
+            for (int e = 0; e < 4; ++e) actl[gr * O + f0 + e] = v[e];
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = activate(kind, v[e]);
+          if (row_ok) {
+            float* g = last ? p.out + gr * ow + p.flat_dim + f0 : actl ? actl + gr * O + f0 : nullptr;
+            if (g) {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) g[e] = v[e];
+            }
+          }
+        }
+        // the next layer's input (zeros in the columns behind O up to its k blocks' end)
+        if (!last) *(f32x4*)(dst + row * sd + f0) = v;
+      }
+    }
+  }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------------
+int check_desc(const char* fn, const char* who, const lt_encoder_desc* d) {
+  if (!d) return refuse(fn, who, "", "non-null");
+  if (d->num_layers < 1 || d->num_layers > kMaxL) return refuse(fn, who, ".num_layers", "in [1, LT_ENCODER_MAX_LAYERS]");
+  if (d->obs_dim < 1) return refuse(fn, who, ".obs_dim", "at least 1");
+  if (d->enc_in < 1 || d->enc_in > LT_ENCODER_MAX_WIDTH || d->enc_in > d->obs_dim)
+    return refuse(fn, who, ".enc_in", "in [1, LT_ENCODER_MAX_WIDTH] and at most obs_dim");
+  if (d->flat_dim < 0 || d->flat_dim > d->obs_dim) return refuse(fn, who, ".flat_dim", "in [0, obs_dim]");
+  for (int l = 0; l < d->num_layers; ++l)
+    if (d->dims[l] < 8 || d->dims[l] > LT_ENCODER_MAX_WIDTH || d->dims[l] % 8 != 0) {
+      char field[32];
+      snprintf(field, sizeof field, ".dims[%d]", l);
+      return refuse(fn, who, field, "a multiple of 8 in [8, LT_ENCODER_MAX_WIDTH]");
+    }
+  if (d->activation != LT_ACT_ELU && d->activation != LT_ACT_RELU && d->activation != LT_ACT_TANH)
+    return refuse(fn, who, ".activation", "LT_ACT_ELU, LT_ACT_RELU or LT_ACT_TANH");
+  if (d->final_activation != LT_ACT_NONE && d->final_activation != LT_ACT_ELU && d->final_activation != LT_ACT_RELU && d->final_activation != LT_ACT_TANH)
+    return refuse(fn, who, ".final_activation", "LT_ACT_NONE, LT_ACT_ELU, LT_ACT_RELU or LT_ACT_TANH");
+  return LT_OK;
+}
+
+bool overlaps(const void* a, long long na, const void* b, long long nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + (uintptr_t)nb * sizeof(float) && b0 < a0 + (uintptr_t)na * sizeof(float);
+}
+
+int check_net(const char* fn, const char* who, const lt_encoder_net* net, int n) {
+  if (!net) return refuse(fn, who, "", "non-null");
+  char sub[32];
+  snprintf(sub, sizeof sub, "%s.desc", who);
+  if (const int rc = check_desc(fn, sub, &net->desc)) return rc;
+  const lt_encoder_desc& d = net->desc;
+  if (net->obs_stride < d.obs_dim) return refuse(fn, who, ".obs_stride", "at least obs_dim");
+  if (const int rc = check_ptrs(fn, who, {{".obs", net->obs, 4}, {".out", net->out, 4}})) return rc;
+  const int L = d.num_layers;
+  for (int l = 0; l < L; ++l) {
+    char wn[32], bn[32];
+    snprintf(wn, sizeof wn, ".weight[%d]", l);
+    snprintf(bn, sizeof bn, ".bias[%d]", l);
+    if (const int rc = check_ptrs(fn, who, {{wn, net->weight[l], 4}, {bn, net->bias[l], 4}})) return rc;
+  }
+  // the training form: every hidden layer's buffer (and the pre-activation embedding's, with a final activation), or none at all
+  bool any = false;
+  for (int l = 0; l < kMaxL; ++l) any = any || net->acts[l] != nullptr;
+  if (any) {
+    const int need = d.final_activation != LT_ACT_NONE ? L : L - 1;
+    for (int l = 0; l < kMaxL; ++l) {
+      char an[32];
+      snprintf(an, sizeof an, ".acts[%d]", l);
+      if (l < need) {
+        if (const int rc = check_ptr(fn, who, {an, net->acts[l], 4})) return rc;
+      } else if (net->acts[l]) {
+        return refuse(fn, who, an, "NULL (only hidden layers, and the embedding with a final activation, have a buffer)");
+      }
+    }
+  }
+  const long long ow = d.flat_dim + d.dims[L - 1];
+  if (overlaps(net->out, (long long)n * ow, net->obs, (long long)(n - 1) * net->obs_stride + d.obs_dim))
+    return refuse(fn, who, ".out", "a buffer that does not overlap obs");
+  return LT_OK;
+}
+
+void set_net(EncNet& r, const lt_encoder_net* net) {
+  const lt_encoder_desc& d = net->desc;
+  r.obs = net->obs; r.obs_stride = net->obs_stride; r.out = net->out;
+  r.obs_dim = d.obs_dim; r.flat_dim = d.flat_dim; r.L = d.num_layers;
+  r.act = d.activation; r.final_act = d.final_activation;
+  r.dims[0] = d.enc_in;
+  r.stride[0] = r.stride[1] = 0;
+  for (int l = 0; l < kMaxL; ++l) {
+    const bool used = l < d.num_layers;
+    r.w[l] = used ? net->weight[l] : nullptr; r.b[l] = used ? net->bias[l] : nullptr; r.acts[l] = used ? net->acts[l] : nullptr;
+    r.dims[l + 1] = used ? d.dims[l] : 0;
+    if (used && lds_stride(r.dims[l]) > r.stride[l & 1]) r.stride[l & 1] = lds_stride(r.dims[l]);  // layer l reads buffer l & 1
+  }
+}
+
+int cu_count() {
+  static int cus = 0;  // (every device of a node is the same chip)
+  if (cus == 0) {
+    int dev = 0, v = 0;
+    cus = hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0 ? v : 256;
+  }
+  return cus;
+}
+
+// Row block, panel height and the LDS carve of one launch (nets networks set in a.net): the largest row block that still gives every
+// CU a workgroup, then the highest panel that fits beside its activations.  RB = PM = 16 always fits: 2 x 16 x 520 + 16 x 520 floats.
+int plan(EncArgs& a, int nets) {
+  int sa = 0, sb = 0, kp = 0, omax = 0;
+  for (int k = 0; k < nets; ++k) {
+    const EncNet& r = a.net[k];
+    sa = r.stride[0] > sa ? r.stride[0] : sa;
+    sb = r.stride[1] > sb ? r.stride[1] : sb;
+    for (int l = 0; l < r.L; ++l) {
+      kp = lds_stride(r.dims[l]) > kp ? lds_stride(r.dims[l]) : kp;
+      omax = r.dims[l + 1] > omax ? r.dims[l + 1] : omax;
+    }
+  }
+  const int cus = cu_count();
+  for (const int rb : {64, 32, 16}) {
+    if (rb > 16 && (long long)((a.n + rb - 1) / rb) * nets < cus) continue;
+    for (const int pm : {64, 32, 16}) {
+      if (pm > 16 && pm >= 2 * round_up(omax, 16)) continue;  // (higher than the widest layer: rows nobody reads)
+      const int floats = rb * (sa + sb) + pm * kp;
+      if (floats * (int)sizeof(float) > kLdsBytes) continue;
+      a.RB = rb; a.PM = pm; a.off_b = rb * sa; a.off_panel = rb * (sa + sb);
+      return floats * (int)sizeof(float);
+    }
+  }
+  return 0;  // (unreachable for a validated descriptor)
+}
+
+}  // namespace
+
+extern "C" {
+
+int lt_encoder_validate(const lt_encoder_desc* desc) { return check_desc("lt_encoder_validate", "desc", desc); }
+
+int lt_encoder_forward_launches(const lt_encoder_desc* actor, const lt_encoder_desc* critic) {
+  const char* fn = "lt_encoder_forward_launches";
+  if (const int rc = check_desc(fn, "actor", actor)) return rc;
+  if (critic)
+    if (const int rc = check_desc(fn, "critic", critic)) return rc;
+  return 1;
+}
+
+int lt_encoder_forward(const lt_encoder_net* actor, const lt_encoder_net* critic, int n, void* stream) {
+  const char* fn = "lt_encoder_forward";
+  if (n < 1 || n > 16 * 65535) return refuse(fn, "", "n", "in [1, 16 * 65535]");
+  if (const int rc = check_net(fn, "actor", actor, n)) return rc;
+  if (critic)
+    if (const int rc = check_net(fn, "critic", critic, n)) return rc;
+  EncArgs a;
+  const int nets = critic ? 2 : 1;
+  set_net(a.net[0], actor);
+  set_net(a.net[1], critic ? critic : actor);
+  a.n = n;
+  const int lds = plan(a, nets);
+  if (lds <= 0) return refuse(fn, "the layers do not fit the LDS");
+  if (const int e = lt_ensure_dynamic_lds((const void*)lt_encoder_kernel, kLdsBytes)) { lt_set_error(hipGetErrorString((hipError_t)e)); return LT_EHIP; }
+  hipLaunchKernelGGL(lt_encoder_kernel, dim3((unsigned)((n + a.RB - 1) / a.RB), (unsigned)nets), dim3(256), lds, (hipStream_t)stream, a);
+  return launch_status(fn);
+}
+
+}  // extern "C"

@@ -1,0 +1,127 @@
+"""The encoder in front of an `ActorCriticEncoder`'s stacks on the HIP library (include/lt_encoder.h, csrc/lt_encoder.hip): one launch
+writes `[ obs[:, :flat_dim] | enc(obs[:, -enc_in:]) ]` for the actor and, when it has an encoder, the critic.  The kernel reads the live
+`nn.Linear` parameters: nothing is packed, so there is nothing to refresh after an optimizer step.
+
+`EncoderPair` holds the descriptors of a policy's encoders; `forward(obs, critic_obs, out, critic_out, acts=...)` is the launch - the
+rollout's form without `acts`, the update's with them (the activation behind every hidden layer and, with a final activation, the
+pre-activation embedding: what `rl/mlp.py::backward_chain` and the final activation's derivative read).
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from .. import _abi
+
+_ACT_IDS = {nn.ELU: "LT_ACT_ELU", nn.ReLU: "LT_ACT_RELU", nn.Tanh: "LT_ACT_TANH"}
+
+
+def make_desc(obs_dim: int, flat_dim: int, enc_in: int, dims, activation: int, final_activation: int):
+    """LtEncoderDesc of an encoder with layer outputs `dims` (the last one is the embedding width); nothing is checked here."""
+    d = _abi.LtEncoderDesc()
+    d.obs_dim, d.flat_dim, d.enc_in, d.num_layers = int(obs_dim), int(flat_dim), int(enc_in), len(dims)
+    for l, w in enumerate(list(dims)[:_abi.ENCODER_CONSTS["LT_ENCODER_MAX_LAYERS"]]):
+        d.dims[l] = int(w)
+    d.activation, d.final_activation = int(activation), int(final_activation)
+    return d
+
+
+def validate(desc) -> str | None:
+    """None for a descriptor the kernel serves, else the library's refusal text (host only)."""
+    import ctypes
+
+    lib = _abi.load()
+    if lib.lt_encoder_validate(ctypes.byref(desc)) == 0:
+        return None
+    return lib.lt_last_error().decode()
+
+
+def make_net(desc, obs: torch.Tensor, weights, biases, out: torch.Tensor, acts=None, obs_stride: int | None = None):
+    """LtEncoderNet of one network: `obs` rows read in place (`obs_stride` floats apart; default: the tensor's own row stride)."""
+    net = _abi.LtEncoderNet()
+    net.desc = desc
+    net.obs = obs.data_ptr()
+    net.obs_stride = int(obs.stride(0) if obs_stride is None else obs_stride)
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        net.weight[l], net.bias[l] = w.data_ptr(), b.data_ptr()
+    net.out = out.data_ptr()
+    for l, a in enumerate(acts or ()):
+        net.acts[l] = None if a is None else a.data_ptr()
+    return net
+
+
+def describe(enc: nn.Module, obs_dim: int, flat_dim: int):
+    """(LtEncoderDesc, [Linear...]) of an `MLP` encoder module (rl/models.py) reading the last `in_features` of `obs_dim` columns;
+    ValueError naming the reason for a module the kernel does not serve."""
+    mods = list(enc.model) if hasattr(enc, "model") else list(enc)
+    linears = [m for m in mods if isinstance(m, nn.Linear)]
+    if not linears or any(m.bias is None or m.weight.dtype != torch.float32 or not m.weight.is_contiguous() for m in linears):
+        raise ValueError("the encoder must be a stack of contiguous f32 Linear layers with biases")
+    C = _abi.CONSTS
+    acts, final, i = set(), C["LT_ACT_NONE"], 0
+    for l, lin in enumerate(linears):  # Linear, activation, ..., Linear[, final activation]
+        if i >= len(mods) or mods[i] is not lin:
+            raise ValueError("the encoder must be Linear layers with one activation between them")
+        i += 1
+        last = l == len(linears) - 1
+        if i < len(mods) and not isinstance(mods[i], nn.Linear):
+            a = mods[i]
+            if type(a) not in _ACT_IDS or (type(a) is nn.ELU and a.alpha != 1.0):
+                raise ValueError(f"encoder activation {type(a).__name__} is not served (ELU with alpha 1, ReLU, Tanh)")
+            if last:
+                final = C[_ACT_IDS[type(a)]]
+            else:
+                acts.add(type(a))
+            i += 1
+        elif not last:
+            raise ValueError("an activation must follow every hidden layer of the encoder")
+    if i != len(mods) or len(acts) > 1:
+        raise ValueError("the encoder must be Linear layers with one activation between them")
+    if any(a.out_features != b.in_features for a, b in zip(linears[:-1], linears[1:])):
+        raise ValueError("the encoder's layers do not chain")
+    if len(linears) > _abi.ENCODER_CONSTS["LT_ENCODER_MAX_LAYERS"]:
+        raise ValueError("the encoder has more than LT_ENCODER_MAX_LAYERS layers")
+    act = C[_ACT_IDS[next(iter(acts))]] if acts else C["LT_ACT_ELU"]  # (a single Linear has no hidden activation: any served id)
+    desc = make_desc(obs_dim, flat_dim, linears[0].in_features, [m.out_features for m in linears], act, final)
+    why = validate(desc)
+    if why is not None:
+        raise ValueError(why)
+    return desc, linears
+
+
+class EncoderPair:
+    """The encoders of an `ActorCriticEncoder` as one launch: the actor's and, when `ac.critic_with_encoder`, the critic's."""
+
+    def __init__(self, ac, obs_dim: int, critic_obs_dim: int):
+        self.a_desc, self.a_linears = describe(ac.actor_encoder, obs_dim, ac.actor_flatten_obs_dim)
+        self.a_width = ac.actor_flatten_obs_dim + self.a_linears[-1].out_features
+        if self.a_width != ac.actor[0].in_features:
+            raise ValueError(f"the actor reads {ac.actor[0].in_features} columns, its encoder's rows have {self.a_width}")
+        self.c_desc = self.c_linears = None
+        self.c_width = critic_obs_dim
+        if ac.critic_with_encoder:
+            self.c_desc, self.c_linears = describe(ac.critic_encoder, critic_obs_dim, ac.critic_flatten_obs_dim)
+            self.c_width = ac.critic_flatten_obs_dim + self.c_linears[-1].out_features
+            if self.c_width != ac.critic[0].in_features:
+                raise ValueError(f"the critic reads {ac.critic[0].in_features} columns, its encoder's rows have {self.c_width}")
+
+    @staticmethod
+    def _acts(desc, n, device):
+        """The training form's buffers of one network: hidden activations, then the pre-activation embedding if a final activation is set."""
+        count = desc.num_layers if desc.final_activation != _abi.CONSTS["LT_ACT_NONE"] else desc.num_layers - 1
+        return [torch.empty(n, desc.dims[l], device=device, dtype=torch.float32) for l in range(count)]
+
+    def forward(self, obs, critic_obs, out, critic_out=None, train: bool = False):
+        """One launch.  Returns (actor acts, critic acts) in the training form, else (None, None)."""
+        n = obs.shape[0]
+        for x in (obs, critic_obs if self.c_desc is not None else None):
+            if x is not None and (x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1):
+                raise ValueError("the encoder reads f32 rows with unit column stride")
+        a_acts = self._acts(self.a_desc, n, obs.device) if train else None
+        c_acts = self._acts(self.c_desc, n, obs.device) if train and self.c_desc is not None else None
+        a = make_net(self.a_desc, obs, [m.weight for m in self.a_linears], [m.bias for m in self.a_linears], out, a_acts)
+        c = None
+        if self.c_desc is not None:
+            c = make_net(self.c_desc, critic_obs, [m.weight for m in self.c_linears], [m.bias for m in self.c_linears], critic_out, c_acts)
+        _abi.call("lt_encoder_forward", a, c, n, _abi.stream(obs.device))
+        return a_acts, c_acts

@@ -34,6 +34,12 @@ and one launch of the cell's `finish` behind the last step leaves where(dones[T-
 4 "Recurrent rollout step").  What differs between the kinds stands in the `Cell` table of rl/memory_seq.py: the state is (h, c) or h
 alone, the launches are `lt_memory_step` / `lt_memory_finish` (csrc/lt_memory.hip) or `lt_memory_gru_step` / `lt_memory_gru_finish`
 (csrc/lt_memory_gru.hip) - both a cell on the one row-block kernel of csrc/lt_memory_tile.h.
+
+Encoder policies (`ActorCriticEncoder`, behind `fused_encoder_policy=True`: the noise comes from the kernels' Philox stream): a step is
+    [lt_encoder_forward: storage slot t -> the rows the stacks read, [head columns | embedding of the tail columns], for the actor and,
+     when it has an encoder, the critic (include/lt_encoder.h; it reads the live parameters, nothing is packed)]
+ -> [policy + value on those rows (a critic without an encoder reads its slot as ever)] -> [env step]
+three launches on the one stream; the storage keeps the raw rows, `compute_returns` stays the eager `evaluate`.
 """
 from __future__ import annotations
 
@@ -59,6 +65,30 @@ def recurrent_unsupported(ac, storage, gru_memories: bool = False) -> str | None
             return f"{name} is not f32"
     if storage.observations.dtype != torch.float32:
         return "bf16 observation rows: the memory step reads f32 rows"
+    return None
+
+
+def encoder_policy_unsupported(alg, normalizers: bool, use_packed_mlp: bool = True) -> str | None:
+    """Why the fused rollout does not serve this policy behind `fused_encoder_policy` (None: it does): an `ActorCriticEncoder` on a GPU
+    whose encoders include/lt_encoder.h serves and whose stacks lt_mlp serves, on f32 observation rows, without normalisers."""
+    from .encoder import EncoderPair
+    from .mlp import describe
+
+    ac, st = alg.actor_critic, alg.storage
+    if torch.device(alg.device).type != "cuda":
+        return f"the device is {alg.device!r}: its kernels run on a GPU only"
+    if type(ac).__name__ != "ActorCriticEncoder":
+        return f"the policy is a {type(ac).__name__}, not an ActorCriticEncoder"
+    if normalizers:
+        return "empirical_normalization is not served together with an encoder policy: the normaliser would have to feed the encoder launch"
+    if st.observations.dtype != torch.float32:
+        return "bf16 observation rows: the encoder launch reads f32 rows"
+    if not use_packed_mlp or describe(ac.actor) is None or describe(ac.critic) is None:
+        return "the actor or the critic stack is outside lt_mlp's limits (rl/mlp.py describe), or use_packed_mlp is off"
+    try:
+        EncoderPair(ac, st.observations.shape[-1], st.privileged_observations.shape[-1])
+    except ValueError as e:
+        return str(e)
     return None
 
 
@@ -92,9 +122,13 @@ class FusedRollout:
     rows), so nothing copies observations."""
 
     def __init__(self, env, alg, use_packed_mlp: bool = True, obs_normalizer=None, critic_obs_normalizer=None,
-                 fused_gru_memories: bool = False):
+                 fused_gru_memories: bool = False, fused_encoder_policy: bool = False):
         from ..env import LocoTouchVecEnv
 
+        if fused_encoder_policy:  # (first: what the key needs is refused by name, whatever else is wrong)
+            why = encoder_policy_unsupported(alg, obs_normalizer is not None or critic_obs_normalizer is not None, use_packed_mlp)
+            if why is not None:
+                raise ValueError(f"fused_encoder_policy: {why}")
         if not isinstance(env, LocoTouchVecEnv):
             raise TypeError("FusedRollout drives a LocoTouchVecEnv (HIP env)")
         ac = alg.actor_critic
@@ -106,7 +140,8 @@ class FusedRollout:
         # recurrent policy: the two memories run in one launch in front of the MLPs; `cell` is their kind (rl/memory_seq.py `LSTM` / `GRU`)
         self.recurrent = bool(getattr(ac, "is_recurrent", False))
         self.cell = None
-        if not self.recurrent and type(ac).__name__ == "ActorCriticEncoder":
+        self.encoders = None  # rl/encoder.py EncoderPair of an ActorCriticEncoder
+        if not self.recurrent and type(ac).__name__ == "ActorCriticEncoder" and not fused_encoder_policy:
             raise ValueError("FusedRollout does not serve ActorCriticEncoder: its encoders are not part of the fused step")
         if self.recurrent:
             why = recurrent_unsupported(ac, alg.storage, gru_memories=fused_gru_memories)
@@ -159,6 +194,27 @@ class FusedRollout:
 
         if self.recurrent:
             self._init_memory()
+        if fused_encoder_policy:
+            self._init_encoders()
+
+    def _init_encoders(self) -> None:
+        """The descriptors of the policy's encoders and the rows the stacks read: [head columns | embedding] per network."""
+        from .encoder import EncoderPair
+
+        st, n = self.alg.storage, self.env.num_envs
+        if self.actor_mlp is None:
+            raise ValueError("fused_encoder_policy: the env has no 12 actions: the policy launch samples 12")
+        self.encoders = EncoderPair(self.alg.actor_critic, st.observations.shape[-1], st.privileged_observations.shape[-1])
+        rows = n + (-n) % 64  # (the MLP launch reads whole row tiles)
+        self._enc_rows = (torch.zeros(rows, self.encoders.a_width, device=self.device),
+                          torch.zeros(rows, self.encoders.c_width, device=self.device) if self.encoders.c_desc is not None else None)
+
+    def _encoder_step(self, obs, cobs):
+        """One launch: the rows of this step's slot -> the rows the two stacks read."""
+        n = self.env.num_envs
+        out_a, out_c = self._enc_rows
+        self.encoders.forward(obs, cobs, out_a, out_c)
+        return out_a[:n], cobs if out_c is None else out_c[:n]
 
     def _init_memory(self) -> None:
         """Ping-pong buffers of the raw state of both memories - (h, c), or h alone: one tensor per state field of the cell - and the
@@ -325,8 +381,8 @@ class FusedRollout:
     def launches_per_step(self) -> int:
         """Kernel launches of one rollout step (the reference-shaped eager loop needs ~30)."""
         base = 2 if self.actor_mlp is not None else 11  # policy + value, env step (the population pass rides in the next step's launch)
-        if self.recurrent:
-            return base + 1  # both memories: one launch in front of the MLPs
+        if self.recurrent or self.encoders is not None:
+            return base + 1  # both memories, or the encoders: one launch in front of the MLPs
         if self.normalizers is None:
             return base
         return base + (2 if self.normalizers[0].training else 1)  # column statistics, merge + snapshot + normalise
@@ -336,6 +392,9 @@ class FusedRollout:
         obs, cobs, _, _ = self._rows(t, False)
         if self.normalizers is not None:
             obs, cobs = self.norm_rows
+        if self.encoders is not None:  # (the rows the last encoder launch left)
+            n = self.env.num_envs
+            obs, cobs = self._enc_rows[0][:n], cobs if self._enc_rows[1] is None else self._enc_rows[1][:n]
         self._policy_value(t, obs, cobs)
 
     def _sigma(self) -> torch.Tensor:
@@ -359,6 +418,8 @@ class FusedRollout:
         if self.recurrent:
             self._memory_step(t, obs, cobs)
             self._policy_value(t, *self._memory_rows(t))
+        elif self.encoders is not None:
+            self._policy_value(t, *self._encoder_step(obs, cobs))
         elif self.normalizers is None:
             self._policy_value(t, obs, cobs)
         else:

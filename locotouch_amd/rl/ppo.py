@@ -5,6 +5,8 @@ ActorCritic path the LocoTouch agents use (agents/rsl_rl_ppo_cfg.py:11-30: clip 
 adaptive, desired KL 0.01, entropy 0.01, value coef 1.0, grad-norm 1.0, 5 epochs x 4 minibatches), with the reference's `symmetry_cfg`
 branch (mirrored data augmentation and / or a mirror loss: `_symmetry_update`; with augmentation on the GPU inside `_direct_update`,
 include/lt_ppo_sym.h).  The RND branch is not built: a `rnd_cfg` is refused.
+An `ActorCriticEncoder` updates through the op chain, or - behind the opt-in key `fused_encoder_policy` - without an autograd graph
+(`_direct_encoder_update`, include/lt_encoder.h).
 
 Data parallelism (new): gradients live in one flat fp32 bucket that is all-reduced (mean) between
 `backward()` and the gradient clip, and the KL estimate is all-reduced before the learning-rate decision.
@@ -45,6 +47,21 @@ class PPO:
         # opt-in, on top of `fused_recurrent_update`: that update without an autograd graph and without a host read between its steps
         # (_direct_recurrent_update); what it cannot serve is refused here and below, never run on another path
         self.direct_recurrent_update = bool(unused.get("direct_recurrent_update", False))
+        # opt-in: an `ActorCriticEncoder` updates without an autograd graph and without a host read between its minibatch steps
+        # (_direct_encoder_update, csrc/lt_encoder.hip); what it cannot serve is refused here and below, never run on another path
+        self.fused_encoder_policy = bool(unused.get("fused_encoder_policy", False))
+        self._encoders = None  # rl/encoder.py EncoderPair, built at the first update (the storage names the rows' widths)
+        if self.fused_encoder_policy:
+            if self.fused_recurrent_update or self.direct_recurrent_update or self.fused_gru_memories:
+                raise ValueError("fused_encoder_policy: the recurrent keys (fused_recurrent_update, direct_recurrent_update, fused_gru_memories) "
+                                 "belong to ActorCriticRecurrent: an encoder policy has no memories")
+            if self.symmetry is not None:
+                raise ValueError("fused_encoder_policy: symmetry_cfg is not served for an encoder policy (the mirror tables cover the plain ActorCritic's rows)")
+            if self.dist.world_size > 1:
+                raise ValueError(f"fused_encoder_policy: dist.world_size is {self.dist.world_size}: the collectives of this form are not "
+                                 "covered by a multi-rank test, it runs on one rank only")
+            if not on_gpu:
+                raise ValueError(f"fused_encoder_policy: the device is {device!r}: its kernels run on a GPU only")
         if self.direct_recurrent_update:
             if not self.fused_recurrent_update:
                 raise ValueError("direct_recurrent_update: it is a form of the whole-rollout update: set fused_recurrent_update=True as well")
@@ -93,6 +110,10 @@ class PPO:
             why = self._direct_recurrent_unsupported()
             if why is not None:
                 raise ValueError(f"direct_recurrent_update: {why}")
+        if self.fused_encoder_policy:
+            why = self._direct_encoder_unsupported()
+            if why is not None:
+                raise ValueError(f"fused_encoder_policy: {why}")
 
     @staticmethod
     def _resolve_symmetry(symmetry_cfg, actor_critic):
@@ -500,11 +521,165 @@ class PPO:
             group["lr"] = self.learning_rate
 
     def update(self):
+        if self.fused_encoder_policy:
+            return self._direct_encoder_update()
         if self.direct_recurrent_update:
             return self._direct_recurrent_update()
         if self.fused_recurrent_update:
             return self._recurrent_update()
         return self._eager_update()
+
+    def _direct_encoder_unsupported(self) -> str | None:
+        """What `_direct_encoder_update` needs beyond a GPU and one rank (None: it is all there)."""
+        from . import encoder
+        from .fused_loss import std_param
+        from .mlp import PackedPair, describe
+
+        ac = self.actor_critic
+        if type(ac).__name__ != "ActorCriticEncoder":
+            return f"the policy is a {type(ac).__name__}, not an ActorCriticEncoder"
+        if self._flat_adam is None:
+            return "there is no FlatAdam (fused_adam=False): the gradients are written in place into its flat bucket"
+        if not self.packed_forward:
+            return "packed_forward is off: the two MLPs run through rl/mlp.py PackedPair"
+        for name, seq in (("actor", ac.actor), ("critic", ac.critic)):
+            if describe(seq) is None:
+                return f"the MLP kernel does not serve the {name} stack (rl/mlp.py describe: Linear/activation stack, hidden widths <= 512)"
+        try:
+            self._pair = PackedPair(ac.actor, ac.critic)
+        except ValueError as e:
+            return str(e)
+        if self._pair.a.out_features > 16:
+            return f"the action width is {self._pair.a.out_features}: the loss kernel serves at most 16"
+        std_p, _ = std_param(ac)
+        if not std_p.requires_grad:
+            return "std has no gradient: the learning-rate launch writes d loss / d std into its slot of the bucket"
+        written = {id(std_p)} | {id(p) for seq in (ac.actor, ac.critic) for p in seq.parameters()}
+        encoders = [("actor_encoder", ac.actor_encoder, ac.actor_flatten_obs_dim)]
+        if ac.critic_with_encoder:
+            encoders.append(("critic_encoder", ac.critic_encoder, ac.critic_flatten_obs_dim))
+        for name, enc, flat in encoders:
+            try:  # (the rows' width is the storage's to say: here the narrowest row that holds both parts)
+                desc, linears = encoder.describe(enc, flat + enc.model[0].in_features, flat)
+            except ValueError as e:
+                return f"{name}: {e}"
+            if len(linears) > 1 and desc.activation != _abi.CONSTS["LT_ACT_ELU"]:
+                return f"{name}: the backward chain of its hidden layers serves ELU (rl/mlp.py backward_chain)"
+            written |= {id(p) for p in enc.parameters()}
+        for name, p in ac.named_parameters():
+            if p.requires_grad and id(p) not in written:
+                return f"the parameter {name} has a gradient this form does not write"
+        return None
+
+    @staticmethod
+    def _final_activation_grad(g: torch.Tensor, pre: torch.Tensor, emb: torch.Tensor, kind: int) -> torch.Tensor:
+        """g * f'(pre) for the encoder's final activation f (emb = f(pre)): the gradient w.r.t. the pre-activation embedding."""
+        C = _abi.CONSTS
+        if kind == C["LT_ACT_TANH"]:
+            return g * (1.0 - emb * emb)
+        if kind == C["LT_ACT_ELU"]:
+            return g * torch.where(pre > 0, torch.ones_like(pre), torch.exp(pre))
+        return g * (pre > 0).to(g.dtype)  # LT_ACT_RELU
+
+    def _direct_encoder_update(self):
+        """The update of an `ActorCriticEncoder` on the GPU with NO autograd graph and NO host read between its minibatch steps, as
+        `_direct_update` is for the plain class.  Once per update: the permutation, the two observation matrices gathered through it,
+        the encoders' input columns of those rows laid out contiguously (what their first layers' weight gradients multiply).  Per step:
+        `lt_encoder_forward` in the training form on the minibatch's rows (include/lt_encoder.h: the rows the stacks read, the
+        encoders' hidden activations, the pre-activation embedding), the packed forward of both stacks on those rows, ONE loss launch,
+        the learning-rate rule on the device scalar, both stacks' backward chains with the gradient w.r.t. their input rows
+        (`PackedPair.backward_raw(dx_out=...)`), the final activation's derivative on dx[:, flat_dim:], `backward_chain` of each
+        encoder from that gradient - every gradient written in place into the flat bucket, so the clip norm covers the encoders as
+        `clip_grad_norm_(actor_critic.parameters())` does - and clip + Adam from the device learning rate.  One host read at the end."""
+        from .encoder import EncoderPair
+        from .fused_loss import adv_stats, std_param
+        from .mlp import SumJobs, backward_chain
+
+        ac, st, fa, pair = self.actor_critic, self.storage, self._flat_adam, self._pair
+        if st.observations.dtype != torch.float32:
+            raise ValueError("fused_encoder_policy: bf16 observation rows: the encoder launch reads f32 rows")
+        obs, cobs, small = self._flat_storage()
+        small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
+        a_dim = small[0].shape[1]
+        if a_dim > 16:
+            raise ValueError(f"fused_encoder_policy: the action width is {a_dim}: the loss kernel serves at most 16")
+        if self._encoders is None:
+            try:
+                self._encoders = EncoderPair(ac, obs.shape[1], cobs.shape[1])
+            except ValueError as e:
+                raise ValueError(f"fused_encoder_policy: {e}") from None
+        enc = self._encoders
+        dev = obs.device
+        none = _abi.CONSTS["LT_ACT_NONE"]
+        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
+        state = torch.zeros(4, device=dev)  # [0] learning rate, [1..3] sums of (value loss, surrogate, entropy)
+        state[0] = self.learning_rate
+        lr_dev, stats = state[:1], state[1:]
+        grad_of = fa.grad_views()
+        std_p, std_is_log = std_param(ac)
+        std_c = std_p.detach()
+        pair.arm_domain_check()
+        stream = _abi.stream(dev)
+        nmb = self.num_mini_batches
+        perm, m = st.mini_batch_permutation(nmb)
+        mb_stats = adv_stats(small[2], perm, m, nmb) if self.normalize_advantage_per_mini_batch else None
+        perm_o, perm_co = obs[perm], cobs[perm]
+        nets = [(enc.a_desc, enc.a_linears, perm_o)]  # the networks with an encoder
+        if enc.c_desc is not None:
+            nets.append((enc.c_desc, enc.c_linears, perm_co))
+        tails = [rows[:, d.obs_dim - d.enc_in:].contiguous() for d, _, rows in nets]
+        n_steps = self.num_learning_epochs * nmb
+        for step_i in range(n_steps):
+            i = step_i % nmb
+            idx = perm[i * m:(i + 1) * m]
+            o, co = perm_o[i * m:(i + 1) * m], perm_co[i * m:(i + 1) * m]
+            x_a = torch.empty(m, enc.a_width, device=dev, dtype=torch.float32)
+            x_c = torch.empty(m, enc.c_width, device=dev, dtype=torch.float32) if enc.c_desc is not None else co
+            enc_acts = enc.forward(o, co, x_a, x_c if enc.c_desc is not None else None, train=True)
+            (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
+            dmu = torch.empty_like(mu)
+            dvalue = torch.empty(m, 1, device=dev, dtype=torch.float32)
+            acc = torch.empty(24, device=dev, dtype=torch.float32)
+            out = torch.empty(24, device=dev, dtype=torch.float32)
+            if std_is_log or mb_stats is not None:
+                _abi.call("lt_ppo_loss_opts", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
+                          None if mb_stats is None else mb_stats[i], dmu, dvalue, acc, out, stream)
+            else:
+                _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
+                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
+            _abi.call("lt_ppo_lr_rule", out[4:5] if adaptive else None, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out,
+                      grad_of[std_p], a_dim, stream)
+            dx = (torch.empty_like(x_a), torch.empty_like(x_c))
+            pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
+            sums = SumJobs()
+            for k, (d, linears, _) in enumerate(nets):
+                L, flat = d.num_layers, d.flat_dim
+                g = dx[k][:, flat:].contiguous()
+                if d.final_activation != none:
+                    g = self._final_activation_grad(g, enc_acts[k][L - 1], (x_a, x_c)[k][:, flat:], d.final_activation)
+                backward_chain([lin.weight for lin in linears], [grad_of[lin.bias] for lin in linears], [grad_of[lin.weight] for lin in linears],
+                               tails[k][i * m:(i + 1) * m], enc_acts[k][:L - 1], g, sums)
+            sums.launch()
+            fa.step_dev(self.max_grad_norm, lr_dev)
+        sat, dom = pair.saturated(), pair.domain_max
+        pair.domain_max = None
+        zero = state.new_zeros(1)
+        lr, sv, ss, se, nsat, dmax = torch.cat((state, zero if sat is None else sat, zero if dom is None else dom.view(1))).tolist()  # the update's only host read
+        if nsat > 0:
+            import warnings
+
+            sat.zero_()
+            warnings.warn(f"lt_mlp_backward_pair: {int(nsat)} workgroup-layers of the gradient chain reached the f16 image's bound "
+                          "(a gradient grew by more than 500x through the layers): those rows were saturated; set LT_FUSED_BACKWARD=0 "
+                          "to run the chain as f32 library GEMMs")
+        self.learning_rate = lr
+        for group in self.optimizer.param_groups:
+            group["lr"] = lr
+        if dmax >= float(_abi.CONSTS["LT_MLP_INPUT_CLAMP"]):
+            self._warn_mlp_domain()
+        st.clear()
+        return sv / n_steps, ss / n_steps, se / n_steps, None, None
 
     def _direct_recurrent_unsupported(self) -> str | None:
         """What `_direct_recurrent_update` needs beyond `_recurrent_update_unsupported`, a GPU and one rank (None: it is all there)."""

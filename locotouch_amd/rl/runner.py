@@ -17,7 +17,7 @@ from collections import deque
 import torch
 
 from .dist import Dist
-from .modules import ActorCritic, ActorCriticRecurrent
+from .modules import ActorCritic, ActorCriticEncoder, ActorCriticRecurrent
 from .normalizer import EmpiricalNormalization
 from .ppo import PPO
 
@@ -44,6 +44,8 @@ class OnPolicyRunner:
             self.alg_cfg["fused_gru_memories"] = bool(self.cfg["fused_gru_memories"])
         if "direct_recurrent_update" in self.cfg:  # opt-in on top of `fused_recurrent_update` (rl/ppo.py `_direct_recurrent_update`)
             self.alg_cfg["direct_recurrent_update"] = bool(self.cfg["direct_recurrent_update"])
+        if "fused_encoder_policy" in self.cfg:  # opt-in: an ActorCriticEncoder on the fused rollout and `_direct_encoder_update`
+            self.alg_cfg["fused_encoder_policy"] = bool(self.cfg["fused_encoder_policy"])
         sym = self.alg_cfg.get("symmetry_cfg")
         if sym is not None:  # on_policy_runner.py:60-63: the augmentation function is handed the env; PPO takes a plain dict
             sym = sym.to_dict() if hasattr(sym, "to_dict") else (dict(sym) if isinstance(sym, dict) else dict(vars(sym)))
@@ -174,7 +176,8 @@ class OnPolicyRunner:
     def _make_fused(self):
         """FusedRollout when the env is the HIP env on a GPU and the policy is the plain feed-forward ActorCritic (either noise_std_type), or - behind the cfg
         key `fused_recurrent_rollout` (default False: the fused path draws its exploration noise from the kernels' Philox stream, which
-        would change existing runs) - an ActorCriticRecurrent whose memories csrc/lt_memory.hip serves."""
+        would change existing runs) - an ActorCriticRecurrent whose memories csrc/lt_memory.hip serves, or - behind `fused_encoder_policy`, for
+        the same reason - an ActorCriticEncoder whose encoders csrc/lt_encoder.hip serves."""
         try:
             from ..env import LocoTouchVecEnv
             from .fused import FusedRollout
@@ -196,8 +199,15 @@ class OnPolicyRunner:
                     or recurrent_unsupported(ac, self.alg.storage, gru_memories=gru) is not None):
                 return None
             return FusedRollout(target, self.alg, fused_gru_memories=gru)
+        if type(ac) is ActorCriticEncoder:
+            from .fused import encoder_policy_unsupported
+
+            # without the key, or for what FusedRollout would refuse (a normaliser, bf16 rows, shapes outside the kernels' limits): the eager loop
+            if not self.cfg.get("fused_encoder_policy", False) or encoder_policy_unsupported(self.alg, self.empirical_normalization) is not None:
+                return None
+            return FusedRollout(target, self.alg, fused_encoder_policy=True)
         if type(ac) is not ActorCritic:
-            return None  # the fused rollout packs the actor / critic MLPs (ActorCriticEncoder keeps the eager loop)
+            return None  # the fused rollout packs the actor / critic MLPs
         if not self.empirical_normalization:
             return FusedRollout(target, self.alg)
         # The device normaliser (csrc/lt_obs_norm.hip) reads and writes f32 rows, and it keeps per-process statistics: ranks cannot
