@@ -7,6 +7,9 @@ branch (mirrored data augmentation and / or a mirror loss: `_symmetry_update`; w
 include/lt_ppo_sym.h).  The RND branch is not built: a `rnd_cfg` is refused.
 An `ActorCriticEncoder` updates through the op chain, or - behind the opt-in key `fused_encoder_policy` - without an autograd graph
 (`_direct_encoder_update`, include/lt_encoder.h).
+The three updates without an autograd graph (`_direct_update`, `_direct_encoder_update`, `_direct_recurrent_update`) share one skeleton -
+`_direct_begin`, `_direct_loss_and_rule` per step, `_direct_end` with the update's one host read - and keep only their own forward and
+backward passes; the updates that run the loss as torch ops share `_op_chain_loss`.
 
 Data parallelism (new): gradients live in one flat fp32 bucket that is all-reduced (mean) between
 `backward()` and the gradient clip, and the KL estimate is all-reduced before the learning-rate decision.
@@ -242,7 +245,6 @@ class PPO:
         ac, st = self.actor_critic, self.storage
         obs, cobs, small = self._flat_storage()
         stats = torch.zeros(3, device=obs.device)
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         pair = self._packed_pair()
         std_p, std_is_log = std_param(ac)
         if pair is not None and self._flat_adam is not None and self.direct_update and std_p.requires_grad:
@@ -265,10 +267,10 @@ class PPO:
             # the 1-float KL all-reduce starts here and its host read waits until the backward pass is enqueued: the collective's
             # latency (and the host round trip of the learning-rate rule, ppo.py:273-281) hides under the backward GEMMs; the
             # decision still precedes this step's optimizer update, as in the reference
-            kl_handle = self.dist.all_reduce_mean_begin(kl_mean.detach().clone()) if adaptive else None
+            kl_handle = self.dist.all_reduce_mean_begin(kl_mean.detach().clone()) if self._adaptive else None
             self._zero_grad()
             loss.backward()
-            if adaptive:
+            if self._adaptive:
                 self._apply_kl(self.dist.all_reduce_mean_end(kl_handle), reduced=True)
             self._optim_step()
             stats = stats + torch.stack((value_loss, surrogate_loss, ent.detach()))
@@ -280,41 +282,31 @@ class PPO:
         return sv, ss, se, None, None
 
     def _direct_update(self, pair, split_buckets: bool = True):
-        """The update of the plain ActorCritic on the GPU with NO host read between its minibatch steps and no autograd graph: per step
-        two row gathers, the packed forward (rl/mlp.py), ONE loss launch that also writes d loss / d (mu, value, std) (csrc/lt_ppo.hip),
-        the adaptive-KL learning-rate rule as a one-lane launch on a device scalar (`lt_ppo_lr_rule`, ppo.py:273-281), the two
-        stacks' backward chains writing their gradients straight into the flat bucket (rl/mlp.py `backward_chain`), [gradient
-        all-reduce], clip + Adam with the learning rate read from the device (`lt_adam_clip_step_dev`).  Statistics and the learning
-        rate come back in ONE read at the end.  Arithmetic equal to `_fused_update` (tests/test_hip_ppo_graph.py); the host used to
-        wait for the KL of every step - 20 stalls per iteration, ~350 us of idle GPU each.
+        """The update of the plain ActorCritic on the GPU with NO host read between its minibatch steps and no autograd graph.  The
+        skeleton it shares with `_direct_encoder_update` and `_direct_recurrent_update`: `_direct_begin` (device state, std, bucket
+        views, [`lt_adv_stats`]); per step a forward, `_direct_loss_and_rule` - ONE loss launch that also writes d loss / d (mu, value,
+        std) (csrc/lt_ppo.hip) and the adaptive-KL learning-rate rule as a one-lane launch on a device scalar (`lt_ppo_lr_rule`,
+        ppo.py:273-281) -, the two stacks' backward chains writing their gradients straight into the flat bucket (rl/mlp.py
+        `backward_raw`), clip + Adam with the learning rate read from the device (`lt_adam_clip_step_dev`); `_direct_end`: statistics,
+        learning rate, saturation count and domain record come back in ONE read.  Arithmetic equal to `_fused_update`
+        (tests/test_hip_ppo_graph.py); the host used to wait for the KL of every step - 20 stalls per iteration, ~350 us of idle GPU each.
 
-        Log-type std and per-minibatch advantage normalisation as in `_fused_update`: `log_std` and its slot of the bucket stand where
-        `std` and its slot do, the statistics come from one `lt_adv_stats` launch per update and stay per rank in a multi-rank job."""
-        from .fused_loss import adv_stats, std_param
-
-        ac, st, fa = self.actor_critic, self.storage, self._flat_adam
-        obs, cobs, small = self._flat_storage()
-        small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
-        dev = obs.device
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        a_dim = small[0].shape[1]
-        sym = self.symmetry
-        state = torch.zeros(4 if sym is None else 5, device=dev)  # [0] learning rate, [1..3] sums of (value loss, surrogate, entropy), [4] of the symmetry loss
-        state[0] = self.learning_rate
-        lr_dev, stats = state[:1], state[1:4]
-        grad_of = fa.grad_views()
-        std_p, std_is_log = std_param(ac)
-        std_c = std_p.detach()
-        pair.arm_domain_check()
-        n_steps = 0
+        This form's own: the rows of both networks gathered through the permutation once per update (with `symmetry_cfg` by
+        `lt_sym_gather_rows`, [original; mirrored]), the same rows in the split format, the packed forward on them, and the gradient
+        all-reduce of a multi-rank job around the backward pass.  Log-type std and per-minibatch advantage normalisation as in
+        `_fused_update`: `log_std` and its slot of the bucket stand where `std` and its slot do, the statistics come from one
+        `lt_adv_stats` launch per update and stay per rank in a multi-rank job."""
+        ac, fa, sym = self.actor_critic, self._flat_adam, self.symmetry
         # The reference draws ONE permutation per update and reuses it in every epoch (rollout_storage.py:189): the two observation
         # matrices are gathered through it once - minibatch i of every epoch is rows [i mb, (i + 1) mb) of the permuted copies -
         # instead of 2 x 16 us of row gathers in each of the 20 steps.  (The small per-row tensors are read through the index
         # by the loss kernel itself.)
+        perm, m = self.storage.mini_batch_permutation(self.num_mini_batches)
+        c = self._direct_begin("direct_update", pair, perm, m, symmetric=sym is not None)
+        obs, cobs, dev, grad_of = c.obs, c.cobs, c.dev, c.grad_of
         critic_at = fa.offset_of(next(iter(ac.critic.parameters())))
         two_buckets = split_buckets and 0 < critic_at < self._flat_grad.numel()
-        perm, m = st.mini_batch_permutation(self.num_mini_batches)
-        mb_stats = adv_stats(small[2], perm, m, self.num_mini_batches) if self.normalize_advantage_per_mini_batch else None
+        sym_args = None
         if sym is None:
             rows = m
             perm_o, perm_co = obs[perm], cobs[perm]
@@ -324,9 +316,9 @@ class PPO:
             # the mirror-augmented update (include/lt_ppo_sym.h): ONE gather per network writes every minibatch as 2 m contiguous f32 rows
             # [original; mirrored]; the statistics above are those of the original rows (ppo.py:223-225 runs before the repeat)
             rows = 2 * m
-            tab_o, tab_co, tab_a = self._symmetry_tables(dev, obs.shape[1], cobs.shape[1], a_dim)
+            tab_o, tab_co, tab_a = self._symmetry_tables(dev, obs.shape[1], cobs.shape[1], c.a_dim)
             perm_o, perm_co = (self._symmetry_gather(x, perm, m, t) for x, t in ((obs, tab_o), (cobs, tab_co)))
-            mirror_coeff = float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0
+            sym_args = (tab_a, float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0)
         # the same rows in the MLP kernels' split format (f16 hi | f16 lo): what the first layer's weight gradient multiplies, 20 times
         split_o = (pair.split_rows(perm_o), pair.split_rows(perm_co)) if pair._fused_backward_possible(perm_o[:rows], perm_co[:rows]) else None
         for step_i in range(self.num_learning_epochs * self.num_mini_batches):
@@ -335,28 +327,7 @@ class PPO:
             o, co = perm_o[i * rows:(i + 1) * rows], perm_co[i * rows:(i + 1) * rows]
             xs = (split_o[0][i * rows:(i + 1) * rows], split_o[1][i * rows:(i + 1) * rows]) if split_o is not None else None
             (mu, value), acts = pair.forward_raw(o, co)
-            dmu = torch.empty_like(mu)
-            dvalue = torch.empty(rows, 1, device=dev, dtype=torch.float32)
-            acc = torch.empty(24, device=dev, dtype=torch.float32)
-            out = torch.empty(24, device=dev, dtype=torch.float32)
-            stream = _abi.stream(dev)
-            if sym is not None:
-                _abi.call("lt_ppo_loss_sym", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
-                          None if mb_stats is None else mb_stats[i], tab_a, mirror_coeff, dmu, dvalue, acc, out, state[4:5], stream)
-            elif std_is_log or mb_stats is not None:
-                _abi.call("lt_ppo_loss_opts", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
-                          None if mb_stats is None else mb_stats[i], dmu, dvalue, acc, out, stream)
-            else:
-                _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
-            kl = None
-            if adaptive:
-                kl = out[4:5]
-                if self.dist.world_size > 1:  # every rank must take the same decision; the collective is stream-ordered
-                    kl = self.dist.all_reduce_mean_(kl.clone())
-            _abi.call("lt_ppo_lr_rule", kl, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out, grad_of[std_p], a_dim, stream)
+            dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx, m, i, sym_args)
             if self.dist.world_size > 1 and two_buckets:
                 # the bucket in two halves (std + actor | critic): the actor's all-reduce runs on RCCL's stream under the critic's
                 # three weight-gradient launches (~105 us at 24 576 rows), only the critic's half stays exposed
@@ -371,25 +342,90 @@ class PPO:
                 pair.backward_raw(o, co, acts, dmu, dvalue, grad_of, xs, dy_amax=(acc[20:21], acc[21:22]))
                 if self.dist.world_size > 1:
                     self.dist.all_reduce_mean_(self._flat_grad)  # RCCL all-reduce of the policy gradients over xGMI
-            fa.step_dev(self.max_grad_norm, lr_dev)
-            n_steps += 1
-        sat = pair.saturated()
-        read = torch.cat((state, sat if sat is not None else state[:0].new_zeros(1))).tolist()  # the update's only host read
-        (lr, sv, ss, se), nsat = read[:4], read[-1]
+            fa.step_dev(self.max_grad_norm, c.lr_dev)
+        return self._direct_end(c, with_dx=False)
+
+    def _direct_begin(self, key: str, pair, index, m: int, symmetric: bool = False):
+        """What the three graph-free updates set up alike, as one namespace: the storage's rows (`obs`, `cobs`, `small` with its
+        one-column tensors as vectors), `a_dim`, the device `state` ([0] learning rate, [1..3] sums of (value loss, surrogate, entropy),
+        with `symmetric` [4] of the symmetry loss) and its views `lr_dev` and `stats`, the bucket's `grad_of`, the std parameter
+        (`std_p`, `std_is_log`, `std_c`), the `stream`, the armed domain check of `pair`, and `mb_stats`: `lt_adv_stats` of the
+        minibatches that are consecutive runs of `m` entries of `index` (None without per-minibatch normalisation).  `key` names the
+        form in a refusal."""
+        from types import SimpleNamespace
+
+        from .fused_loss import adv_stats, std_param
+
+        obs, cobs, small = self._flat_storage()
+        small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
+        a_dim = small[0].shape[1]
+        if a_dim > 16:
+            raise ValueError(f"{key}: the action width is {a_dim}: the loss kernel serves at most 16")
+        dev = obs.device
+        state = torch.zeros(5 if symmetric else 4, device=dev)
+        state[0] = self.learning_rate
+        std_p, std_is_log = std_param(self.actor_critic)
+        pair.arm_domain_check()
+        mb_stats = adv_stats(small[2], index, m, self.num_mini_batches) if self.normalize_advantage_per_mini_batch else None
+        return SimpleNamespace(pair=pair, obs=obs, cobs=cobs, small=small, a_dim=a_dim, dev=dev, state=state, lr_dev=state[:1], stats=state[1:4],
+                               grad_of=self._flat_adam.grad_views(), std_p=std_p, std_is_log=std_is_log, std_c=std_p.detach(),
+                               stream=_abi.stream(dev), mb_stats=mb_stats)
+
+    def _direct_loss_and_rule(self, c, mu, value, idx, m: int, i: int, sym_args=None):
+        """One step's loss launch and learning-rate launch, for every graph-free update: -> (dmu, dvalue, acc).  The loss entry reads the
+        small per-row tensors through `idx` (m rows; minibatch `i` of the update) and writes d loss / d (mu, value), its sums and the
+        gradient maxima acc[20], acc[21]: `lt_ppo_loss_sym` with `sym_args` = (action table, mirror coefficient) on [original; mirrored]
+        rows, `lt_ppo_loss_opts` for a log-type std or per-minibatch statistics, else `lt_ppo_loss`.  `lt_ppo_lr_rule` then applies the
+        adaptive-KL rule (ppo.py:273-281) to the device learning rate, adds the step's statistics to `c.stats` and writes d loss / d std
+        into its slot of the bucket."""
+        dev = c.dev
+        dmu = torch.empty_like(mu)
+        dvalue = torch.empty(mu.shape[0], 1, device=dev, dtype=torch.float32)
+        acc = torch.empty(24, device=dev, dtype=torch.float32)
+        out = torch.empty(24, device=dev, dtype=torch.float32)
+        rows = (mu, c.std_c, value, *c.small, idx, m, c.a_dim, float(self.clip_param), float(self.value_loss_coef), float(self.entropy_coef),
+                int(bool(self.use_clipped_value_loss)))
+        opts = (int(c.std_is_log), None if c.mb_stats is None else c.mb_stats[i])
+        if sym_args is not None:
+            _abi.call("lt_ppo_loss_sym", *rows, *opts, *sym_args, dmu, dvalue, acc, out, c.state[4:5], c.stream)
+        elif c.std_is_log or c.mb_stats is not None:
+            _abi.call("lt_ppo_loss_opts", *rows, *opts, dmu, dvalue, acc, out, c.stream)
+        else:
+            _abi.call("lt_ppo_loss", *rows, dmu, dvalue, acc, out, c.stream)
+        kl = None
+        if self._adaptive:
+            kl = out[4:5]
+            if self.dist.world_size > 1:  # every rank must take the same decision (SURVEY.md 8(e).2); the collective is stream-ordered
+                kl = self.dist.all_reduce_mean_(kl.clone())
+        _abi.call("lt_ppo_lr_rule", kl, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, c.lr_dev, c.stats, out, c.grad_of[c.std_p], c.a_dim, c.stream)
+        return dmu, dvalue, acc
+
+    def _direct_end(self, c, with_dx: bool):
+        """The end of every graph-free update: ONE host read (the device state, the backward chain's saturation count, the domain record),
+        the learning rate written back, the two warnings, the storage cleared -> the update's 5-tuple.  `with_dx`: the backward passes
+        were given `dx_out`."""
+        pair, state = c.pair, c.state
+        sat, dom = pair.saturated(), pair.domain_max
+        pair.domain_max = None
+        zero = state.new_zeros(1)
+        read = torch.cat((state, zero if sat is None else sat, zero if dom is None else dom.view(1))).tolist()  # the update's only host read
+        (lr, sv, ss, se), (nsat, dmax) = read[:4], read[-2:]
         if nsat > 0:
             import warnings
 
             sat.zero_()
-            warnings.warn(f"lt_mlp_backward_pair: {int(nsat)} workgroup-layers of the gradient chain reached the f16 image's bound "
+            entry = "lt_mlp_backward_pair_dx" if with_dx and pair._dx_kernel_ok() else "lt_mlp_backward_pair"
+            warnings.warn(f"{entry}: {int(nsat)} workgroup-layers of the gradient chain reached the f16 image's bound "
                           "(a gradient grew by more than 500x through the layers): those rows were saturated; set LT_FUSED_BACKWARD=0 "
                           "to run the chain as f32 library GEMMs")
         self.learning_rate = lr
         for group in self.optimizer.param_groups:
             group["lr"] = lr
-        if pair.domain_violated():
+        if dmax >= float(_abi.CONSTS["LT_MLP_INPUT_CLAMP"]):
             self._warn_mlp_domain()
-        st.clear()
-        return sv / n_steps, ss / n_steps, se / n_steps, None, None if sym is None else read[4] / n_steps
+        self.storage.clear()
+        n = self.num_learning_epochs * self.num_mini_batches
+        return sv / n, ss / n, se / n, None, read[4] / n if state.numel() == 5 else None
 
     def _symmetry_tables(self, dev, obs_dim: int, critic_obs_dim: int, a_dim: int):
         """The packed device tables (policy rows, critic rows, actions) of the env's mirror map, checked on the host by
@@ -464,17 +500,9 @@ class PPO:
             log_prob = ac.get_actions_log_prob(actions)
             value = ac.evaluate(critic_obs)
             mu, sigma, entropy = ac.action_mean[:B], ac.action_std[:B], ac.entropy[:B]
-            if self.desired_kl is not None and self.schedule == "adaptive":
+            if self._adaptive:
                 self._adapt_learning_rate(mu, sigma, b.mu, b.sigma)
-            ratio = torch.exp(log_prob - torch.squeeze(old_log_prob))
-            a = torch.squeeze(adv)
-            surrogate_loss = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
-            if self.use_clipped_value_loss:
-                clipped = target_values + (value - target_values).clamp(-self.clip_param, self.clip_param)
-                value_loss = torch.max((value - returns).pow(2), (clipped - returns).pow(2)).mean()
-            else:
-                value_loss = (returns - value).pow(2).mean()
-            loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+            loss, surrogate_loss, value_loss = self._op_chain_loss(log_prob, value, old_log_prob, adv, returns, target_values, entropy.mean())
             if not sym["use_data_augmentation"]:
                 obs, _ = func(obs=obs, actions=None, env=env, is_critic=False)
                 num_aug = int(obs.shape[0] / B)
@@ -501,6 +529,22 @@ class PPO:
         warnings.warn("an observation or hidden activation reached the MLP kernel's saturation bound (|x| >= LT_MLP_INPUT_CLAMP, "
                       "include/lt_env.h): the fused forward computes MLP(clamp(x)) there, unlike the fp32 reference; "
                       "construct PPO(..., packed_forward=False) and FusedRollout(..., use_packed_mlp=False) to run the fp32 GEMM path")
+
+    @property
+    def _adaptive(self) -> bool:
+        return self.desired_kl is not None and self.schedule == "adaptive"
+
+    def _op_chain_loss(self, log_prob, value, old_log_prob, adv, returns, old_values, entropy_mean):
+        """(loss, surrogate loss, value loss) of the reference as torch ops (ppo.py:284-302), for every update that runs the op chain."""
+        ratio = torch.exp(log_prob - torch.squeeze(old_log_prob))
+        a = torch.squeeze(adv)
+        surrogate_loss = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
+        if self.use_clipped_value_loss:
+            clipped = old_values + (value - old_values).clamp(-self.clip_param, self.clip_param)
+            value_loss = torch.max((value - returns).pow(2), (clipped - returns).pow(2)).mean()
+        else:
+            value_loss = (returns - value).pow(2).mean()
+        return surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy_mean, surrogate_loss, value_loss
 
     def _adapt_learning_rate(self, mu, sigma, old_mu, old_sigma) -> None:
         with torch.inference_mode():
@@ -529,32 +573,47 @@ class PPO:
             return self._recurrent_update()
         return self._eager_update()
 
-    def _direct_encoder_unsupported(self) -> str | None:
-        """What `_direct_encoder_update` needs beyond a GPU and one rank (None: it is all there)."""
-        from . import encoder
+    def _direct_stacks_unsupported(self):
+        """What the encoder and recurrent graph-free updates need of the optimizer, the two stacks and std -> (why, None), or, with all of
+        it there, (None, the ids of the parameters whose gradients the shared steps write); builds `self._pair`."""
         from .fused_loss import std_param
         from .mlp import PackedPair, describe
 
         ac = self.actor_critic
-        if type(ac).__name__ != "ActorCriticEncoder":
-            return f"the policy is a {type(ac).__name__}, not an ActorCriticEncoder"
         if self._flat_adam is None:
-            return "there is no FlatAdam (fused_adam=False): the gradients are written in place into its flat bucket"
+            return "there is no FlatAdam (fused_adam=False): the gradients are written in place into its flat bucket", None
         if not self.packed_forward:
-            return "packed_forward is off: the two MLPs run through rl/mlp.py PackedPair"
+            return "packed_forward is off: the two MLPs run through rl/mlp.py PackedPair", None
         for name, seq in (("actor", ac.actor), ("critic", ac.critic)):
             if describe(seq) is None:
-                return f"the MLP kernel does not serve the {name} stack (rl/mlp.py describe: Linear/activation stack, hidden widths <= 512)"
+                return f"the MLP kernel does not serve the {name} stack (rl/mlp.py describe: Linear/activation stack, hidden widths <= 512)", None
         try:
             self._pair = PackedPair(ac.actor, ac.critic)
         except ValueError as e:
-            return str(e)
+            return str(e), None
         if self._pair.a.out_features > 16:
-            return f"the action width is {self._pair.a.out_features}: the loss kernel serves at most 16"
+            return f"the action width is {self._pair.a.out_features}: the loss kernel serves at most 16", None
         std_p, _ = std_param(ac)
         if not std_p.requires_grad:
-            return "std has no gradient: the learning-rate launch writes d loss / d std into its slot of the bucket"
-        written = {id(std_p)} | {id(p) for seq in (ac.actor, ac.critic) for p in seq.parameters()}
+            return "std has no gradient: the learning-rate launch writes d loss / d std into its slot of the bucket", None
+        return None, {id(std_p)} | {id(p) for seq in (ac.actor, ac.critic) for p in seq.parameters()}
+
+    def _unwritten_gradient(self, written) -> str | None:
+        for name, p in self.actor_critic.named_parameters():
+            if p.requires_grad and id(p) not in written:
+                return f"the parameter {name} has a gradient this form does not write"
+        return None
+
+    def _direct_encoder_unsupported(self) -> str | None:
+        """What `_direct_encoder_update` needs beyond a GPU and one rank (None: it is all there)."""
+        from . import encoder
+
+        ac = self.actor_critic
+        if type(ac).__name__ != "ActorCriticEncoder":
+            return f"the policy is a {type(ac).__name__}, not an ActorCriticEncoder"
+        why, written = self._direct_stacks_unsupported()
+        if why is not None:
+            return why
         encoders = [("actor_encoder", ac.actor_encoder, ac.actor_flatten_obs_dim)]
         if ac.critic_with_encoder:
             encoders.append(("critic_encoder", ac.critic_encoder, ac.critic_flatten_obs_dim))
@@ -566,10 +625,7 @@ class PPO:
             if len(linears) > 1 and desc.activation != _abi.CONSTS["LT_ACT_ELU"]:
                 return f"{name}: the backward chain of its hidden layers serves ELU (rl/mlp.py backward_chain)"
             written |= {id(p) for p in enc.parameters()}
-        for name, p in ac.named_parameters():
-            if p.requires_grad and id(p) not in written:
-                return f"the parameter {name} has a gradient this form does not write"
-        return None
+        return self._unwritten_gradient(written)
 
     @staticmethod
     def _final_activation_grad(g: torch.Tensor, pre: torch.Tensor, emb: torch.Tensor, kind: int) -> torch.Tensor:
@@ -583,53 +639,36 @@ class PPO:
 
     def _direct_encoder_update(self):
         """The update of an `ActorCriticEncoder` on the GPU with NO autograd graph and NO host read between its minibatch steps, as
-        `_direct_update` is for the plain class.  Once per update: the permutation, the two observation matrices gathered through it,
-        the encoders' input columns of those rows laid out contiguously (what their first layers' weight gradients multiply).  Per step:
-        `lt_encoder_forward` in the training form on the minibatch's rows (include/lt_encoder.h: the rows the stacks read, the
-        encoders' hidden activations, the pre-activation embedding), the packed forward of both stacks on those rows, ONE loss launch,
-        the learning-rate rule on the device scalar, both stacks' backward chains with the gradient w.r.t. their input rows
-        (`PackedPair.backward_raw(dx_out=...)`), the final activation's derivative on dx[:, flat_dim:], `backward_chain` of each
-        encoder from that gradient - every gradient written in place into the flat bucket, so the clip norm covers the encoders as
-        `clip_grad_norm_(actor_critic.parameters())` does - and clip + Adam from the device learning rate.  One host read at the end."""
+        `_direct_update` is for the plain class and on its skeleton.  What the encoders add.  Once per update: their input columns of
+        the permuted rows laid out contiguously (what their first layers' weight gradients multiply).  Per step: `lt_encoder_forward` in
+        the training form on the minibatch's rows (include/lt_encoder.h: the rows the stacks read, the encoders' hidden activations,
+        the pre-activation embedding) in front of the packed forward; behind the loss, both stacks' backward chains with the gradient
+        w.r.t. their input rows (`PackedPair.backward_raw(dx_out=...)`), the final activation's derivative on dx[:, flat_dim:] and
+        `backward_chain` of each encoder from that gradient - every gradient written in place into the flat bucket, so the clip norm
+        covers the encoders as `clip_grad_norm_(actor_critic.parameters())` does."""
         from .encoder import EncoderPair
-        from .fused_loss import adv_stats, std_param
         from .mlp import SumJobs, backward_chain
 
         ac, st, fa, pair = self.actor_critic, self.storage, self._flat_adam, self._pair
         if st.observations.dtype != torch.float32:
             raise ValueError("fused_encoder_policy: bf16 observation rows: the encoder launch reads f32 rows")
-        obs, cobs, small = self._flat_storage()
-        small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
-        a_dim = small[0].shape[1]
-        if a_dim > 16:
-            raise ValueError(f"fused_encoder_policy: the action width is {a_dim}: the loss kernel serves at most 16")
         if self._encoders is None:
             try:
-                self._encoders = EncoderPair(ac, obs.shape[1], cobs.shape[1])
+                self._encoders = EncoderPair(ac, st.observations.shape[-1], st.privileged_observations.shape[-1])
             except ValueError as e:
                 raise ValueError(f"fused_encoder_policy: {e}") from None
         enc = self._encoders
-        dev = obs.device
         none = _abi.CONSTS["LT_ACT_NONE"]
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        state = torch.zeros(4, device=dev)  # [0] learning rate, [1..3] sums of (value loss, surrogate, entropy)
-        state[0] = self.learning_rate
-        lr_dev, stats = state[:1], state[1:]
-        grad_of = fa.grad_views()
-        std_p, std_is_log = std_param(ac)
-        std_c = std_p.detach()
-        pair.arm_domain_check()
-        stream = _abi.stream(dev)
         nmb = self.num_mini_batches
         perm, m = st.mini_batch_permutation(nmb)
-        mb_stats = adv_stats(small[2], perm, m, nmb) if self.normalize_advantage_per_mini_batch else None
-        perm_o, perm_co = obs[perm], cobs[perm]
+        c = self._direct_begin("fused_encoder_policy", pair, perm, m)
+        dev, grad_of = c.dev, c.grad_of
+        perm_o, perm_co = c.obs[perm], c.cobs[perm]
         nets = [(enc.a_desc, enc.a_linears, perm_o)]  # the networks with an encoder
         if enc.c_desc is not None:
             nets.append((enc.c_desc, enc.c_linears, perm_co))
         tails = [rows[:, d.obs_dim - d.enc_in:].contiguous() for d, _, rows in nets]
-        n_steps = self.num_learning_epochs * nmb
-        for step_i in range(n_steps):
+        for step_i in range(self.num_learning_epochs * nmb):
             i = step_i % nmb
             idx = perm[i * m:(i + 1) * m]
             o, co = perm_o[i * m:(i + 1) * m], perm_co[i * m:(i + 1) * m]
@@ -637,19 +676,7 @@ class PPO:
             x_c = torch.empty(m, enc.c_width, device=dev, dtype=torch.float32) if enc.c_desc is not None else co
             enc_acts = enc.forward(o, co, x_a, x_c if enc.c_desc is not None else None, train=True)
             (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
-            dmu = torch.empty_like(mu)
-            dvalue = torch.empty(m, 1, device=dev, dtype=torch.float32)
-            acc = torch.empty(24, device=dev, dtype=torch.float32)
-            out = torch.empty(24, device=dev, dtype=torch.float32)
-            if std_is_log or mb_stats is not None:
-                _abi.call("lt_ppo_loss_opts", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
-                          None if mb_stats is None else mb_stats[i], dmu, dvalue, acc, out, stream)
-            else:
-                _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx, m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
-            _abi.call("lt_ppo_lr_rule", out[4:5] if adaptive else None, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out,
-                      grad_of[std_p], a_dim, stream)
+            dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx, m, i)
             dx = (torch.empty_like(x_a), torch.empty_like(x_c))
             pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
             sums = SumJobs()
@@ -661,54 +688,17 @@ class PPO:
                 backward_chain([lin.weight for lin in linears], [grad_of[lin.bias] for lin in linears], [grad_of[lin.weight] for lin in linears],
                                tails[k][i * m:(i + 1) * m], enc_acts[k][:L - 1], g, sums)
             sums.launch()
-            fa.step_dev(self.max_grad_norm, lr_dev)
-        sat, dom = pair.saturated(), pair.domain_max
-        pair.domain_max = None
-        zero = state.new_zeros(1)
-        lr, sv, ss, se, nsat, dmax = torch.cat((state, zero if sat is None else sat, zero if dom is None else dom.view(1))).tolist()  # the update's only host read
-        if nsat > 0:
-            import warnings
-
-            sat.zero_()
-            warnings.warn(f"lt_mlp_backward_pair: {int(nsat)} workgroup-layers of the gradient chain reached the f16 image's bound "
-                          "(a gradient grew by more than 500x through the layers): those rows were saturated; set LT_FUSED_BACKWARD=0 "
-                          "to run the chain as f32 library GEMMs")
-        self.learning_rate = lr
-        for group in self.optimizer.param_groups:
-            group["lr"] = lr
-        if dmax >= float(_abi.CONSTS["LT_MLP_INPUT_CLAMP"]):
-            self._warn_mlp_domain()
-        st.clear()
-        return sv / n_steps, ss / n_steps, se / n_steps, None, None
+            fa.step_dev(self.max_grad_norm, c.lr_dev)
+        return self._direct_end(c, with_dx=True)
 
     def _direct_recurrent_unsupported(self) -> str | None:
         """What `_direct_recurrent_update` needs beyond `_recurrent_update_unsupported`, a GPU and one rank (None: it is all there)."""
-        from .fused_loss import std_param
-        from .mlp import PackedPair, describe
-
         ac = self.actor_critic
-        if self._flat_adam is None:
-            return "there is no FlatAdam (fused_adam=False): the gradients are written in place into its flat bucket"
-        if not self.packed_forward:
-            return "packed_forward is off: the two MLPs run through rl/mlp.py PackedPair"
-        for name, seq in (("actor", ac.actor), ("critic", ac.critic)):
-            if describe(seq) is None:
-                return f"the MLP kernel does not serve the {name} stack (rl/mlp.py describe: Linear/activation stack, hidden widths <= 512)"
-        try:
-            self._pair = PackedPair(ac.actor, ac.critic)
-        except ValueError as e:
-            return str(e)
-        if self._pair.a.out_features > 16:
-            return f"the action width is {self._pair.a.out_features}: the loss kernel serves at most 16"
-        std_p, _ = std_param(ac)
-        if not std_p.requires_grad:
-            return "std has no gradient: the learning-rate launch writes d loss / d std into its slot of the bucket"
-        written = {id(std_p)} | {id(p) for seq in (ac.actor, ac.critic) for p in seq.parameters()}
+        why, written = self._direct_stacks_unsupported()
+        if why is not None:
+            return why
         written |= {id(p) for mem in (ac.memory_a, ac.memory_c) for p in (mem.rnn.weight_ih_l0, mem.rnn.weight_hh_l0, mem.rnn.bias_ih_l0, mem.rnn.bias_hh_l0)}
-        for name, p in ac.named_parameters():
-            if p.requires_grad and id(p) not in written:
-                return f"the parameter {name} has a gradient this form does not write"
-        return None
+        return self._unwritten_gradient(written)
 
     @staticmethod
     def _block_row_index(T: int, N: int, num_mini_batches: int, device=None) -> torch.Tensor:
@@ -719,19 +709,16 @@ class PPO:
         return (ar(T, 1, T, 1) * N + ar(num_mini_batches, num_mini_batches, 1, 1) * per + ar(per, 1, 1, per)).reshape(num_mini_batches, T * per)
 
     def _direct_recurrent_update(self):
-        """`_recurrent_update` with NO autograd graph and NO host read between its steps, as `_direct_update` is to `_fused_update`.
-        Once per update: the env blocks' observation rows laid out contiguously, their states at step 0, the row index of every block
-        into the flattened storage, [`lt_adv_stats` on those indices], the device state [lr, 3 sums].  Per optimizer step: the cell's
-        `seq_forward` (rl/memory_seq.py `direct_forward`), the packed forward of both stacks on the [T * per, H] outputs, ONE loss launch
-        that reads the small per-row tensors through the block's index and writes d loss / d (mu, value, std) (csrc/lt_ppo.hip), the
-        learning-rate rule on the device scalar, both stacks' backward chains with the gradient w.r.t. their input rows
+        """`_recurrent_update` with NO autograd graph and NO host read between its steps, as `_direct_update` is to `_fused_update` and
+        on its skeleton.  What the memories add.  Once per update: the env blocks' observation rows laid out contiguously, their states
+        at step 0, and the row index of every block into the flattened storage - the minibatch index of the loss launch and of
+        `lt_adv_stats`.  Per optimizer step: the cell's `seq_forward` (rl/memory_seq.py `direct_forward`) in front of the packed forward
+        on its [T * per, H] outputs; behind the loss, both stacks' backward chains with the gradient w.r.t. their input rows
         (`PackedPair.backward_raw(dx_out=...)`, include/lt_mlp_dx.h), the cell's `seq_backward` from those rows and the memories' eight
-        parameter gradients (`direct_backward`) - every gradient written in place into the flat bucket - and clip + Adam from the device
-        learning rate.  One host read at the end: lr, the three statistics, the saturation count and the domain record."""
+        parameter gradients (`direct_backward`) - every gradient written in place into the flat bucket."""
         why = self._recurrent_update_unsupported()  # (with the storage now: the observation rows' dtype)
         if why is not None:
             raise ValueError(f"direct_recurrent_update: {why}")
-        from .fused_loss import adv_stats, std_param
         from .memory_seq import _dones_bytes, cell_of, direct_backward, direct_forward
 
         ac, st, fa, pair = self.actor_critic, self.storage, self._flat_adam, self._pair
@@ -745,70 +732,27 @@ class PPO:
         dev = st.observations.device
         cell = cell_of(ac.memory_a, self.fused_gru_memories)
         H = ac.memory_a.rnn.hidden_size
-        _, _, small = self._flat_storage()
-        small = [t.view(-1) if t.shape[-1] == 1 else t for t in small]
-        a_dim = small[0].shape[1]
-        if a_dim > 16:
-            raise ValueError(f"direct_recurrent_update: the action width is {a_dim}: the loss kernel serves at most 16")
         idx_all = self._block_row_index(T, N, nmb, dev)
-        mb_stats = adv_stats(small[2], idx_all.view(-1), m, nmb) if self.normalize_advantage_per_mini_batch else None
+        c = self._direct_begin("direct_recurrent_update", pair, idx_all.view(-1), m)
+        grad_of = c.grad_of
         dones = _dones_bytes(st.dones.view(T, N))
         blocks = []
         for i in range(nmb):
             sl = (slice(None), slice(i * per, (i + 1) * per))
             states = [tuple(h[0][sl].reshape(per, H) for h in hs) for hs in (st.saved_hidden_states_a, st.saved_hidden_states_c)]
             blocks.append((st.observations[sl].contiguous(), st.privileged_observations[sl].contiguous(), dones[sl], *states))
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        state = torch.zeros(4, device=dev)  # [0] learning rate, [1..3] sums of (value loss, surrogate, entropy)
-        state[0] = self.learning_rate
-        lr_dev, stats = state[:1], state[1:]
-        grad_of = fa.grad_views()
-        std_p, std_is_log = std_param(ac)
-        std_c = std_p.detach()
-        pair.arm_domain_check()
-        stream = _abi.stream(dev)
-        n_steps = self.num_learning_epochs * nmb
-        for step_i in range(n_steps):
+        for step_i in range(self.num_learning_epochs * nmb):
             i = step_i % nmb
             obs, cobs, d, hc_a, hc_c = blocks[i]
             recs = direct_forward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, hc_a, hc_c)
             x_a, x_c = recs[0]["out"].view(m, H), recs[1]["out"].view(m, H)
             (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
-            dmu = torch.empty_like(mu)
-            dvalue = torch.empty(m, 1, device=dev, dtype=torch.float32)
-            acc = torch.empty(24, device=dev, dtype=torch.float32)
-            out = torch.empty(24, device=dev, dtype=torch.float32)
-            if std_is_log or mb_stats is not None:
-                _abi.call("lt_ppo_loss_opts", mu, std_c, value, *small, idx_all[i], m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), int(std_is_log),
-                          None if mb_stats is None else mb_stats[i], dmu, dvalue, acc, out, stream)
-            else:
-                _abi.call("lt_ppo_loss", mu, std_c, value, *small, idx_all[i], m, a_dim, float(self.clip_param), float(self.value_loss_coef),
-                          float(self.entropy_coef), int(bool(self.use_clipped_value_loss)), dmu, dvalue, acc, out, stream)
-            _abi.call("lt_ppo_lr_rule", out[4:5] if adaptive else None, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, lr_dev, stats, out,
-                      grad_of[std_p], a_dim, stream)
+            dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx_all[i], m, i)
             dx = (torch.empty_like(x_a), torch.empty_like(x_c))
             pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
             direct_backward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, recs, dx, grad_of)
-            fa.step_dev(self.max_grad_norm, lr_dev)
-        sat, dom = pair.saturated(), pair.domain_max
-        pair.domain_max = None
-        zero = state.new_zeros(1)
-        lr, sv, ss, se, nsat, dmax = torch.cat((state, zero if sat is None else sat, zero if dom is None else dom.view(1))).tolist()  # the update's only host read
-        if nsat > 0:
-            import warnings
-
-            sat.zero_()
-            warnings.warn(f"lt_mlp_backward_pair_dx: {int(nsat)} workgroup-layers of the gradient chain reached the f16 image's bound "
-                          "(a gradient grew by more than 500x through the layers): those rows were saturated; set LT_FUSED_BACKWARD=0 "
-                          "to run the chain as f32 library GEMMs")
-        self.learning_rate = lr
-        for group in self.optimizer.param_groups:
-            group["lr"] = lr
-        if dmax >= float(_abi.CONSTS["LT_MLP_INPUT_CLAMP"]):
-            self._warn_mlp_domain()
-        st.clear()
-        return sv / n_steps, ss / n_steps, se / n_steps, None, None
+            fa.step_dev(self.max_grad_norm, c.lr_dev)
+        return self._direct_end(c, with_dx=True)
 
     def _recurrent_update_unsupported(self) -> str | None:
         """Why `_recurrent_update` does not serve this policy / storage (None: it does)."""
@@ -840,7 +784,6 @@ class PPO:
         T, N = st.num_steps, st.num_envs
         per = N // self.num_mini_batches
         dones = st.dones.view(T, N)  # uint8 [T, N]
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
         fused = (self.fused_loss and st.observations.is_cuda and getattr(ac, "noise_std_type", "scalar") == "scalar" and st.actions.shape[-1] <= 16)
         if fused:
             from .fused_loss import fused_ppo_loss
@@ -868,7 +811,7 @@ class PPO:
                         ac.actor(out_a.view(T * per, -1)), ac.std, ac.critic(out_c.view(T * per, -1)), f(st.actions[sl]),
                         f(st.actions_log_prob[sl]), f(adv), f(returns), f(old_values), f(old_mu), f(old_sigma), self.clip_param,
                         self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
-                    if adaptive:
+                    if self._adaptive:
                         self._apply_kl(kl_mean)
                     ent = ent.detach()
                 else:
@@ -876,17 +819,9 @@ class PPO:
                     log_prob = ac.get_actions_log_prob(st.actions[sl])
                     value = ac.critic(out_c)
                     mu, sigma, ent = ac.action_mean, ac.action_std, ac.entropy.mean()
-                    if adaptive:
+                    if self._adaptive:
                         self._adapt_learning_rate(mu, sigma, old_mu, old_sigma)
-                    ratio = torch.exp(log_prob - torch.squeeze(st.actions_log_prob[sl]))
-                    a = torch.squeeze(adv)
-                    surrogate_loss = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
-                    if self.use_clipped_value_loss:
-                        clipped = old_values + (value - old_values).clamp(-self.clip_param, self.clip_param)
-                        value_loss = torch.max((value - returns).pow(2), (clipped - returns).pow(2)).mean()
-                    else:
-                        value_loss = (returns - value).pow(2).mean()
-                    loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * ent
+                    loss, surrogate_loss, value_loss = self._op_chain_loss(log_prob, value, st.actions_log_prob[sl], adv, returns, old_values, ent)
                 self._zero_grad()
                 loss.backward()
                 self._optim_step()
@@ -929,7 +864,7 @@ class PPO:
                 loss, surrogate_loss, value_loss, ent, kl_mean = fused_ppo_loss(
                     ac.actor(b.obs), std_p, ac.critic(b.critic_obs), b.actions, b.log_prob, adv, b.returns, b.values, b.mu, b.sigma,
                     self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss, std_is_log=std_is_log)
-                if self.desired_kl is not None and self.schedule == "adaptive":
+                if self._adaptive:
                     self._apply_kl(kl_mean)
                 if stats is None:
                     stats = torch.zeros(3, device=loss.device)
@@ -947,17 +882,9 @@ class PPO:
                 log_prob = ac.get_actions_log_prob(b.actions)
                 value = ac.evaluate(b.critic_obs)
             mu, sigma, entropy = ac.action_mean, ac.action_std, ac.entropy
-            if self.desired_kl is not None and self.schedule == "adaptive":
+            if self._adaptive:
                 self._adapt_learning_rate(mu, sigma, b.mu, b.sigma)
-            ratio = torch.exp(log_prob - torch.squeeze(b.log_prob))
-            a = torch.squeeze(adv)
-            surrogate_loss = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
-            if self.use_clipped_value_loss:
-                clipped = b.values + (value - b.values).clamp(-self.clip_param, self.clip_param)
-                value_loss = torch.max((value - b.returns).pow(2), (clipped - b.returns).pow(2)).mean()
-            else:
-                value_loss = (b.returns - value).pow(2).mean()
-            loss = surrogate_loss + self.value_loss_coef * value_loss - self.entropy_coef * entropy.mean()
+            loss, surrogate_loss, value_loss = self._op_chain_loss(log_prob, value, b.log_prob, adv, b.returns, b.values, entropy.mean())
             self._zero_grad()
             loss.backward()
             self._optim_step()

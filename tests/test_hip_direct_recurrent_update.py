@@ -145,6 +145,7 @@ def test_no_autograd_and_one_host_read(rnn, monkeypatch):
 
     from locotouch_amd.rl import memory_seq
     from locotouch_amd.rl.storage import RolloutStorage
+    from tests.test_hip_ppo_opts_train import count_scalar_reads
 
     direct = build(rnn, 16, "cuda:0", torch.float32, 2, 2, **KEYS)
     torch.cuda.synchronize()
@@ -165,9 +166,10 @@ def test_no_autograd_and_one_host_read(rnn, monkeypatch):
     monkeypatch.setattr(RolloutStorage, "recurrent_mini_batches", refuse("recurrent_mini_batches"))
     monkeypatch.setattr(torch.Tensor, "item", refuse("Tensor.item"))
     monkeypatch.setattr(torch.Tensor, "tolist", counted)
+    scalars = count_scalar_reads(monkeypatch)  # float(t), bool(t), int(t): reads that the two above do not see
     out = direct.update()
     monkeypatch.undo()
-    assert reads["tolist"] == 1
+    assert reads["tolist"] == 1 and scalars == []
     assert all(np.isfinite(v) for v in out[:3])
 
 

@@ -262,6 +262,8 @@ def test_one_optimizer_step_is_as_close_to_float64_as_the_autograd_form(kind):
 def test_no_autograd_and_one_host_read(monkeypatch):
     import torch
 
+    from tests.test_hip_ppo_opts_train import count_scalar_reads
+
     direct = build("actor-encoder-tanh", "cuda:0", torch.float32, 2, 2, fused_encoder_policy=True)
     before = [p.detach().clone() for p in direct.actor_critic.parameters()]
     torch.cuda.synchronize()
@@ -280,9 +282,10 @@ def test_no_autograd_and_one_host_read(monkeypatch):
     monkeypatch.setattr(torch.Tensor, "backward", refuse("Tensor.backward"))
     monkeypatch.setattr(torch.Tensor, "item", refuse("Tensor.item"))
     monkeypatch.setattr(torch.Tensor, "tolist", counted)
+    scalars = count_scalar_reads(monkeypatch)  # float(t), bool(t), int(t): reads that the two above do not see
     out = direct.update()
     monkeypatch.undo()
-    assert reads["tolist"] == 1
+    assert reads["tolist"] == 1 and scalars == []
     assert all(np.isfinite(v) for v in out[:3]) and direct.storage.step == 0
     assert all(not torch.equal(p, q) and bool(torch.isfinite(p).all()) for p, q in zip(direct.actor_critic.parameters(), before))
 

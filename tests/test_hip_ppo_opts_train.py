@@ -59,6 +59,21 @@ def count_calls(monkeypatch, names=NEW_ENTRIES, forbid=False):
     return seen
 
 
+def count_scalar_reads(monkeypatch):
+    """-> [dunder names] of every `float(t)`, `bool(t)` / `if t:` and `int(t)` of a tensor from here on: on a device tensor each is a
+    blocking host read that watching `.item()` and `.tolist()` does not see.  `monkeypatch`: the fixture, or a context of it."""
+    import torch
+
+    seen = []
+    for name in ("__float__", "__bool__", "__int__"):
+        def wrapped(t, *a, _real=getattr(torch.Tensor, name), _name=name, **k):
+            seen.append(_name)
+            return _real(t, *a, **k)
+
+        monkeypatch.setattr(torch.Tensor, name, wrapped)
+    return seen
+
+
 def test_log_std_rollout_is_fused_and_stores_the_sigma_its_launch_formed(monkeypatch):
     import torch
     from locotouch_amd.rl import FusedRollout
@@ -167,6 +182,42 @@ def test_one_direct_step_equals_the_autograd_form(log, per_mb, monkeypatch):
         torch.testing.assert_close(pa, pb, rtol=0, atol=2 * a.alg.learning_rate)
         assert float((pa - pb).abs().mean()) < 1e-6, name
     assert name_std in dict(a.alg.actor_critic.named_parameters()) and float(getattr(a.alg.actor_critic, name_std).grad.abs().max()) > 0.0
+
+
+def test_plain_direct_update_reads_the_host_once(monkeypatch):
+    """`_direct_update` of a scalar-std runner without symmetry (2 epochs x 2 minibatches): ONE `.tolist()`, no `.item()`, and no
+    `float(t)` / `bool(t)` / `int(t)` of a tensor inside `update()` - the domain record comes back in that one read."""
+    import torch
+    from locotouch_amd.rl import PPO
+
+    runner = make_runner(log=False)
+    ran = []
+    real = PPO._direct_update
+    monkeypatch.setattr(PPO, "_direct_update", lambda self, *a, **k: (ran.append(self), real(self, *a, **k))[1])
+    fused = runner._make_fused()
+    fused.begin()
+    fused.rollout(T)
+    with torch.inference_mode():
+        runner.alg.compute_returns(fused.last_critic_obs)
+    torch.cuda.synchronize()
+    tolist, lists = torch.Tensor.tolist, []
+
+    def refuse(*a, **k):
+        raise AssertionError("Tensor.item() inside the update")
+
+    def counted(t, *a, **k):
+        lists.append(tuple(t.shape))
+        return tolist(t, *a, **k)
+
+    with monkeypatch.context() as m:
+        m.setattr(torch.Tensor, "item", refuse)
+        m.setattr(torch.Tensor, "tolist", counted)
+        scalars = count_scalar_reads(m)
+        out = runner.alg.update()
+    assert ran == [runner.alg]
+    assert len(lists) == 1 and scalars == [], (lists, scalars)
+    assert lists[0] == (6,)  # lr, three sums, the saturation count, the domain record
+    assert all(math.isfinite(v) for v in out[:3]) and out[3:] == (None, None) and runner.alg.storage.step == 0
 
 
 def test_learn_runs_the_statistics_once_per_update_and_checkpoints_log_std(tmp_path, monkeypatch):

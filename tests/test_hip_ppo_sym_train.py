@@ -11,7 +11,7 @@ import math
 import pytest
 
 from tests import ppo_ref as R
-from tests.test_hip_ppo_opts_train import N, T, count_calls, make_runner
+from tests.test_hip_ppo_opts_train import N, T, count_calls, count_scalar_reads, make_runner
 
 pytestmark = pytest.mark.gpu
 
@@ -97,7 +97,7 @@ def test_learn_launches_the_gather_twice_per_update_and_reads_the_host_once(tmp_
     reads, real_update, tolist = [], PPO.update, torch.Tensor.tolist
 
     def update(self):
-        """no `.item()` and ONE `.tolist()` inside an update"""
+        """no `.item()`, no `float(t)` / `bool(t)` / `int(t)` of a tensor and ONE `.tolist()` inside an update"""
         n = [0]
 
         def refuse(*a, **k):
@@ -110,7 +110,9 @@ def test_learn_launches_the_gather_twice_per_update_and_reads_the_host_once(tmp_
         with monkeypatch.context() as m:
             m.setattr(torch.Tensor, "item", refuse)
             m.setattr(torch.Tensor, "tolist", counted)
+            scalars = count_scalar_reads(m)
             out = real_update(self)
+        assert scalars == []
         reads.append(n[0])
         return out
 
