@@ -180,7 +180,7 @@ class OnPolicyRunner:
         the same reason - an ActorCriticEncoder whose encoders csrc/lt_encoder.hip serves."""
         try:
             from ..env import LocoTouchVecEnv
-            from .fused import FusedRollout
+            from .fused import FusedRollout, rollout_unsupported
         except Exception:
             return None
         target = self.env
@@ -188,34 +188,29 @@ class OnPolicyRunner:
             target = getattr(self.env, "fused_target", lambda: None)()
         if not isinstance(target, LocoTouchVecEnv) or self.cfg.get("fused_rollout", True) is False:
             return None
-        ac = self.alg.actor_critic
+        ac, kw = self.alg.actor_critic, {}
         if type(ac) is ActorCriticRecurrent:
-            from .fused import recurrent_unsupported
-
-            # single-layer f32 LSTM memories alone (GRU ones too behind `fused_gru_memories`), without the normaliser (it would have to
-            # feed the memory step, not the MLPs)
-            gru = bool(self.cfg.get("fused_gru_memories", False))
-            if (not self.cfg.get("fused_recurrent_rollout", False) or self.empirical_normalization
-                    or recurrent_unsupported(ac, self.alg.storage, gru_memories=gru) is not None):
+            if not self.cfg.get("fused_recurrent_rollout", False):
                 return None
-            return FusedRollout(target, self.alg, fused_gru_memories=gru)
-        if type(ac) is ActorCriticEncoder:
-            from .fused import encoder_policy_unsupported
-
-            # without the key, or for what FusedRollout would refuse (a normaliser, bf16 rows, shapes outside the kernels' limits): the eager loop
-            if not self.cfg.get("fused_encoder_policy", False) or encoder_policy_unsupported(self.alg, self.empirical_normalization) is not None:
+            kw["fused_gru_memories"] = bool(self.cfg.get("fused_gru_memories", False))
+        elif type(ac) is ActorCriticEncoder:
+            if not self.cfg.get("fused_encoder_policy", False):
                 return None
-            return FusedRollout(target, self.alg, fused_encoder_policy=True)
-        if type(ac) is not ActorCritic:
+            kw["fused_encoder_policy"] = True
+        elif type(ac) is not ActorCritic:
             return None  # the fused rollout packs the actor / critic MLPs
-        if not self.empirical_normalization:
-            return FusedRollout(target, self.alg)
-        # The device normaliser (csrc/lt_obs_norm.hip) reads and writes f32 rows, and it keeps per-process statistics: ranks cannot
-        # all-reduce them per step inside a captured rollout, and one sync per iteration would change what the policy sees.  bf16
-        # observation rows and multi-rank runs therefore keep the eager loop below.
-        if self.alg.storage.observations.dtype != torch.float32 or self.dist.world_size > 1:
+        if self.empirical_normalization:
+            # The device normaliser (csrc/lt_obs_norm.hip) keeps per-process statistics: ranks cannot all-reduce them per step inside a
+            # captured rollout, and one sync per iteration would change what the policy sees.  Multi-rank runs keep the eager loop below.
+            if self.dist.world_size > 1:
+                return None
+            kw.update(obs_normalizer=self.obs_normalizer, critic_obs_normalizer=self.critic_obs_normalizer)
+        # what FusedRollout would refuse (a normaliser beside a memory or an encoder or on bf16 rows, shapes outside the kernels' limits): the
+        # eager loop - rl/fused.py states it once, for its constructor and for this.  That covers normalisers whose buffers, eps or until
+        # the kernels do not serve as well: this runner builds its own, which are served
+        if rollout_unsupported(self.alg, **kw) is not None:
             return None
-        return FusedRollout(target, self.alg, obs_normalizer=self.obs_normalizer, critic_obs_normalizer=self.critic_obs_normalizer)
+        return FusedRollout(target, self.alg, **kw)
 
     # ---- checkpoints (reference on_policy_runner.py:369-422) -------------------------------------------
     def save(self, path: str, infos=None) -> None:

@@ -73,14 +73,25 @@ def storage_snapshot(runner):
 
 @pytest.mark.parametrize("n", [64, 40], ids=["rows_in_storage", "not_a_multiple_of_16"])
 def test_rollout_storage_is_self_consistent_against_float64(n):
+    _check_self_consistency(n, packed=True)
+
+
+def test_torch_module_path_is_self_consistent_against_float64():
+    """`use_packed_mlp=False` (`_step_torch`, the path of stacks outside lt_mlp's limits) behind the memory step: the same checks with the
+    same tolerances - the float64 comparison does not care which GEMM produced mu."""
+    _check_self_consistency(64, packed=False)
+
+
+def _check_self_consistency(n, packed):
     import torch
     from locotouch_amd.rl import FusedRollout
 
     runner = make_runner(n)
     ac, alg, env = runner.alg.actor_critic, runner.alg, runner.env
-    fused = runner._make_fused()
+    fused = runner._make_fused() if packed else FusedRollout(env, alg, use_packed_mlp=False)
     assert isinstance(fused, FusedRollout) and fused.recurrent and fused.rows_in_storage == (n % 16 == 0)
-    assert fused.actor_mlp is not None and fused.launches_per_step == 3  # the packed path: memory step, policy + value, env step
+    # the packed path: memory step, policy + value, env step; the torch-module path: the memory step in front of its 11
+    assert (fused.actor_mlp is not None) == packed and fused.launches_per_step == (3 if packed else 12)
     fused.begin()
     assert all(torch.count_nonzero(x) == 0 and x.shape == (1, n, HID) for m in (ac.memory_a, ac.memory_c) for x in m.hidden_states)
     fused.rollout(T)
