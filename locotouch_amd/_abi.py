@@ -142,6 +142,8 @@ HEADERS = (
     ("PPO_OPTS", "lt_ppo_opts.h", False, (), ()),  # the log-std policy and per-minibatch advantage statistics
     ("MLP_DX", "lt_mlp_dx.h", True, (), ()),  # the input gradient of the actor and critic stacks (recurrent policies: the memories' dout)
     ("PPO_SYM", "lt_ppo_sym.h", False, (), ()),  # the mirror-symmetric PPO update: table pack, row gather, the augmented batch's loss
+    ("PPO_MIRROR", "lt_ppo_mirror.h", False, (), ()),  # the loss of the mirror-loss-only (and logging-only) symmetric update
+    ("MLP_ROWS", "lt_mlp_rows.h", True, (), ()),  # the pair forward and backward chain with a row count per network
     ("ENCODER", "lt_encoder.h", False, ("lt_encoder_forward_launches",), ("lt_encoder_desc", "lt_encoder_net")),  # the encoder in front of an ActorCriticEncoder's stacks
 )
 

@@ -62,6 +62,7 @@
 #include "lt_host_check.h"
 #include "lt_internal.h"
 #include "lt_mlp_dx.h"
+#include "lt_mlp_rows.h"
 
 using namespace lt;
 
@@ -1280,26 +1281,61 @@ int lt_mlp_forward(const lt_mlp_desc* desc, const float* packed, const float* x,
 // Training forward of two networks in one launch (PPO update: actor on the observations, critic on the critic observations):
 // outputs y0 [m][dims0[L0]], y1 [m][dims1[L1]] and, for the backward pass, the activations behind every hidden layer
 // (acts0[l], acts1[l]: [m][dims[l + 1]], l < L - 1; hidden widths must be multiples of 4).
-int lt_mlp_forward_pair(const lt_mlp_desc* d0, const float* packed0, const float* x0, const lt_mlp_desc* d1, const float* packed1, const float* x1,
-                        int64_t m, float* y0, float* y1, float* const* acts0, float* const* acts1, int acts_split, void* stream) {
-  if (!desc_ok(d0) || !desc_ok(d1) || !packed0 || !packed1 || !x0 || !x1 || !y0 || !y1 || !acts0 || !acts1 || m <= 0)
-    return einval("lt_mlp_forward_pair: invalid argument");
+// (the body of lt_mlp_forward_pair and of lt_mlp_forward_pair_rows, include/lt_mlp_rows.h: network k runs on ms[k] rows; the arguments
+// are checked by the entry point, up to the hidden widths and the activation buffers, refused here in the first one's words)
+static int forward_pair_launch(const lt_mlp_desc* const* ds, const float* const* pk, const float* const* xs, const int64_t* ms, float* const* ys,
+                               float* const* const* as, int acts_split, void* stream) {
   DualArgs d = {};
-  const lt_mlp_desc* ds[2] = {d0, d1};
-  const float* pk[2] = {packed0, packed1};
-  const float* xs[2] = {x0, x1};
-  float* ys[2] = {y0, y1};
-  float* const* as[2] = {acts0, acts1};
   for (int k = 0; k < 2; ++k) {
     fill_args(ds[k], d.net[k]);
     d.net[k].mode = MODE_FORWARD;
-    d.net[k].packed = pk[k]; d.net[k].x = xs[k]; d.net[k].m = m; d.net[k].y = ys[k]; d.net[k].acts_split = acts_split != 0;
+    d.net[k].packed = pk[k]; d.net[k].x = xs[k]; d.net[k].m = ms[k]; d.net[k].y = ys[k]; d.net[k].acts_split = acts_split != 0;
     for (int l = 0; l + 1 < ds[k]->num_layers; ++l) {
       if (!as[k][l] || (ds[k]->dims[l + 1] & 3)) return einval("lt_mlp_forward_pair: hidden widths must be multiples of 4 and every activation buffer given");
       d.net[k].act_out[l] = as[k][l];
     }
   }
   return launch(d, 2, (hipStream_t)stream);
+}
+
+int lt_mlp_forward_pair(const lt_mlp_desc* d0, const float* packed0, const float* x0, const lt_mlp_desc* d1, const float* packed1, const float* x1,
+                        int64_t m, float* y0, float* y1, float* const* acts0, float* const* acts1, int acts_split, void* stream) {
+  if (!desc_ok(d0) || !desc_ok(d1) || !packed0 || !packed1 || !x0 || !x1 || !y0 || !y1 || !acts0 || !acts1 || m <= 0)
+    return einval("lt_mlp_forward_pair: invalid argument");
+  const lt_mlp_desc* ds[2] = {d0, d1};
+  const float* pk[2] = {packed0, packed1};
+  const float* xs[2] = {x0, x1};
+  const int64_t ms[2] = {m, m};
+  float* ys[2] = {y0, y1};
+  float* const* as[2] = {acts0, acts1};
+  return forward_pair_launch(ds, pk, xs, ms, ys, as, acts_split, stream);
+}
+
+// include/lt_mlp_rows.h: the same launch with a row count per network.  launch() deals the workgroups by block range [0, b0) | [b0, b0 +
+// b1) unless both networks need the same number of them; with m0 == m1 this is lt_mlp_forward_pair's launch.
+int lt_mlp_forward_pair_rows(const lt_mlp_desc* d0, const float* packed0, const float* x0, const lt_mlp_desc* d1, const float* packed1, const float* x1,
+                             int64_t m0, int64_t m1, float* y0, float* y1, float* const* acts0, float* const* acts1, int acts_split, void* stream) {
+  const char* fn = "lt_mlp_forward_pair_rows";
+  const lt_mlp_desc* ds[2] = {d0, d1};
+  const float* pk[2] = {packed0, packed1};
+  const float* xs[2] = {x0, x1};
+  const int64_t ms[2] = {m0, m1};
+  float* ys[2] = {y0, y1};
+  float* const* as[2] = {acts0, acts1};
+  for (int k = 0; k < 2; ++k) {
+    const char* who = k ? "network 1: " : "network 0: ";
+    if (!desc_ok(ds[k])) return refuse(fn, who, "desc", "a network shape lt_mlp_forward serves");
+    const ptr_check ptrs[] = {{"packed", pk[k], 4}, {"x", xs[k], ds[k]->input_format == LT_ROWS_BF16 ? 2 : 4}, {"y", ys[k], 4}};
+    for (const auto& e : ptrs)
+      if (!e.p || (uintptr_t)e.p % e.align != 0) return refuse(fn, who, e.name, e.align == 2 ? "non-null and 2-byte aligned" : "non-null and 4-byte aligned");
+    if (!as[k]) return refuse(fn, who, "acts", "non-null");
+    if (ms[k] <= 0) return refuse(fn, "", k ? "m1" : "m0", ">= 1");
+    for (int l = 0; l + 1 < ds[k]->num_layers; ++l) {
+      if (ds[k]->dims[l + 1] & 3) return refuse(fn, who, "hidden widths", "multiples of 4");
+      if (!as[k][l] || (uintptr_t)as[k][l] % 4 != 0) return refuse(fn, who, "acts[l]", "non-null and 4-byte aligned");
+    }
+  }
+  return forward_pair_launch(ds, pk, xs, ms, ys, as, acts_split, stream);
 }
 
 int lt_rollout_policy(const lt_mlp_desc* actor, const float* packed, const float* obs, int64_t n, uint64_t seed, const int64_t* step_counter,
@@ -1416,17 +1452,15 @@ int64_t lt_mlp_backward_blocks(const lt_mlp_desc* fwd0, const lt_mlp_desc* fwd1,
   return ((m + 15) / 16 + rt - 1) / rt;
 }
 
-// dy0 [m][out0], dy1 [m][out1]: gradients w.r.t. the two networks' outputs.  acts*[l]: the forward activations behind hidden layer
-// l (lt_mlp_forward_pair); dz*[l]: OUT, the gradient w.r.t. hidden layer l's pre-activation, [m][dims[l + 1]]; amax*[l]: OUT,
-// lt_mlp_backward_blocks() floats, the per-workgroup max |dz_l|.  sat_count (optional): += 1 per workgroup and layer whose scaled
-// gradients reached the f16 image's bound (LT_MLP_INPUT_CLAMP) - the result is then saturated, not exact.
-int lt_mlp_backward_pair(const lt_mlp_desc* fwd0, const float* bpacked0, const float* dy0, const float* const* acts0, float* const* dz0, float* const* amax0,
-                         const lt_mlp_desc* fwd1, const float* bpacked1, const float* dy1, const float* const* acts1, float* const* dz1, float* const* amax1,
-                         int64_t m, int acts_split, const float* in_amax0, const float* in_amax1, int dz_split, float* scales_out, float* sat_count,
-                         void* stream) {
+// (the body of lt_mlp_backward_pair and of lt_mlp_backward_pair_rows, include/lt_mlp_rows.h: network k's chain runs on ms[k] rows; the
+// refusals are worded as lt_mlp_backward_pair has them, behind `fn`)
+static int backward_pair_launch(const char* fn, const lt_mlp_desc* fwd0, const float* bpacked0, const float* dy0, const float* const* acts0, float* const* dz0,
+                                float* const* amax0, const lt_mlp_desc* fwd1, const float* bpacked1, const float* dy1, const float* const* acts1,
+                                float* const* dz1, float* const* amax1, const int64_t* ms, int acts_split, const float* in_amax0, const float* in_amax1,
+                                int dz_split, float* scales_out, float* sat_count, void* stream) {
   lt_mlp_desc bd[2];
   const float* ia[2] = {in_amax0, in_amax1};
-  if (dz_split && (!in_amax0 || !in_amax1 || !scales_out)) return einval("lt_mlp_backward_pair: a split dz needs the global input maxima and scales_out");
+  if (dz_split && (!in_amax0 || !in_amax1 || !scales_out)) return refuse(fn, "a split dz needs the global input maxima and scales_out");
   const lt_mlp_desc* fw[2] = {fwd0, fwd1};
   const float* pk[2] = {bpacked0, bpacked1};
   const float* dy[2] = {dy0, dy1};
@@ -1435,15 +1469,85 @@ int lt_mlp_backward_pair(const lt_mlp_desc* fwd0, const float* bpacked0, const f
   float* const* am[2] = {amax0, amax1};
   DualArgs d = {};
   for (int k = 0; k < 2; ++k) {
-    if (!fw[k] || !pk[k] || !dy[k] || !ac[k] || !dz[k] || !am[k] || m <= 0 || !backward_desc(fw[k], &bd[k]))
-      return einval("lt_mlp_backward_pair: invalid argument");
+    if (!fw[k] || !pk[k] || !dy[k] || !ac[k] || !dz[k] || !am[k] || ms[k] <= 0 || !backward_desc(fw[k], &bd[k])) return refuse(fn, "invalid argument");
     for (int l = 0; l + 1 < fw[k]->num_layers; ++l)
-      if (!ac[k][l] || !dz[k][l] || !am[k][l]) return einval("lt_mlp_backward_pair: null layer buffer");
-    fill_backward(&bd[k], fw[k]->num_layers, pk[k], dy[k], m, ac[k], dz[k], am[k], sat_count, d.net[k]);
+      if (!ac[k][l] || !dz[k][l] || !am[k][l]) return refuse(fn, "null layer buffer");
+    fill_backward(&bd[k], fw[k]->num_layers, pk[k], dy[k], ms[k], ac[k], dz[k], am[k], sat_count, d.net[k]);
     d.net[k].acts_split = acts_split != 0;
     d.net[k].in_amax = ia[k]; d.net[k].dz_split = dz_split != 0; d.net[k].scale_out = scales_out ? scales_out + k : nullptr;
   }
   return launch(d, 2, (hipStream_t)stream);
+}
+
+// dy0 [m][out0], dy1 [m][out1]: gradients w.r.t. the two networks' outputs.  acts*[l]: the forward activations behind hidden layer
+// l (lt_mlp_forward_pair); dz*[l]: OUT, the gradient w.r.t. hidden layer l's pre-activation, [m][dims[l + 1]]; amax*[l]: OUT,
+// lt_mlp_backward_blocks() floats, the per-workgroup max |dz_l|.  sat_count (optional): += 1 per workgroup and layer whose scaled
+// gradients reached the f16 image's bound (LT_MLP_INPUT_CLAMP) - the result is then saturated, not exact.
+int lt_mlp_backward_pair(const lt_mlp_desc* fwd0, const float* bpacked0, const float* dy0, const float* const* acts0, float* const* dz0, float* const* amax0,
+                         const lt_mlp_desc* fwd1, const float* bpacked1, const float* dy1, const float* const* acts1, float* const* dz1, float* const* amax1,
+                         int64_t m, int acts_split, const float* in_amax0, const float* in_amax1, int dz_split, float* scales_out, float* sat_count,
+                         void* stream) {
+  const int64_t ms[2] = {m, m};
+  return backward_pair_launch("lt_mlp_backward_pair", fwd0, bpacked0, dy0, acts0, dz0, amax0, fwd1, bpacked1, dy1, acts1, dz1, amax1, ms, acts_split, in_amax0,
+                              in_amax1, dz_split, scales_out, sat_count, stream);
+}
+
+// include/lt_mlp_rows.h: workgroups of network k in lt_mlp_backward_pair_rows over (m0, m1) rows = entries of every amax array of that
+// network.  The row tiles are one choice for the launch, from the tiles of both networks together (launch_shape).
+int lt_mlp_backward_blocks_rows(const lt_mlp_desc* fwd0, const lt_mlp_desc* fwd1, int64_t m0, int64_t m1, int64_t* blocks0, int64_t* blocks1) {
+  const char* fn = "lt_mlp_backward_blocks_rows";
+  lt_mlp_desc b0, b1;
+  if (!fwd0 || !backward_desc(fwd0, &b0)) return refuse(fn, "network 0: ", "fwd", "a network with a backward stream (lt_mlp_backward_packed_floats)");
+  if (!fwd1 || !backward_desc(fwd1, &b1)) return refuse(fn, "network 1: ", "fwd", "a network with a backward stream (lt_mlp_backward_packed_floats)");
+  if (m0 <= 0) return refuse(fn, "", "m0", ">= 1");
+  if (m1 <= 0) return refuse(fn, "", "m1", ">= 1");
+  if (!blocks0) return refuse(fn, "", "blocks0", "non-null");
+  if (!blocks1) return refuse(fn, "", "blocks1", "non-null");
+  DualArgs d = {};
+  fill_args(&b0, d.net[0]);
+  fill_args(&b1, d.net[1]);
+  d.net[0].m = m0; d.net[1].m = m1;
+  size_t lds;
+  const int rt = launch_shape(d, 2, &lds);
+  *blocks0 = ((m0 + 15) / 16 + rt - 1) / rt;
+  *blocks1 = ((m1 + 15) / 16 + rt - 1) / rt;
+  return LT_OK;
+}
+
+int lt_mlp_backward_pair_rows(const lt_mlp_desc* fwd0, const float* bpacked0, const float* dy0, const float* const* acts0, float* const* dz0, float* const* amax0,
+                              const lt_mlp_desc* fwd1, const float* bpacked1, const float* dy1, const float* const* acts1, float* const* dz1, float* const* amax1,
+                              int64_t m0, int64_t m1, int acts_split, const float* in_amax0, const float* in_amax1, int dz_split, float* scales_out,
+                              float* sat_count, void* stream) {
+  const char* fn = "lt_mlp_backward_pair_rows";
+  const lt_mlp_desc* fw[2] = {fwd0, fwd1};
+  const float* pk[2] = {bpacked0, bpacked1};
+  const float* dy[2] = {dy0, dy1};
+  const float* ia[2] = {in_amax0, in_amax1};
+  const float* const* ac[2] = {acts0, acts1};
+  float* const* dz[2] = {dz0, dz1};
+  float* const* am[2] = {amax0, amax1};
+  const int64_t ms[2] = {m0, m1};
+  for (int k = 0; k < 2; ++k) {
+    const char* who = k ? "network 1: " : "network 0: ";
+    lt_mlp_desc bd;
+    if (!fw[k] || !backward_desc(fw[k], &bd)) return refuse(fn, who, "fwd", "a network with a backward stream (lt_mlp_backward_packed_floats)");
+    const ptr_check ptrs[] = {{"bpacked", pk[k], 4}, {"dy", dy[k], 4}};
+    if (const int rc = check_ptrs(fn, who, ptrs)) return rc;
+    if (!ac[k]) return refuse(fn, who, "acts", "non-null");
+    if (!dz[k]) return refuse(fn, who, "dz", "non-null");
+    if (!am[k]) return refuse(fn, who, "amax", "non-null");
+    if ((uintptr_t)ia[k] % 4 != 0) return refuse(fn, who, "in_amax", "NULL or 4-byte aligned");
+    if (dz_split && !ia[k]) return refuse(fn, who, "in_amax", "non-null where dz_split is set (a split dz carries one scale for the launch)");
+    if (ms[k] <= 0) return refuse(fn, "", k ? "m1" : "m0", ">= 1");
+    for (int l = 0; l + 1 < fw[k]->num_layers; ++l) {
+      const ptr_check layer[] = {{"acts[l]", ac[k][l], 4}, {"dz[l]", dz[k][l], 4}, {"amax[l]", am[k][l], 4}};
+      if (const int rc = check_ptrs(fn, who, layer)) return rc;
+    }
+  }
+  if ((uintptr_t)scales_out % 4 != 0 || (dz_split && !scales_out)) return refuse(fn, "", "scales_out", "4-byte aligned, and non-null where dz_split is set");
+  if ((uintptr_t)sat_count % 4 != 0) return refuse(fn, "", "sat_count", "NULL or 4-byte aligned");
+  return backward_pair_launch(fn, fwd0, bpacked0, dy0, acts0, dz0, amax0, fwd1, bpacked1, dy1, acts1, dz1, amax1, ms, acts_split, in_amax0, in_amax1, dz_split,
+                              scales_out, sat_count, stream);
 }
 
 

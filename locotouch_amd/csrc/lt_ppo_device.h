@@ -1,5 +1,5 @@
-// Device functions of the PPO minibatch loss, shared by its two kernels: lt_ppo_loss_kernel (lt_ppo.hip) and lt_ppo_loss_sym_kernel
-// (lt_ppo_sym.hip, the mirror-augmented batch).  One text for the pieces whose numeric care was paid for once: the float64 exponential
+// Device functions of the PPO minibatch loss, shared by its three kernels: lt_ppo_loss_kernel (lt_ppo.hip), lt_ppo_loss_sym_kernel
+// (lt_ppo_sym.hip, the mirror-augmented batch) and lt_ppo_loss_mirror_kernel (the same file, the mirror loss without augmentation).  One text for the pieces whose numeric care was paid for once: the float64 exponential
 // of a log-std policy's sigma, the KL with true divisions, the branch rules of the two clips, the block reduction and the one-wave finish.
 #pragma once
 

@@ -1,5 +1,6 @@
 // The mirror-symmetric PPO update (include/lt_ppo_sym.h): the packed table of a signed column permutation, the once-per-update gather of
-// every minibatch's rows with their mirror images, and the minibatch loss with its gradients for the augmented batch [original; mirrored].
+// every minibatch's rows with their mirror images, and the minibatch loss with its gradients for the augmented batch [original; mirrored];
+// and (include/lt_ppo_mirror.h) the loss of the update WITHOUT augmentation, where the actor alone runs on [original; mirrored].
 //
 // Reference: loco_rl/loco_rl/algorithms/ppo.py:216-246 (augmentation: observations and actions mirrored, old log-prob / advantages /
 // returns / target values repeated) and :304-337 (mirror loss: MSE between the actor's mean on the mirrored observation and the mirror
@@ -14,6 +15,7 @@
 #include "lt_host_check.h"
 #include "lt_internal.h"
 #include "lt_ppo_device.h"
+#include "lt_ppo_mirror.h"
 #include "lt_ppo_sym.h"
 
 namespace {
@@ -170,6 +172,94 @@ __global__ __launch_bounds__(64) void lt_ppo_sym_finalize_kernel(const float* __
   }
 }
 
+// ---- the loss, mirror term alone (include/lt_ppo_mirror.h) -------------------------------------------------------------------------
+// A thread owns row r: scored as lt_ppo_loss_kernel scores it (divisor M), and the mirror difference of the pair (r, M + r), whose
+// gradient goes into row M + r alone.  MIRROR as above; without it row M + r of dmu is written as zeros (the backward chain may still
+// read it).  acc as lt_ppo_loss_sym_kernel's.
+template <bool LOG, bool NORM, bool MIRROR>
+__global__ __launch_bounds__(256) void lt_ppo_loss_mirror_kernel(const float* __restrict__ mu, const float* __restrict__ stdp, const float* __restrict__ value,
+                                                                 const float* __restrict__ actions, const float* __restrict__ old_logp,
+                                                                 const float* __restrict__ adv, const float* __restrict__ returns,
+                                                                 const float* __restrict__ old_values, const float* __restrict__ old_mu,
+                                                                 const float* __restrict__ old_sigma, const long long* __restrict__ idx, long long M, int A,
+                                                                 float clip, float vcoef, int clipped_value, const float* __restrict__ adv_stats,
+                                                                 const int* __restrict__ act_table, float mirror_scale, float* __restrict__ dmu,
+                                                                 float* __restrict__ dvalue, float* __restrict__ acc) {
+  const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool ok = row < M;
+  const long long src = (ok && idx) ? idx[row] : row;  // row of the rollout storage this minibatch row was drawn from
+  __shared__ float sigma_lds[MAX_A];  // (LOG alone; unreferenced otherwise)
+  if constexpr (LOG) {
+    if ((int)threadIdx.x < A) sigma_lds[threadIdx.x] = lt_sigma_of_log(stdp[threadIdx.x]);
+    __syncthreads();
+  }
+  float part[4 + MAX_A];
+  float amax_mu = 0.f, amax_v = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4 + MAX_A; ++i) part[i] = 0.f;
+  if (ok) {
+    const float inv_m = 1.f / (float)M;
+    const long long row1 = M + row;
+    float logp = 0.f, kl = 0.f, sq = 0.f;
+    float z[MAX_A], isg[MAX_A], d[MAX_A];
+#pragma unroll
+    for (int a = 0; a < MAX_A; ++a) {
+      if (a < A) {
+        const unsigned t = (unsigned)act_table[a];
+        const int sa = min((int)(t & 0x7FFFu), A - 1);  // (a packed table of A columns holds src < A; the clamp keeps any other in the row)
+        const float sg = LOG ? sigma_lds[a] : stdp[a], m = mu[row * A + a], x = actions[src * A + a];
+        const float om = old_mu[src * A + a], os = old_sigma[src * A + a];
+        isg[a] = 1.f / sg;
+        z[a] = (x - m) * isg[a];
+        logp += lt_ppo_logp_term<LOG>(z[a], sg, stdp[a]);
+        kl += lt_ppo_kl_term(sg, os, om, m);
+        d[a] = mu[row1 * A + a] - __uint_as_float(__float_as_uint(mu[row * A + sa]) ^ (t & SIGN_BIT));  // against the mirror of row r's mean (detached)
+        sq += d[a] * d[a];
+      }
+    }
+    float advr = adv[src];
+    if constexpr (NORM) advr = (advr - adv_stats[0]) * adv_stats[1];
+    const float ratio = __expf(logp - old_logp[src]);
+    LT_PPO_SURROGATE(advr, ratio, clip, s1, s2, dsurr_dratio)
+    const float dlogp = dsurr_dratio * ratio * inv_m;
+#pragma unroll
+    for (int a = 0; a < MAX_A; ++a) {
+      if (a < A) {
+        const float g0 = dlogp * z[a] * isg[a];
+        const float g1 = MIRROR ? mirror_scale * d[a] : 0.f;  // mirror_coeff * 2 d / (M A)
+        dmu[row * A + a] = g0;
+        dmu[row1 * A + a] = g1;
+        amax_mu = fmaxf(amax_mu, fmaxf(fabsf(g0), fabsf(g1)));
+        if constexpr (LOG) part[4 + a] = dlogp * (z[a] * z[a] - 1.f);
+        else part[4 + a] = dlogp * (z[a] * z[a] - 1.f) * isg[a];
+      }
+    }
+    const float v = value[row], R = returns[src];
+    float vl, dv;
+    LT_PPO_VALUE_LOSS(v, R, old_values, src, clip, clipped_value, vl, dv)
+    dvalue[row] = vcoef * dv * inv_m;
+    amax_v = fabsf(vcoef * dv * inv_m);
+    part[0] = fmaxf(s1, s2);
+    part[1] = vl;
+    part[2] = kl;
+    part[3] = sq;
+  }
+  LT_PPO_BLOCK_REDUCE(part, amax_mu, amax_v, A, acc, true)
+}
+
+// The one-wave finish: lt_ppo_finalize with the divisor M, then lane 0 forms the symmetry loss and adds it where asked.
+__global__ __launch_bounds__(64) void lt_ppo_mirror_finalize_kernel(const float* __restrict__ acc, const float* __restrict__ stdp, int A, float inv_m, float inv_ma,
+                                                                    float vcoef, float ecoef, int std_is_log, float mirror_coeff, float* __restrict__ out,
+                                                                    float* __restrict__ sym_sum) {
+  lt_ppo_finalize(acc, stdp, A, inv_m, vcoef, ecoef, std_is_log, out);
+  if (threadIdx.x == 0) {
+    const float sym = acc[3] * inv_ma;
+    out[5] = sym;
+    if (mirror_coeff != 0.f) out[0] += mirror_coeff * sym;
+    if (sym_sum) *sym_sum += sym;
+  }
+}
+
 }  // namespace
 
 extern "C" int lt_sym_table_pack(const int32_t* src_host, const float* sign_host, int D, int32_t* table, void* stream) {
@@ -262,5 +352,53 @@ extern "C" int lt_ppo_loss_sym(const float* mu, const float* stdp, const float* 
   if (out)
     hipLaunchKernelGGL(lt_ppo_sym_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, stdp, A, 1.f / (float)(2 * M), 1.f / (float)M, inv_ma,
                        value_loss_coef, entropy_coef, std_is_log ? 1 : 0, mirror_coeff, out, sym_sum);
+  return launch_status(fn);
+}
+
+extern "C" int lt_ppo_loss_mirror(const float* mu, const float* stdp, const float* value, const float* actions, const float* old_logp, const float* adv,
+                                  const float* returns, const float* old_values, const float* old_mu, const float* old_sigma, const int64_t* idx, int64_t M,
+                                  int A, float clip, float value_loss_coef, float entropy_coef, int use_clipped_value_loss, int std_is_log,
+                                  const float* adv_stats, const int32_t* act_table, float mirror_coeff, float* dmu, float* dvalue, float* acc, float* out,
+                                  float* sym_sum, void* stream) {
+  const char* fn = "lt_ppo_loss_mirror";
+  const ptr_check ptrs[] = {{"mu", mu, 4}, {"std", stdp, 4}, {"value", value, 4}, {"actions", actions, 4}, {"old_logp", old_logp, 4}, {"adv", adv, 4},
+                            {"returns", returns, 4}, {"old_values", old_values, 4}, {"old_mu", old_mu, 4}, {"old_sigma", old_sigma, 4},
+                            {"act_table", act_table, 4}, {"dmu", dmu, 4}, {"dvalue", dvalue, 4}, {"acc", acc, 4}};
+  if (const int rc = check_ptrs(fn, "", ptrs)) return rc;
+  if ((uintptr_t)idx % 8 != 0) return refuse(fn, "", "idx", "NULL or 8-byte aligned");
+  if ((uintptr_t)adv_stats % 4 != 0) return refuse(fn, "", "adv_stats", "NULL or 4-byte aligned");
+  if ((uintptr_t)out % 4 != 0) return refuse(fn, "", "out", "NULL or 4-byte aligned");
+  if ((uintptr_t)sym_sum % 4 != 0) return refuse(fn, "", "sym_sum", "NULL or 4-byte aligned");
+  if (sym_sum && !out) return refuse(fn, "", "out", "non-null where sym_sum is given (the finish launch forms the symmetry loss)");
+  if (M < 1 || M > 0x7FFFFFFF) return refuse(fn, "", "M", "in [1, 2^31)");
+  if (A < 1 || A > MAX_A) return refuse(fn, "", "A", "in [1, 16]");
+  // (the library is built with -ffinite-math-only, which lets the compiler take a float ARGUMENT for finite: the value is read back
+  // through a volatile, and a NaN or an infinity is told by its exponent bits)
+  volatile float coeff_held = mirror_coeff;
+  const float coeff_seen = coeff_held;
+  uint32_t coeff_bits;
+  memcpy(&coeff_bits, &coeff_seen, sizeof coeff_bits);
+  if ((coeff_bits & 0x7F800000u) == 0x7F800000u) return refuse(fn, "", "mirror_coeff", "finite");
+  const hipError_t e = hipMemsetAsync(acc, 0, sizeof(float) * (4 + MAX_A + 4), (hipStream_t)stream);
+  if (e != hipSuccess) { lt_set_error(hipGetErrorString(e)); return LT_EHIP; }
+  const dim3 grid((unsigned)((M + 255) / 256));
+  const float inv_ma = (float)(1.0 / ((double)M * (double)A));
+  const float mirror_scale = (float)((double)mirror_coeff * 2.0 / ((double)M * (double)A));
+#define LT_PPO_MIRROR_LAUNCH(LOG, NORM, MIRROR)                                                                                                        \
+  hipLaunchKernelGGL((lt_ppo_loss_mirror_kernel<LOG, NORM, MIRROR>), grid, dim3(256), 0, (hipStream_t)stream, mu, stdp, value, actions, old_logp, adv, \
+                     returns, old_values, old_mu, old_sigma, (const long long*)idx, (long long)M, A, clip, value_loss_coef, use_clipped_value_loss,    \
+                     adv_stats, (const int*)act_table, mirror_scale, dmu, dvalue, acc)
+#define LT_PPO_MIRROR_PICK(MIRROR)                                       \
+  if (std_is_log && adv_stats) LT_PPO_MIRROR_LAUNCH(true, true, MIRROR); \
+  else if (std_is_log) LT_PPO_MIRROR_LAUNCH(true, false, MIRROR);        \
+  else if (adv_stats) LT_PPO_MIRROR_LAUNCH(false, true, MIRROR);         \
+  else LT_PPO_MIRROR_LAUNCH(false, false, MIRROR)
+  if (mirror_coeff != 0.f) { LT_PPO_MIRROR_PICK(true); }
+  else { LT_PPO_MIRROR_PICK(false); }
+#undef LT_PPO_MIRROR_PICK
+#undef LT_PPO_MIRROR_LAUNCH
+  if (out)
+    hipLaunchKernelGGL(lt_ppo_mirror_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, stdp, A, 1.f / (float)M, inv_ma, value_loss_coef,
+                       entropy_coef, std_is_log ? 1 : 0, mirror_coeff, out, sym_sum);
   return launch_status(fn);
 }

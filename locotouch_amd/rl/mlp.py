@@ -126,9 +126,9 @@ class PackedMLP:
     __call__ = forward
 
 
-def _alloc_outputs(nets, m, device):
+def _alloc_outputs(nets, ms, device):
     ys, acts = [], []
-    for net in nets:
+    for net, m in zip(nets, ms):
         dims = [net.desc.dims[i] for i in range(net.desc.num_layers + 1)]
         ys.append(torch.empty(m, dims[-1], device=device, dtype=torch.float32))
         acts.append([torch.empty(m, d, device=device, dtype=torch.float32) for d in dims[1:-1]])
@@ -136,8 +136,14 @@ def _alloc_outputs(nets, m, device):
 
 
 def _forward_pair(nets, x0, x1, acts_split: bool):
-    """lt_mlp_forward_pair into fresh tensors: ((y0, y1), (activations of nets[0], of nets[1]))."""
-    ys, acts = _alloc_outputs(nets, x0.shape[0], x0.device)
+    """lt_mlp_forward_pair into fresh tensors: ((y0, y1), (activations of nets[0], of nets[1])).  Inputs of different row counts go
+    through lt_mlp_forward_pair_rows (include/lt_mlp_rows.h): every tensor of network k then has x_k's rows."""
+    m0, m1 = x0.shape[0], x1.shape[0]
+    ys, acts = _alloc_outputs(nets, (m0, m1), x0.device)
+    if m0 != m1:
+        _abi.call("lt_mlp_forward_pair_rows", nets[0].desc, nets[0].packed, x0, nets[1].desc, nets[1].packed, x1, m0, m1, ys[0], ys[1],
+                  _abi.ptr_array(acts[0]), _abi.ptr_array(acts[1]), int(acts_split), _abi.stream())
+        return ys, acts
     _abi.call("lt_mlp_forward_pair", nets[0].desc, nets[0].packed, x0, nets[1].desc, nets[1].packed, x1, x0.shape[0], ys[0], ys[1],
               _abi.ptr_array(acts[0]), _abi.ptr_array(acts[1]), int(acts_split), _abi.stream())
     return ys, acts
@@ -400,10 +406,12 @@ class PackedPair:
     def _backward_fused(self, x0, x1, acts, dy0, dy1, grad_of, sums, x_split_rows=None, after_first=None, dy_amax=None, dx_out=None) -> None:
         """The backward pass as: two head launches (lt_head_wgrad), ONE launch for both stacks' chains of input gradients
         (lt_mlp_backward_pair: dz of every hidden layer, ELU' applied in the layer epilogue, per-workgroup max |dz|), six weight
-        gradients on the matrix cores that also leave the bias gradients' partials (lt_wgrad), one launch of ordered sums."""
+        gradients on the matrix cores that also leave the bias gradients' partials (lt_wgrad), one launch of ordered sums.
+        x0 and x1 may differ in their row counts (lt_mlp_backward_pair_rows, include/lt_mlp_rows.h): every launch of network k then
+        takes x_k's rows and the chain's workgroups per network."""
         lib = _abi.load()
         stream = _abi.stream()
-        m = x0.shape[0]
+        ms = (x0.shape[0], x1.shape[0])
         nets, xs = (self.a, self.b), (x0, x1)
         asp = int(self.acts_split)                      # format of `acts` (forward_raw)
         xsp = int(x_split_rows is not None)             # the observation rows in the split format, from the caller (once per update)
@@ -415,7 +423,14 @@ class PackedPair:
         dev = x0.device
         if self.sat is None:
             self.sat = torch.zeros(1, device=dev, dtype=torch.float32)
-        nblk = lib.lt_mlp_backward_blocks(ctypes.byref(nets[0].desc), ctypes.byref(nets[1].desc), m)
+        if ms[0] == ms[1]:
+            nblks = (lib.lt_mlp_backward_blocks(ctypes.byref(nets[0].desc), ctypes.byref(nets[1].desc), ms[0]),) * 2
+        else:
+            if dx_out is not None:
+                raise ValueError("PackedPair: input gradients (dx_out) are served for inputs of equal row counts only")
+            blocks = (ctypes.c_int64(), ctypes.c_int64())
+            _abi.call("lt_mlp_backward_blocks_rows", nets[0].desc, nets[1].desc, ms[0], ms[1], ctypes.byref(blocks[0]), ctypes.byref(blocks[1]))
+            nblks = (blocks[0].value, blocks[1].value)
         dzs, amaxs, arrs = [], [], []
         # one list of ordered sums per network when the caller wants the first network's gradients early (`after_first`: the trainer
         # starts the all-reduce of the actor's half of the bucket under the critic's weight gradients), else one list for both
@@ -424,6 +439,7 @@ class PackedPair:
             if not self._bpacked_fresh:  # (forward_raw packs the transposed streams with the forward ones)
                 net.pack_backward()
             L = len(net.linears)
+            m, nblk = ms[k], nblks[k]
             n, kk = dys[k].shape[1], acts[k][L - 2].shape[1]
             ws = torch.empty(lib.lt_head_wgrad_ws_floats(m, n, kk), device=dev, dtype=torch.float32)
             _abi.call("lt_head_wgrad", dys[k], acts[k][L - 2], asp, m, n, kk, None, None, ws, stream)
@@ -442,8 +458,10 @@ class PackedPair:
         if dx_kernel and not self._dx_fresh:  # (forward_raw(with_dx=True) packs W_0 with everything else)
             self.pack_training(with_backward=True, with_dx=True)
         chain = (nets[0].desc, nets[0].bpacked, dys[0], *arrs[0], nets[1].desc, nets[1].bpacked, dys[1], *arrs[1],
-                 m, asp, in_amax[0], in_amax[1], dzsp, scales, self.sat)
-        if dx_kernel:  # the chain and, behind it, dx = dz_0 W_0 of both stacks (include/lt_mlp_dx.h)
+                 *(ms[:1] if ms[0] == ms[1] else ms), asp, in_amax[0], in_amax[1], dzsp, scales, self.sat)
+        if ms[0] != ms[1]:
+            _abi.call("lt_mlp_backward_pair_rows", *chain, stream)
+        elif dx_kernel:  # the chain and, behind it, dx = dz_0 W_0 of both stacks (include/lt_mlp_dx.h)
             _abi.call("lt_mlp_backward_pair_dx", *chain, dx_out[0], dx_out[1], stream)
         else:
             _abi.call("lt_mlp_backward_pair", *chain, stream)
@@ -451,6 +469,7 @@ class PackedPair:
                 for k, net in enumerate(nets):
                     self._dx_library(dzs[k][0], net.linears[0].weight, scales[k] if dzsp else None, dx_out[k])
         for k, net in enumerate(nets):
+            m, nblk = ms[k], nblks[k]
             for l in range(len(net.linears) - 2, -1, -1):
                 inp = acts[k][l - 1] if l > 0 else xs[k]
                 dz = dzs[k][l]

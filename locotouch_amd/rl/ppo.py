@@ -3,8 +3,8 @@
 Behavioural twin of the reference's `PPO` (loco_rl/loco_rl/algorithms/ppo.py:19-385) for the feed-forward
 ActorCritic path the LocoTouch agents use (agents/rsl_rl_ppo_cfg.py:11-30: clip 0.2, gamma 0.99, lam 0.95, lr 1e-3
 adaptive, desired KL 0.01, entropy 0.01, value coef 1.0, grad-norm 1.0, 5 epochs x 4 minibatches), with the reference's `symmetry_cfg`
-branch (mirrored data augmentation and / or a mirror loss: `_symmetry_update`; with augmentation on the GPU inside `_direct_update`,
-include/lt_ppo_sym.h).  The RND branch is not built: a `rnd_cfg` is refused.
+branch (mirrored data augmentation and / or a mirror loss: `_symmetry_update`; on the GPU inside `_direct_update`, include/lt_ppo_sym.h
+with augmentation and include/lt_ppo_mirror.h without).  The RND branch is not built: a `rnd_cfg` is refused.
 An `ActorCriticEncoder` updates through the op chain, or - behind the opt-in key `fused_encoder_policy` - without an autograd graph
 (`_direct_encoder_update`, include/lt_encoder.h).
 The three updates without an autograd graph (`_direct_update`, `_direct_encoder_update`, `_direct_recurrent_update`) share one skeleton -
@@ -292,7 +292,7 @@ class PPO:
         (tests/test_hip_ppo_graph.py); the host used to wait for the KL of every step - 20 stalls per iteration, ~350 us of idle GPU each.
 
         This form's own: the rows of both networks gathered through the permutation once per update (with `symmetry_cfg` by
-        `lt_sym_gather_rows`, [original; mirrored]), the same rows in the split format, the packed forward on them, and the gradient
+        `lt_sym_gather_rows`, [original; mirrored]: both networks' under augmentation, the actor's alone without), the same rows in the split format, the packed forward on them, and the gradient
         all-reduce of a multi-rank job around the backward pass.  Log-type std and per-minibatch advantage normalisation as in
         `_fused_update`: `log_std` and its slot of the bucket stand where `std` and its slot do, the statistics come from one
         `lt_adv_stats` launch per update and stay per rank in a multi-rank job."""
@@ -307,27 +307,43 @@ class PPO:
         critic_at = fa.offset_of(next(iter(ac.critic.parameters())))
         two_buckets = split_buckets and 0 < critic_at < self._flat_grad.numel()
         sym_args = None
+        mirror_only = sym is not None and not sym["use_data_augmentation"]
         if sym is None:
-            rows = m
+            rows = crows = m  # rows of a minibatch in the actor's and in the critic's forward
             perm_o, perm_co = obs[perm], cobs[perm]
             if perm_o.dtype != torch.float32:  # bf16 observation storage (BASELINE config 5): the update computes in f32
                 perm_o, perm_co = perm_o.float(), perm_co.float()
+        elif mirror_only:
+            # the mirror loss without augmentation, or the symmetry loss for the log alone (include/lt_ppo_mirror.h): the ACTOR runs on
+            # [original; mirrored], gathered once as below; the critic, the surrogate and the value loss keep their m rows, and the two
+            # networks share launches with a row count each (include/lt_mlp_rows.h)
+            rows, crows = 2 * m, m
+            tab_o, _, tab_a = self._symmetry_tables(dev, obs.shape[1], None, c.a_dim)
+            perm_o, perm_co = self._symmetry_gather(obs, perm, m, tab_o), cobs[perm]
+            if perm_co.dtype != torch.float32:
+                perm_co = perm_co.float()
+            sym_args = ("lt_ppo_loss_mirror", tab_a, float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0)
         else:
             # the mirror-augmented update (include/lt_ppo_sym.h): ONE gather per network writes every minibatch as 2 m contiguous f32 rows
             # [original; mirrored]; the statistics above are those of the original rows (ppo.py:223-225 runs before the repeat)
-            rows = 2 * m
+            rows = crows = 2 * m
             tab_o, tab_co, tab_a = self._symmetry_tables(dev, obs.shape[1], cobs.shape[1], c.a_dim)
             perm_o, perm_co = (self._symmetry_gather(x, perm, m, t) for x, t in ((obs, tab_o), (cobs, tab_co)))
-            sym_args = (tab_a, float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0)
+            sym_args = ("lt_ppo_loss_sym", tab_a, float(sym["mirror_loss_coeff"]) if sym["use_mirror_loss"] else 0.0)
+        # with no mirror term in the loss (logged only) the mirrored rows carry no gradient: the actor's backward pass runs on the first m
+        # rows, a prefix of every buffer, and both networks have m rows there again
+        brows = m if mirror_only and not sym["use_mirror_loss"] else rows
         # the same rows in the MLP kernels' split format (f16 hi | f16 lo): what the first layer's weight gradient multiplies, 20 times
-        split_o = (pair.split_rows(perm_o), pair.split_rows(perm_co)) if pair._fused_backward_possible(perm_o[:rows], perm_co[:rows]) else None
+        split_o = (pair.split_rows(perm_o), pair.split_rows(perm_co)) if pair._fused_backward_possible(perm_o[:rows], perm_co[:crows]) else None
         for step_i in range(self.num_learning_epochs * self.num_mini_batches):
             i = step_i % self.num_mini_batches
             idx = perm[i * m:(i + 1) * m]
-            o, co = perm_o[i * rows:(i + 1) * rows], perm_co[i * rows:(i + 1) * rows]
-            xs = (split_o[0][i * rows:(i + 1) * rows], split_o[1][i * rows:(i + 1) * rows]) if split_o is not None else None
+            o, co = perm_o[i * rows:(i + 1) * rows], perm_co[i * crows:(i + 1) * crows]
+            xs = (split_o[0][i * rows:i * rows + brows], split_o[1][i * crows:(i + 1) * crows]) if split_o is not None else None
             (mu, value), acts = pair.forward_raw(o, co)
             dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx, m, i, sym_args)
+            if brows != rows:
+                o, dmu, acts = o[:brows], dmu[:brows], ([a[:brows] for a in acts[0]], acts[1])
             if self.dist.world_size > 1 and two_buckets:
                 # the bucket in two halves (std + actor | critic): the actor's all-reduce runs on RCCL's stream under the critic's
                 # three weight-gradient launches (~105 us at 24 576 rows), only the critic's half stays exposed
@@ -374,20 +390,20 @@ class PPO:
     def _direct_loss_and_rule(self, c, mu, value, idx, m: int, i: int, sym_args=None):
         """One step's loss launch and learning-rate launch, for every graph-free update: -> (dmu, dvalue, acc).  The loss entry reads the
         small per-row tensors through `idx` (m rows; minibatch `i` of the update) and writes d loss / d (mu, value), its sums and the
-        gradient maxima acc[20], acc[21]: `lt_ppo_loss_sym` with `sym_args` = (action table, mirror coefficient) on [original; mirrored]
-        rows, `lt_ppo_loss_opts` for a log-type std or per-minibatch statistics, else `lt_ppo_loss`.  `lt_ppo_lr_rule` then applies the
+        gradient maxima acc[20], acc[21]: with `sym_args` = (entry, action table, mirror coefficient) `lt_ppo_loss_sym` on [original; mirrored]
+        rows of both networks or `lt_ppo_loss_mirror` on those rows of the actor and the m original rows of the critic, `lt_ppo_loss_opts` for a log-type std or per-minibatch statistics, else `lt_ppo_loss`.  `lt_ppo_lr_rule` then applies the
         adaptive-KL rule (ppo.py:273-281) to the device learning rate, adds the step's statistics to `c.stats` and writes d loss / d std
         into its slot of the bucket."""
         dev = c.dev
         dmu = torch.empty_like(mu)
-        dvalue = torch.empty(mu.shape[0], 1, device=dev, dtype=torch.float32)
+        dvalue = torch.empty(value.shape[0], 1, device=dev, dtype=torch.float32)
         acc = torch.empty(24, device=dev, dtype=torch.float32)
         out = torch.empty(24, device=dev, dtype=torch.float32)
         rows = (mu, c.std_c, value, *c.small, idx, m, c.a_dim, float(self.clip_param), float(self.value_loss_coef), float(self.entropy_coef),
                 int(bool(self.use_clipped_value_loss)))
         opts = (int(c.std_is_log), None if c.mb_stats is None else c.mb_stats[i])
         if sym_args is not None:
-            _abi.call("lt_ppo_loss_sym", *rows, *opts, *sym_args, dmu, dvalue, acc, out, c.state[4:5], c.stream)
+            _abi.call(sym_args[0], *rows, *opts, *sym_args[1:], dmu, dvalue, acc, out, c.state[4:5], c.stream)
         elif c.std_is_log or c.mb_stats is not None:
             _abi.call("lt_ppo_loss_opts", *rows, *opts, dmu, dvalue, acc, out, c.stream)
         else:
@@ -427,15 +443,19 @@ class PPO:
         n = self.num_learning_epochs * self.num_mini_batches
         return sv / n, ss / n, se / n, None, read[4] / n if state.numel() == 5 else None
 
-    def _symmetry_tables(self, dev, obs_dim: int, critic_obs_dim: int, a_dim: int):
+    def _symmetry_tables(self, dev, obs_dim: int, critic_obs_dim: int | None, a_dim: int):
         """The packed device tables (policy rows, critic rows, actions) of the env's mirror map, checked on the host by
-        `lt_sym_table_pack` and built once per PPO object."""
+        `lt_sym_table_pack` and built once per PPO object.  `critic_obs_dim` None: the critic sees no mirrored row (the update without
+        augmentation), its table is not packed and stands as None."""
         if self._sym_tables is None:
             from .symmetry import mirror_tables
 
             tables = mirror_tables(self.symmetry["_env"])
             packed = []
             for kind, width in (("policy", obs_dim), ("critic", critic_obs_dim), ("action", a_dim)):
+                if width is None:
+                    packed.append(None)
+                    continue
                 src, sign = tables.of(kind)
                 if src.numel() != width:
                     raise ValueError(f"symmetry_cfg: the env's {kind} mirror table covers {src.numel()} columns, the storage's rows have {width}")
@@ -458,19 +478,24 @@ class PPO:
         return out
 
     def _symmetry_direct_ok(self) -> bool:
-        """Whether `_direct_update` serves this symmetric update: augmentation by this package's `mirror_go1` (the kernels mirror through
-        its tables) on the conditions the direct update has without symmetry, on one rank.  Everything else runs `_symmetry_update`."""
+        """Whether `_direct_update` serves this symmetric update: any of the four modes with this package's `mirror_go1` (the kernels
+        mirror through its tables) on the conditions the direct update has without symmetry, on one rank; without augmentation the two
+        networks differ in their row counts, which the fused backward pass alone serves.  Everything else runs `_symmetry_update`."""
         from .fused_loss import std_param
         from .symmetry import mirror_go1
 
         sym = self.symmetry
-        if not (sym["use_data_augmentation"] and sym["data_augmentation_func"] is mirror_go1 and self.dist.world_size == 1):
+        if not (sym["data_augmentation_func"] is mirror_go1 and self.dist.world_size == 1):
             return False
         if not (self.direct_update and self._flat_adam is not None and self._fused_loss_ok(None) and std_param(self.actor_critic)[0].requires_grad):
             return False
         if self.normalize_advantage_per_mini_batch and (self.storage.num_envs * self.storage.num_steps) // self.num_mini_batches < 2:
             return False
-        return self._packed_pair() is not None
+        pair = self._packed_pair()
+        if pair is None or sym["use_data_augmentation"]:
+            return pair is not None
+        dev = self.storage.observations.device
+        return pair._fused_backward_possible(*(torch.empty(0, net.in_features, device=dev) for net in (pair.a, pair.b)))
 
     def _symmetry_update(self):
         """The reference's update with its `symmetry_cfg` branch as a chain of torch ops (ppo.py:216-337), on any device: per-minibatch
