@@ -2064,6 +2064,25 @@ void lt_oracle_tactile_format_u(const lt_cfg* cfg, int format, const float* forc
   memcpy(out + nt, ch[second], sizeof(float) * nt);
 }
 
+/* threshold uniforms of one term instance of env `ekey`: stream RS_TACTILE_THR + 0x40 term + taxel / 4 on the startup key, so
+ * they never change with the step; ut: [221 + 3] (whole Philox blocks) */
+static void tactile_threshold_uniforms(const lt_cfg* cfg, uint32_t ekey, int term, float* ut) {
+  float u[4];
+  for (int t = 0; t < LT_TAXEL_ROWS * LT_TAXEL_COLS; t += 4) {
+    lt_rng4(cfg->seed, ekey, ~(uint64_t)0, RS_TACTILE_THR + 0x40u * (uint32_t)term + (uint32_t)(t >> 2), u);
+    memcpy(ut + t, u, sizeof(u));
+  }
+}
+
+void lt_oracle_tactile_thresholds(const lt_cfg* cfg, int term, int64_t env, float* out) {
+  float ut[LT_TAXEL_ROWS * LT_TAXEL_COLS + 4];
+  tactile_threshold_uniforms(cfg, EKEY(cfg, env), term, ut);
+  for (int t = 0; t < LT_TAXEL_ROWS * LT_TAXEL_COLS; ++t) {  /* the expression of lt_oracle_tactile_channels_u (:126) */
+    const float n_min = -cfg->tactile_threshold_noise, n_max = cfg->tactile_threshold_noise;
+    out[t] = cfg->tactile_threshold + (ut[t] * (n_max - n_min) + n_min);
+  }
+}
+
 static void tactile_pass(const lt_cfg* cfg, void* arena, const lt_layout* L) {
   enum { NT = LT_TAXEL_ROWS * LT_TAXEL_COLS };
   const uint64_t step = (uint64_t)((int64_t*)((char*)arena + L->off_counters))[0];
@@ -2074,6 +2093,7 @@ static void tactile_pass(const lt_cfg* cfg, void* arena, const lt_layout* L) {
     real x[4], y[4], f[4], forces_r[NT];
     float forces[NT];                 /* what the f32 TactileSignals classes read (lt_oracle_tactile_channels_u) */
     float ut[NT + 4], U[7][NT], u[4]; /* Philox uniforms */
+    const uint32_t ekey = EKEY(cfg, e);
     for (int k = 0; k < 4; ++k) {
       x[k] = lt_quad(arena, L, LT_F_PLATE_SAMPLES, 0)[e * 4 + k];
       y[k] = lt_quad(arena, L, LT_F_PLATE_SAMPLES, 1)[e * 4 + k];
@@ -2085,11 +2105,11 @@ static void tactile_pass(const lt_cfg* cfg, void* arena, const lt_layout* L) {
       if (term > 0 && !(cfg->tactile_aux_groups & term)) continue;
       /* stream ids: thresholds RS_TACTILE_THR + 0x40 term + taxel / 4 (startup key); per step RS_TACTILE + 0x200 term + 2 taxel
        * -> (drop, add, drop force, add force), + 1 -> (force noise, too-small repair, level noise, -) */
-      for (int t = 0; t < NT; t += 4) { lt_rng4(cfg->seed, EKEY(cfg, e), ~(uint64_t)0, RS_TACTILE_THR + 0x40u * (uint32_t)term + (uint32_t)(t >> 2), u); memcpy(ut + t, u, sizeof(u)); }
+      tactile_threshold_uniforms(cfg, ekey, term, ut);
       for (int t = 0; t < NT; ++t) {
-        lt_rng4(cfg->seed, EKEY(cfg, e), step, RS_TACTILE + 0x200u * (uint32_t)term + 2u * (uint32_t)t, u);
+        lt_rng4(cfg->seed, ekey, step, RS_TACTILE + 0x200u * (uint32_t)term + 2u * (uint32_t)t, u);
         U[0][t] = u[0]; U[2][t] = u[1]; U[1][t] = u[2]; U[3][t] = u[3];
-        lt_rng4(cfg->seed, EKEY(cfg, e), step, RS_TACTILE + 0x200u * (uint32_t)term + 2u * (uint32_t)t + 1u, u);
+        lt_rng4(cfg->seed, ekey, step, RS_TACTILE + 0x200u * (uint32_t)term + 2u * (uint32_t)t + 1u, u);
         U[4][t] = u[0]; U[5][t] = u[1]; U[6][t] = u[2];
       }
       const float* u8[8] = {ut, U[0], U[1], U[2], U[3], U[4], U[5], U[6]};
@@ -2162,6 +2182,14 @@ int lt_oracle_eval_terms(const lt_cfg* cfg, void* arena) {
   uint64_t step = (uint64_t)counters(arena, &L)[0];
   int nz = any_nonzero(arena, &L);
   for (int64_t e = 0; e < L.n; ++e) step_one(cfg, arena, &L, NULL, e, step, nz, LT_ORACLE_MODE_TERMS);
+  return 0;
+}
+
+/* the tactile pass alone on the arena as it stands (plate samples, counters[0]): what lt_env_tactile_update does on the device */
+int lt_oracle_tactile_update(const lt_cfg* cfg, void* arena) {
+  lt_layout L;
+  lt_layout_init(&L, cfg->num_envs, lt_oracle_obs_dim(cfg), cfg->tactile_enabled);
+  if (cfg->tactile_enabled) tactile_pass(cfg, arena, &L);
   return 0;
 }
 

@@ -55,6 +55,10 @@ int64_t lt_oracle_state_bytes(const lt_cfg* cfg);
 int lt_oracle_reset_all(const lt_cfg* cfg, void* arena);
 int lt_oracle_step(const lt_cfg* cfg, void* arena, const float* actions, int nthreads);
 int lt_oracle_eval_terms(const lt_cfg* cfg, void* arena);
+/* arena twin of lt_env_tactile_update: the tactile pass alone, from the arena's plate samples and step counter */
+int lt_oracle_tactile_update(const lt_cfg* cfg, void* arena);
+/* per-(env, taxel) contact thresholds [221] of term instance `term` (0 tactile, 1 original, 2 processed), as that pass draws them */
+void lt_oracle_tactile_thresholds(const lt_cfg* cfg, int term, int64_t env, float* out);
 
 /* term-level entry points (golden-vector tests) */
 void lt_oracle_process_action(const lt_cfg* cfg, const float a[12], float raw[12], float prev[12], float prev2[12]);

@@ -105,3 +105,7 @@ class OracleEnv:
 
     def eval_terms(self):
         self.lib.lt_oracle_eval_terms(ctypes.byref(self.cfg), self.ptr)
+
+    def tactile_update(self):
+        """The tactile pass alone on the arena as it stands (the twin of LocoTouchVecEnv.tactile_update)."""
+        self.lib.lt_oracle_tactile_update(ctypes.byref(self.cfg), self.ptr)
