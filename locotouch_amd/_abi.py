@@ -145,6 +145,8 @@ HEADERS = (
     ("PPO_MIRROR", "lt_ppo_mirror.h", False, (), ()),  # the loss of the mirror-loss-only (and logging-only) symmetric update
     ("MLP_ROWS", "lt_mlp_rows.h", True, (), ()),  # the pair forward and backward chain with a row count per network
     ("ENCODER", "lt_encoder.h", False, ("lt_encoder_forward_launches",), ("lt_encoder_desc", "lt_encoder_net")),  # the encoder in front of an ActorCriticEncoder's stacks
+    ("RNN_ENCODER", "lt_rnn_encoder.h", False, ("lt_rnn_encoder_forward_launches",),
+     ("lt_rnn_encoder_memory", "lt_rnn_encoder_net")),  # an ActorCriticRNNEncoder's rollout: the memory step on strided rows, the encoder on the memory's output
 )
 
 

@@ -1,4 +1,4 @@
-from locotouch_amd.rl.modules import ActorCritic, ActorCriticEncoder, ActorCriticRecurrent
+from locotouch_amd.rl.modules import ActorCritic, ActorCriticEncoder, ActorCriticRecurrent, ActorCriticRNNEncoder
 from locotouch_amd.rl.normalizer import EmpiricalNormalization
 
-__all__ = ["ActorCritic", "ActorCriticRecurrent", "ActorCriticEncoder", "EmpiricalNormalization"]
+__all__ = ["ActorCritic", "ActorCriticRecurrent", "ActorCriticEncoder", "ActorCriticRNNEncoder", "EmpiricalNormalization"]

@@ -659,6 +659,9 @@ class _PolicyExport(torch.nn.Module):
         super().__init__()
         import copy
 
+        if type(actor_critic).__name__ == "ActorCriticRNNEncoder":
+            raise NotImplementedError("export: ActorCriticRNNEncoder is not served (its memory reads the row's tail columns and an encoder "
+                                      "stands between it and the actor; this module is rnn -> actor, ActorCriticRecurrent's shape)")
         self.is_recurrent = bool(getattr(actor_critic, "is_recurrent", False))
         self.is_lstm = False
         if self.is_recurrent:

@@ -1,5 +1,6 @@
 // The encoder in front of an ActorCriticEncoder's stacks (include/lt_encoder.h): out[r] = [ obs[r, :flat_dim] | enc(obs[r, -enc_in:]) ]
-// for one or two networks in ONE launch.
+// for one or two networks in ONE launch - and the same with the encoder's input rows read from a second array, the output of a memory
+// (include/lt_rnn_encoder.h: out[r] = [ obs[r, :flat_dim] | enc(h[r, :enc_in]) ]; only where the tail columns are staged from differs).
 //
 // Shape: n = num_envs rows in the rollout (4096), a minibatch's rows in the update (some 24 k); the reference encoder is
 // 78 -> 256 -> 128 -> 64 -> 64, 65 k MACs per row, 260 KB of weights - more than a CU's LDS.  A workgroup of four waves owns a ROW BLOCK
@@ -30,7 +31,9 @@
 #include "lt_env.h"
 #include "lt_host_check.h"
 #include "lt_internal.h"
+#include "lt_rnn_encoder.h"
 
+static_assert(LT_RNN_ENCODER_MAX_LAYERS == LT_ENCODER_MAX_LAYERS, "lt_rnn_encoder.h states its layer limit as lt_encoder.h's");
 static_assert(LT_ENCODER_MAX_LAYERS == LT_MLP_MAX_LAYERS, "lt_encoder.h states its layer limit as lt_mlp's");
 
 namespace {
@@ -42,6 +45,7 @@ constexpr int kLdsBytes = 160 * 1024;
 
 struct EncNet {
   const float* obs; long long obs_stride;
+  const float* h; long long h_stride;  // non-null: the encoder reads h[r, :enc_in] instead of the tail columns of obs
   const float* w[kMaxL]; const float* b[kMaxL];
   float* out; float* acts[kMaxL];
   int obs_dim, flat_dim, L;
@@ -122,7 +126,8 @@ __global__ __launch_bounds__(256) void lt_encoder_kernel(const EncArgs a) {
   }
   {
     const int K = p.dims[0];
-    stage<16, float>(p.obs + (long long)r0 * p.obs_stride + (p.obs_dim - K), p.obs_stride, rows, K, buf[0], p.stride[0], 16 * nsub, round_up(K, 16), tid);
+    const float* src = p.h ? p.h + (long long)r0 * p.h_stride : p.obs + (long long)r0 * p.obs_stride + (p.obs_dim - K);
+    stage<16, float>(src, p.h ? p.h_stride : p.obs_stride, rows, K, buf[0], p.stride[0], 16 * nsub, round_up(K, 16), tid);
   }
 
   // ---- 2. the layers
@@ -195,11 +200,13 @@ __global__ __launch_bounds__(256) void lt_encoder_kernel(const EncArgs a) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
-int check_desc(const char* fn, const char* who, const lt_encoder_desc* d) {
+// `tail`: the encoder reads the tail columns of the row (false: a second array, whose width the row does not bound)
+int check_desc(const char* fn, const char* who, const lt_encoder_desc* d, bool tail = true) {
   if (!d) return refuse(fn, who, "", "non-null");
   if (d->num_layers < 1 || d->num_layers > kMaxL) return refuse(fn, who, ".num_layers", "in [1, LT_ENCODER_MAX_LAYERS]");
   if (d->obs_dim < 1) return refuse(fn, who, ".obs_dim", "at least 1");
-  if (d->enc_in < 1 || d->enc_in > LT_ENCODER_MAX_WIDTH || d->enc_in > d->obs_dim)
+  if (!tail && (d->enc_in < 1 || d->enc_in > LT_ENCODER_MAX_WIDTH)) return refuse(fn, who, ".enc_in", "in [1, LT_ENCODER_MAX_WIDTH]");
+  if (tail && (d->enc_in < 1 || d->enc_in > LT_ENCODER_MAX_WIDTH || d->enc_in > d->obs_dim))
     return refuse(fn, who, ".enc_in", "in [1, LT_ENCODER_MAX_WIDTH] and at most obs_dim");
   if (d->flat_dim < 0 || d->flat_dim > d->obs_dim) return refuse(fn, who, ".flat_dim", "in [0, obs_dim]");
   for (int l = 0; l < d->num_layers; ++l)
@@ -259,6 +266,7 @@ int check_net(const char* fn, const char* who, const lt_encoder_net* net, int n)
 void set_net(EncNet& r, const lt_encoder_net* net) {
   const lt_encoder_desc& d = net->desc;
   r.obs = net->obs; r.obs_stride = net->obs_stride; r.out = net->out;
+  r.h = nullptr; r.h_stride = 0;
   r.obs_dim = d.obs_dim; r.flat_dim = d.flat_dim; r.L = d.num_layers;
   r.act = d.activation; r.final_act = d.final_activation;
   r.dims[0] = d.enc_in;
@@ -269,6 +277,43 @@ void set_net(EncNet& r, const lt_encoder_net* net) {
     r.dims[l + 1] = used ? d.dims[l] : 0;
     if (used && lds_stride(r.dims[l]) > r.stride[l & 1]) r.stride[l & 1] = lds_stride(r.dims[l]);  // layer l reads buffer l & 1
   }
+}
+
+// the widths of an lt_rnn_encoder_net as the descriptor the kernel's checks and plan read
+lt_encoder_desc desc_of(const lt_rnn_encoder_net* net) {
+  lt_encoder_desc d;
+  d.obs_dim = net->obs_dim; d.flat_dim = net->flat_dim; d.enc_in = net->enc_in; d.num_layers = net->num_layers;
+  for (int l = 0; l < kMaxL; ++l) d.dims[l] = net->dims[l];
+  d.activation = net->activation; d.final_activation = net->final_activation;
+  return d;
+}
+
+// checks an lt_rnn_encoder_net and hands it back as the lt_encoder_net of the same widths and operands (its obs tail is never read)
+int check_rnn_net(const char* fn, const char* who, const lt_rnn_encoder_net* net, int n, lt_encoder_net& e) {
+  if (!net) return refuse(fn, who, "", "non-null");
+  e.desc = desc_of(net);
+  if (const int rc = check_desc(fn, who, &e.desc, false)) return rc;
+  if (net->obs_stride < net->obs_dim) return refuse(fn, who, ".obs_stride", "at least obs_dim");
+  if (net->h_stride < net->enc_in || net->h_stride % 4 != 0) return refuse(fn, who, ".h_stride", "at least enc_in and a multiple of 4");
+  if (const int rc = check_ptrs(fn, who, {{".obs", net->obs, 4}, {".h", net->h, 16}, {".out", net->out, 4}})) return rc;
+  const int L = net->num_layers;
+  for (int l = 0; l < kMaxL; ++l) {
+    char wn[32], bn[32], an[32];
+    snprintf(wn, sizeof wn, ".weight[%d]", l);
+    snprintf(bn, sizeof bn, ".bias[%d]", l);
+    snprintf(an, sizeof an, ".acts[%d]", l);
+    if (l < L)
+      if (const int rc = check_ptrs(fn, who, {{wn, net->weight[l], 4}, {bn, net->bias[l], 4}})) return rc;
+    if (net->acts[l]) return refuse(fn, who, an, "NULL (this launch has the inference form alone)");
+    e.weight[l] = l < L ? net->weight[l] : nullptr; e.bias[l] = l < L ? net->bias[l] : nullptr; e.acts[l] = nullptr;
+  }
+  const long long ow = net->flat_dim + net->dims[L - 1];
+  if (overlaps(net->out, (long long)n * ow, net->obs, (long long)(n - 1) * net->obs_stride + net->obs_dim))
+    return refuse(fn, who, ".out", "a buffer that does not overlap obs");
+  if (overlaps(net->out, (long long)n * ow, net->h, (long long)(n - 1) * net->h_stride + net->enc_in))
+    return refuse(fn, who, ".out", "a buffer that does not overlap h");
+  e.obs = net->obs; e.obs_stride = net->obs_stride; e.out = net->out;
+  return LT_OK;
 }
 
 int cu_count() {
@@ -331,6 +376,39 @@ int lt_encoder_forward(const lt_encoder_net* actor, const lt_encoder_net* critic
   const int nets = critic ? 2 : 1;
   set_net(a.net[0], actor);
   set_net(a.net[1], critic ? critic : actor);
+  a.n = n;
+  const int lds = plan(a, nets);
+  if (lds <= 0) return refuse(fn, "the layers do not fit the LDS");
+  if (const int e = lt_ensure_dynamic_lds((const void*)lt_encoder_kernel, kLdsBytes)) { lt_set_error(hipGetErrorString((hipError_t)e)); return LT_EHIP; }
+  hipLaunchKernelGGL(lt_encoder_kernel, dim3((unsigned)((n + a.RB - 1) / a.RB), (unsigned)nets), dim3(256), lds, (hipStream_t)stream, a);
+  return launch_status(fn);
+}
+
+int lt_rnn_encoder_forward_launches(const lt_rnn_encoder_net* actor, const lt_rnn_encoder_net* critic) {
+  const char* fn = "lt_rnn_encoder_forward_launches";
+  if (!actor) return refuse(fn, "actor", "", "non-null");
+  const lt_encoder_desc da = desc_of(actor);
+  if (const int rc = check_desc(fn, "actor", &da, false)) return rc;
+  if (critic) {
+    const lt_encoder_desc dc = desc_of(critic);
+    if (const int rc = check_desc(fn, "critic", &dc, false)) return rc;
+  }
+  return 1;
+}
+
+int lt_rnn_encoder_forward(const lt_rnn_encoder_net* actor, const lt_rnn_encoder_net* critic, int n, void* stream) {
+  const char* fn = "lt_rnn_encoder_forward";
+  if (n < 1 || n > 16 * 65535) return refuse(fn, "", "n", "in [1, 16 * 65535]");
+  lt_encoder_net ea, ec;
+  if (const int rc = check_rnn_net(fn, "actor", actor, n, ea)) return rc;
+  if (critic)
+    if (const int rc = check_rnn_net(fn, "critic", critic, n, ec)) return rc;
+  EncArgs a;
+  const int nets = critic ? 2 : 1;
+  set_net(a.net[0], &ea);
+  set_net(a.net[1], critic ? &ec : &ea);
+  a.net[0].h = actor->h; a.net[0].h_stride = actor->h_stride;
+  a.net[1].h = critic ? critic->h : actor->h; a.net[1].h_stride = critic ? critic->h_stride : actor->h_stride;
   a.n = n;
   const int lds = plan(a, nets);
   if (lds <= 0) return refuse(fn, "the layers do not fit the LDS");

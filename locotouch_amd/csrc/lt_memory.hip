@@ -8,6 +8,7 @@
 #include "lt_memory_cells.h"
 #include "lt_memory_seq.h"
 #include "lt_memory_tile.h"
+#include "lt_rnn_encoder.h"
 
 namespace {
 
@@ -44,6 +45,23 @@ int check_seq_grad(const char* fn, const char* who, const lt_memory_seq_grad* n)
                               {".dgates", n->dgates, 16}, {".dc_carry", n->dc_carry, 16}});
 }
 
+// one step of both memories, the x rows of network k xs_k floats apart (validated operands)
+int launch_step(const lt_memory_net* actor, const lt_memory_net* critic, long long xs_a, long long xs_c, const uint8_t* dones, int N, int H,
+                void* stream) {
+  const lt_memory_net* nets[2] = {actor, critic};
+  const long long xs[2] = {xs_a, xs_c};
+  StepArgs<2> a;
+  for (int k = 0; k < 2; ++k) {
+    NetArgs<2>& r = a.net[k];
+    const lt_memory_net* n = nets[k];
+    set_weights(r, n, H);
+    r.x = n->x; r.XS = xs[k]; r.s_in[0] = n->h_in; r.s_in[1] = n->c_in; r.s_out[0] = n->h_out; r.s_out[1] = n->c_out;
+    r.saved[0] = n->saved_h; r.saved[1] = n->saved_c;
+  }
+  a.dones = dones; a.N = N; a.H = H;
+  return launch_steps<LstmCell, false>(a, 1, stream, [](int) {});
+}
+
 }  // namespace
 
 extern "C" {
@@ -53,17 +71,25 @@ int lt_memory_step(const lt_memory_net* actor, const lt_memory_net* critic, cons
   if (const int rc = check_sizes(fn, "N", N, H)) return rc;
   if (const int rc = check_net(fn, "actor", actor, H)) return rc;
   if (const int rc = check_net(fn, "critic", critic, H)) return rc;
-  const lt_memory_net* nets[2] = {actor, critic};
-  StepArgs<2> a;
+  return launch_step(actor, critic, actor->I, critic->I, dones, N, H, stream);
+}
+
+// include/lt_rnn_encoder.h: the same step with each network's x rows x_stride floats apart
+int lt_memory_step_strided(const lt_rnn_encoder_memory* actor, const lt_rnn_encoder_memory* critic, const uint8_t* dones, int N, int H,
+                           void* stream) {
+  const char* fn = "lt_memory_step_strided";
+  if (const int rc = check_sizes(fn, "N", N, H)) return rc;
+  const lt_rnn_encoder_memory* src[2] = {actor, critic};
+  const char* who[2] = {"actor", "critic"};
+  lt_memory_net nets[2];
   for (int k = 0; k < 2; ++k) {
-    NetArgs<2>& r = a.net[k];
-    const lt_memory_net* n = nets[k];
-    set_weights(r, n, H);
-    r.x = n->x; r.s_in[0] = n->h_in; r.s_in[1] = n->c_in; r.s_out[0] = n->h_out; r.s_out[1] = n->c_out;
-    r.saved[0] = n->saved_h; r.saved[1] = n->saved_c;
+    const lt_rnn_encoder_memory* m = src[k];
+    if (!m) return refuse(fn, who[k], "", "non-null");
+    nets[k] = {m->x, m->I, m->w_ih, m->w_hh, m->b_ih, m->b_hh, m->h_in, m->c_in, m->h_out, m->c_out, m->saved_h, m->saved_c};
+    if (const int rc = check_net(fn, who[k], &nets[k], H)) return rc;
+    if (m->x_stride < m->I) return refuse(fn, who[k], ".x_stride", "at least I");
   }
-  a.dones = dones; a.N = N; a.H = H;
-  return launch_steps<LstmCell, false>(a, 1, stream, [](int) {});
+  return launch_step(&nets[0], &nets[1], actor->x_stride, critic->x_stride, dones, N, H, stream);
 }
 
 int lt_memory_finish(const float* h_a, const float* c_a, const float* h_c, const float* c_c, const uint8_t* dones, int N, int H,

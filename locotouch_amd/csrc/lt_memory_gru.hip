@@ -13,6 +13,7 @@
 #include "lt_memory_cells.h"
 #include "lt_memory_gru.h"
 #include "lt_memory_tile.h"
+#include "lt_rnn_encoder.h"
 
 namespace {
 
@@ -45,6 +46,22 @@ int check_seq_grad(const char* fn, const char* who, const lt_memory_gru_seq_grad
                               {".dig", n->dig, 16}, {".dhg", n->dhg, 16}, {".dh_carry", n->dh_carry, 16}});
 }
 
+// one step of both memories, the x rows of network k xs_k floats apart (validated operands)
+int launch_step(const lt_memory_gru_net* actor, const lt_memory_gru_net* critic, long long xs_a, long long xs_c, const uint8_t* dones, int N,
+                int H, void* stream) {
+  const lt_memory_gru_net* nets[2] = {actor, critic};
+  const long long xs[2] = {xs_a, xs_c};
+  StepArgs<1> a;
+  for (int k = 0; k < 2; ++k) {
+    NetArgs<1>& r = a.net[k];
+    const lt_memory_gru_net* n = nets[k];
+    set_weights(r, n, H);
+    r.x = n->x; r.XS = xs[k]; r.s_in[0] = n->h_in; r.s_out[0] = n->h_out; r.saved[0] = n->saved_h;
+  }
+  a.dones = dones; a.N = N; a.H = H;
+  return launch_steps<GruCell, false>(a, 1, stream, [](int) {});
+}
+
 }  // namespace
 
 extern "C" {
@@ -54,16 +71,26 @@ int lt_memory_gru_step(const lt_memory_gru_net* actor, const lt_memory_gru_net* 
   if (const int rc = check_sizes(fn, "N", N, H)) return rc;
   if (const int rc = check_net(fn, "actor", actor, H)) return rc;
   if (const int rc = check_net(fn, "critic", critic, H)) return rc;
-  const lt_memory_gru_net* nets[2] = {actor, critic};
-  StepArgs<1> a;
+  return launch_step(actor, critic, actor->I, critic->I, dones, N, H, stream);
+}
+
+// include/lt_rnn_encoder.h: the same step with each network's x rows x_stride floats apart
+int lt_memory_gru_step_strided(const lt_rnn_encoder_memory* actor, const lt_rnn_encoder_memory* critic, const uint8_t* dones, int N, int H,
+                               void* stream) {
+  const char* fn = "lt_memory_gru_step_strided";
+  if (const int rc = check_sizes(fn, "N", N, H)) return rc;
+  const lt_rnn_encoder_memory* src[2] = {actor, critic};
+  const char* who[2] = {"actor", "critic"};
+  lt_memory_gru_net nets[2];
   for (int k = 0; k < 2; ++k) {
-    NetArgs<1>& r = a.net[k];
-    const lt_memory_gru_net* n = nets[k];
-    set_weights(r, n, H);
-    r.x = n->x; r.s_in[0] = n->h_in; r.s_out[0] = n->h_out; r.saved[0] = n->saved_h;
+    const lt_rnn_encoder_memory* m = src[k];
+    if (!m) return refuse(fn, who[k], "", "non-null");
+    nets[k] = {m->x, m->I, m->w_ih, m->w_hh, m->b_ih, m->b_hh, m->h_in, m->h_out, m->saved_h};
+    if (const int rc = check_net(fn, who[k], &nets[k], H)) return rc;
+    if (m->c_in || m->c_out || m->saved_c) return refuse(fn, who[k], ".c_in / .c_out / .saved_c", "NULL (a GRU's state is h alone)");
+    if (m->x_stride < m->I) return refuse(fn, who[k], ".x_stride", "at least I");
   }
-  a.dones = dones; a.N = N; a.H = H;
-  return launch_steps<GruCell, false>(a, 1, stream, [](int) {});
+  return launch_step(&nets[0], &nets[1], actor->x_stride, critic->x_stride, dones, N, H, stream);
 }
 
 int lt_memory_gru_finish(const float* h_a, const float* h_c, const uint8_t* dones, int N, int H, float* out_h_a, float* out_h_c, void* stream) {

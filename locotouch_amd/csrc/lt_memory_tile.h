@@ -49,6 +49,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int NS> struct NetArgs {
   const float* x; const float* w_ih; const float* w_hh; const float* b_ih; const float* b_hh; const float* s_in[NS];
   float* s_out[NS]; float* saved[NS];
+  long long XS;    // floats between two x rows (I: contiguous rows; more: the rows are columns of wider ones, include/lt_rnn_encoder.h)
   int I, IP, KP;  // IP: I rounded up to 16 (the x side's k blocks; the panel holds zeros in [I, IP)); KP: LDS row stride in floats
 };
 template <int NS> struct StepArgs { NetArgs<NS> net[2]; const uint8_t* dones; int N, H, RB; };
@@ -65,7 +66,7 @@ __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m *
 __host__ __device__ inline int panel_stride(int I, int H) { return round_up(I, 16) + H + 8; }
 
 // The B operand of k block `blk` for lane (row, q): x[row][16 blk + 4 q .. + 3] (zeros past I; rows are only 4-byte aligned unless
-// `xvec`), or behind the x side's blocks where(done, 0, h[row][...]).
+// `xvec`: x, I and the row stride all multiples of 16 bytes), or behind the x side's blocks where(done, 0, h[row][...]).
 __device__ __forceinline__ f32x4 load_b(const float* __restrict__ xrow, const float* __restrict__ hrow, int blk, int q, int I, int xblks, bool xvec,
                                         bool done) {
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -144,14 +145,14 @@ __global__ __launch_bounds__(256) void lt_memory_step_kernel(const step_args<Cel
 
   // ---- 2. the row block, 16 rows per wave and pass
   const int xblks = IP / 16, nblk = xblks + H / 16;
-  const bool xvec = (I & 3) == 0 && ((uintptr_t)p.x & 15) == 0;
+  const bool xvec = (I & 3) == 0 && (p.XS & 3) == 0 && ((uintptr_t)p.x & 15) == 0;
   const int nsub = (r1 - r0 + 15) / 16;
   for (int s = wave; s < nsub; s += 4) {
     const int row = r0 + 16 * s + i;  // the row this lane feeds as the B operand, and (n = i) the row it owns in the epilogue
     const bool row_ok = row < r1;
     const int rc = row_ok ? row : r0;  // (a clamped lane computes a column of D nobody stores)
     const bool done = a.dones && a.dones[rc] != 0;
-    const float* xrow = p.x + (long long)rc * I;
+    const float* xrow = p.x + (long long)rc * p.XS;
     const float* hrow = p.s_in[0] + (long long)rc * H;
     // the epilogue's operand, requested now: the last state tensor at (row, units j0 + q * MT .. + MT - 1)
     float prev[MT];
@@ -417,7 +418,7 @@ template <class A> int allow_lds(kernel_fn<A> kernel) {
 // the weights and widths of one network (every net struct of the three headers names them alike)
 template <int NS, class Net> void set_weights(NetArgs<NS>& r, const Net* n, int H) {
   r.w_ih = n->w_ih; r.w_hh = n->w_hh; r.b_ih = n->b_ih; r.b_hh = n->b_hh;
-  r.I = n->I; r.IP = round_up(n->I, 16); r.KP = panel_stride(n->I, H);
+  r.I = n->I; r.IP = round_up(n->I, 16); r.KP = panel_stride(n->I, H); r.XS = n->I;
 }
 
 // T step launches of one plan: picks the unit tile for a (weights, N and H set), allows its kernel the LDS, then `at(t)` puts step t's

@@ -50,9 +50,10 @@ def make_net(desc, obs: torch.Tensor, weights, biases, out: torch.Tensor, acts=N
     return net
 
 
-def describe(enc: nn.Module, obs_dim: int, flat_dim: int):
+def describe(enc: nn.Module, obs_dim: int, flat_dim: int, tail: bool = True):
     """(LtEncoderDesc, [Linear...]) of an `MLP` encoder module (rl/models.py) reading the last `in_features` of `obs_dim` columns;
-    ValueError naming the reason for a module the kernel does not serve."""
+    ValueError naming the reason for a module the kernel does not serve.  `tail=False`: the encoder reads another array than the row
+    (`RnnEncoderPair`), so the library's check of the widths is the caller's to ask."""
     mods = list(enc.model) if hasattr(enc, "model") else list(enc)
     linears = [m for m in mods if isinstance(m, nn.Linear)]
     if not linears or any(m.bias is None or m.weight.dtype != torch.float32 or not m.weight.is_contiguous() for m in linears):
@@ -83,7 +84,7 @@ def describe(enc: nn.Module, obs_dim: int, flat_dim: int):
         raise ValueError("the encoder has more than LT_ENCODER_MAX_LAYERS layers")
     act = C[_ACT_IDS[next(iter(acts))]] if acts else C["LT_ACT_ELU"]  # (a single Linear has no hidden activation: any served id)
     desc = make_desc(obs_dim, flat_dim, linears[0].in_features, [m.out_features for m in linears], act, final)
-    why = validate(desc)
+    why = validate(desc) if tail else None
     if why is not None:
         raise ValueError(why)
     return desc, linears
@@ -125,3 +126,53 @@ class EncoderPair:
             c = make_net(self.c_desc, critic_obs, [m.weight for m in self.c_linears], [m.bias for m in self.c_linears], critic_out, c_acts)
         _abi.call("lt_encoder_forward", a, c, n, _abi.stream(obs.device))
         return a_acts, c_acts
+
+
+class RnnEncoderPair:
+    """The encoders of an `ActorCriticRNNEncoder` as one launch (include/lt_rnn_encoder.h): per network
+    `[ obs[:, :flat_dim] | enc(h) ]` with `h` the output rows of the network's memory.  Both networks have an encoder."""
+
+    def __init__(self, ac, obs_dim: int, critic_obs_dim: int):
+        import ctypes
+
+        if not ac.critic_with_encoder:
+            raise ValueError("the critic has no encoder")
+        self.nets = []
+        for who, enc, mem, stack, dim, flat in (("actor", ac.actor_encoder, ac.memory_a, ac.actor, obs_dim, ac.actor_flatten_obs_dim),
+                                                ("critic", ac.critic_encoder, ac.memory_c, ac.critic, critic_obs_dim, ac.critic_flatten_obs_dim)):
+            try:
+                desc, linears = describe(enc, dim, flat, tail=False)
+            except ValueError as e:
+                raise ValueError(f"{who}_encoder: {e}") from None
+            if desc.enc_in != mem.rnn.hidden_size:
+                raise ValueError(f"the {who}'s encoder reads {desc.enc_in} columns, its memory's hidden size is {mem.rnn.hidden_size}")
+            width = flat + linears[-1].out_features
+            if width != stack[0].in_features:
+                raise ValueError(f"the {who} reads {stack[0].in_features} columns, its encoder's rows have {width}")
+            self.nets.append((desc, linears, width))
+        self.a_width, self.c_width = self.nets[0][2], self.nets[1][2]
+        lib = _abi.load()
+        if lib.lt_rnn_encoder_forward_launches(ctypes.byref(self._net(0)), ctypes.byref(self._net(1))) != 1:
+            raise ValueError(lib.lt_last_error().decode())
+
+    def _net(self, which: int, obs=None, h=None, out=None):
+        """LtRnnEncoderNet of network `which` (0 actor, 1 critic); without tensors: its widths alone."""
+        desc, linears, _ = self.nets[which]
+        net = _abi.LtRnnEncoderNet()
+        net.obs_dim, net.flat_dim, net.enc_in, net.num_layers = desc.obs_dim, desc.flat_dim, desc.enc_in, desc.num_layers
+        for l in range(desc.num_layers):
+            net.dims[l] = desc.dims[l]
+        net.activation, net.final_activation = desc.activation, desc.final_activation
+        if obs is not None:
+            net.obs, net.obs_stride, net.h, net.h_stride, net.out = obs.data_ptr(), obs.stride(0), h.data_ptr(), h.stride(0), out.data_ptr()
+            for l, m in enumerate(linears):
+                net.weight[l], net.bias[l] = m.weight.data_ptr(), m.bias.data_ptr()
+        return net
+
+    def forward(self, obs, critic_obs, h_a, h_c, out, critic_out) -> None:
+        """One launch, the inference form."""
+        for x in (obs, critic_obs, h_a, h_c):
+            if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+                raise ValueError("the encoder reads f32 rows with unit column stride")
+        _abi.call("lt_rnn_encoder_forward", self._net(0, obs, h_a, out), self._net(1, critic_obs, h_c, critic_out), obs.shape[0],
+                  _abi.stream(obs.device))

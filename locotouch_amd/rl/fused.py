@@ -71,6 +71,40 @@ def encoder_policy_unsupported(alg, normalizers: bool, use_packed_mlp: bool = Tr
     return None
 
 
+def rnn_encoder_policy_unsupported(alg, normalizers: bool, use_packed_mlp: bool = True) -> str | None:
+    """Why the fused rollout does not serve this policy behind `fused_rnn_encoder_policy` (None: it does): an `ActorCriticRNNEncoder` on a
+    GPU with an encoder on both networks, two single-layer f32 memories of one kind (LSTM or GRU) and one hidden size within
+    include/lt_memory.h's limits, encoders include/lt_rnn_encoder.h serves and stacks lt_mlp serves, on f32 observation rows, without
+    normalisers."""
+    from .encoder import RnnEncoderPair
+    from .mlp import describe
+
+    ac, st = alg.actor_critic, alg.storage
+    if torch.device(alg.device).type != "cuda":
+        return f"the device is {alg.device!r}: its kernels run on a GPU only"
+    if type(ac).__name__ != "ActorCriticRNNEncoder":
+        return f"the policy is a {type(ac).__name__}, not an ActorCriticRNNEncoder"
+    if not ac.critic_with_encoder:
+        return "the critic has no encoder (critic_encoder_hidden_dims=None): the step's launches serve two memories and two encoders"
+    if normalizers:
+        return "empirical_normalization is not served together with an RNN-encoder policy: the normaliser would have to feed the memory launch"
+    if st.observations.dtype != torch.float32:
+        return "bf16 observation rows: the memory step and the encoder launch read f32 rows"
+    why = memories_unsupported(ac.memory_a, ac.memory_c, gru_memories=True, layer_count=True)
+    if why is not None:
+        return why
+    for name, m in (("memory_a", ac.memory_a), ("memory_c", ac.memory_c)):
+        if m.rnn.weight_ih_l0.dtype != torch.float32:
+            return f"{name} is not f32"
+    if not use_packed_mlp or describe(ac.actor) is None or describe(ac.critic) is None:
+        return "the actor or the critic stack is outside lt_mlp's limits (rl/mlp.py describe), or use_packed_mlp is off"
+    try:
+        RnnEncoderPair(ac, st.observations.shape[-1], st.privileged_observations.shape[-1])
+    except ValueError as e:
+        return str(e)
+    return None
+
+
 def normalizers_unsupported(alg, actor_norm, critic_norm) -> str | None:
     """Why the fused rollout does not serve these running normalisers (None: it does): both networks' or neither's, on f32 observation
     rows, with the buffers of rl/normalizer.py on the rollout's device and one `eps` and `until` (the same launches serve both)."""
@@ -91,15 +125,21 @@ def normalizers_unsupported(alg, actor_norm, critic_norm) -> str | None:
 
 
 def rollout_unsupported(alg, obs_normalizer=None, critic_obs_normalizer=None, fused_gru_memories: bool = False,
-                        fused_encoder_policy: bool = False, use_packed_mlp: bool = True, kind_only: bool = False) -> str | None:
+                        fused_encoder_policy: bool = False, use_packed_mlp: bool = True, fused_rnn_encoder_policy: bool = False,
+                        kind_only: bool = False) -> str | None:
     """Why `FusedRollout` does not serve this policy with these normalisers and keys (None: it does), in the words its constructor raises:
     the one statement of what is served, which the runner's `_make_fused` asks as well.  The kind's reason comes first (behind the
-    encoder key nothing else is reached: its check refuses any normaliser), then the normalisers' own, which `kind_only=True` leaves out."""
+    encoder keys nothing else is reached: their checks refuse any normaliser), then the normalisers' own, which `kind_only=True` leaves out."""
     ac = alg.actor_critic
     norms = obs_normalizer is not None or critic_obs_normalizer is not None
     if fused_encoder_policy:  # (first: what the key needs is refused by name, whatever else is wrong)
         why = encoder_policy_unsupported(alg, norms, use_packed_mlp)
         return None if why is None else f"fused_encoder_policy: {why}"
+    if fused_rnn_encoder_policy:  # (the same rule for this key)
+        why = rnn_encoder_policy_unsupported(alg, norms, use_packed_mlp)
+        return None if why is None else f"fused_rnn_encoder_policy: {why}"
+    if type(ac).__name__ == "ActorCriticRNNEncoder":
+        return "FusedRollout does not serve ActorCriticRNNEncoder without fused_rnn_encoder_policy: its memories read the rows' tail columns"
     if getattr(ac, "is_recurrent", False):
         why = recurrent_unsupported(ac, alg.storage, gru_memories=fused_gru_memories)
         if why is None and obs_normalizer is not None:
@@ -361,6 +401,60 @@ class _EncoderFront(_Front):
         return out_a[:n], cobs if out_c is None else out_c[:n]
 
 
+class _RnnEncoderFront(_MemoryFront):
+    """RNN-encoder policies (`ActorCriticRNNEncoder`, behind `fused_rnn_encoder_policy=True`: the noise comes from the kernels' Philox
+    stream): a step is
+        [the cell's strided step (include/lt_rnn_encoder.h): both memories on the TAIL columns of storage slot t, read in place; reset
+         mask, saved slot and ping-pong as `_MemoryFront`'s step]
+     -> [lt_rnn_encoder_forward: [head columns of slot t | encoder of the new h] for the actor and the critic, one launch]
+     -> [policy + value on those rows] -> [env step]
+    four launches on the one stream, and the cell's `finish` behind the last step.  LSTM and GRU memories are both served by the key
+    alone.  The state handling (adopting the modules' tensors, the saved slots, `finish`) is `_MemoryFront`'s; the storage keeps the raw
+    rows, `compute_returns` stays the eager `evaluate` on the state `finish` left."""
+    launches = 2  # both memories in one launch, both encoders in one launch
+
+    def __init__(self, fr, *_):
+        from .encoder import RnnEncoderPair
+
+        super().__init__(fr, None, None, True)
+        st, n = self.alg.storage, self.env.num_envs
+        if fr.actor_mlp is None:
+            raise ValueError("fused_rnn_encoder_policy: the env has no 12 actions: the policy launch samples 12")
+        self.encoders = RnnEncoderPair(self.alg.actor_critic, st.observations.shape[-1], st.privileged_observations.shape[-1])
+        self._strided_step = "lt_memory_gru_step_strided" if self.cell.nn is torch.nn.GRU else "lt_memory_step_strided"
+        rows = n + (-n) % 64  # (the MLP launch reads whole row tiles)
+        self._enc_rows = (torch.zeros(rows, self.encoders.a_width, device=self.device), torch.zeros(rows, self.encoders.c_width, device=self.device))
+
+    def _memory_step(self, t: int, obs, cobs) -> None:
+        """Step t of both memories in one launch, each on the last `input_size` columns of its rows."""
+        ac, st = self.alg.actor_critic, self.alg.storage
+        src = self._state if t == 0 else self._hc[(t - 1) & 1]
+        dst = self._hc[t & 1]
+        lstm = len(self.cell.state) == 2
+        nets = []
+        for k, (mem, x, saved) in enumerate(((ac.memory_a, obs, st.saved_hidden_states_a), (ac.memory_c, cobs, st.saved_hidden_states_c))):
+            rnn, m = mem.rnn, _abi.LtRnnEncoderMemory()
+            if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or x.shape[1] < rnn.input_size:
+                raise ValueError("the memory step reads f32 rows with unit column stride that hold the memory's input columns")
+            m.x, m.x_stride, m.I = x.data_ptr() + 4 * (x.shape[1] - rnn.input_size), x.stride(0), rnn.input_size
+            m.w_ih, m.w_hh, m.b_ih, m.b_hh = (p.data_ptr() for p in (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0))
+            m.h_in, m.h_out, m.saved_h = src[k][0].data_ptr(), dst[k][0].data_ptr(), saved[0][t].data_ptr()
+            if lstm:
+                m.c_in, m.c_out, m.saved_c = src[k][1].data_ptr(), dst[k][1].data_ptr(), saved[1][t].data_ptr()
+            nets.append(m)
+        _abi.call(self._strided_step, nets[0], nets[1], st.dones[t - 1] if t > 0 else None, self.env.num_envs, ac.memory_a.rnn.hidden_size,
+                  _abi.stream(self.device))
+
+    def rows(self, t: int, obs, cobs, launch: bool = True):
+        """Two launches: the memories on the slot's tail columns, then the rows the two stacks read."""
+        if launch:
+            self._memory_step(t, obs, cobs)
+            h_a, h_c = self._memory_rows(t)
+            self.encoders.forward(obs, cobs, h_a, h_c, *self._enc_rows)
+        n = self.env.num_envs
+        return self._enc_rows[0][:n], self._enc_rows[1][:n]
+
+
 class FusedRollout:
     """Drives a LocoTouchVecEnv and a PPO instance through rollout steps without leaving the device (module docstring).
 
@@ -368,11 +462,12 @@ class FusedRollout:
     rows), so nothing copies observations."""
 
     def __init__(self, env, alg, use_packed_mlp: bool = True, obs_normalizer=None, critic_obs_normalizer=None,
-                 fused_gru_memories: bool = False, fused_encoder_policy: bool = False):
+                 fused_gru_memories: bool = False, fused_encoder_policy: bool = False, fused_rnn_encoder_policy: bool = False):
         from ..env import LocoTouchVecEnv
 
-        served = (alg, obs_normalizer, critic_obs_normalizer, fused_gru_memories, fused_encoder_policy, use_packed_mlp)
-        if fused_encoder_policy and (why := rollout_unsupported(*served)) is not None:  # (first: refused by name, whatever else is wrong)
+        served = (alg, obs_normalizer, critic_obs_normalizer, fused_gru_memories, fused_encoder_policy, use_packed_mlp, fused_rnn_encoder_policy)
+        keyed = fused_encoder_policy or fused_rnn_encoder_policy  # (an encoder key: its own check is the whole statement of support)
+        if keyed and (why := rollout_unsupported(*served)) is not None:  # (first: refused by name, whatever else is wrong)
             raise ValueError(why)
         if not isinstance(env, LocoTouchVecEnv):
             raise TypeError("FusedRollout drives a LocoTouchVecEnv (HIP env)")
@@ -382,7 +477,7 @@ class FusedRollout:
         self._std_buf = torch.zeros(12, device=env.device) if getattr(ac, "noise_std_type", "scalar") == "log" else None
         if self._std_buf is not None and ac.log_std.shape != (12,):
             raise ValueError("FusedRollout: log_std must hold the env's 12 actions")
-        if not fused_encoder_policy and (why := rollout_unsupported(*served, kind_only=True)) is not None:
+        if not keyed and (why := rollout_unsupported(*served, kind_only=True)) is not None:
             raise ValueError(why)
         self.env, self.alg = env, alg
         self.device = env.device
@@ -415,10 +510,10 @@ class FusedRollout:
             self.critic_mlp.set_input_format(torch.bfloat16)
             st = alg.storage
             self._tail_rows = (torch.zeros_like(st.observations[0]), torch.zeros_like(st.privileged_observations[0]))
-        if not fused_encoder_policy and (why := rollout_unsupported(*served)) is not None:  # (the normalisers' own: behind the bf16 check, as ever)
+        if not keyed and (why := rollout_unsupported(*served)) is not None:  # (the normalisers' own: behind the bf16 check, as ever)
             raise ValueError(why)
         self.recurrent = bool(getattr(ac, "is_recurrent", False))
-        kind = _EncoderFront if fused_encoder_policy else _MemoryFront if self.recurrent else _NormalizerFront if obs_normalizer is not None else _Front
+        kind = _EncoderFront if fused_encoder_policy else _RnnEncoderFront if fused_rnn_encoder_policy else _MemoryFront if self.recurrent else _NormalizerFront if obs_normalizer is not None else _Front
         front = self.front = kind(self, obs_normalizer, critic_obs_normalizer, fused_gru_memories)
         self.gru = front.cell is not None and front.cell.nn is torch.nn.GRU
 

@@ -234,3 +234,95 @@ class ActorCriticEncoder(ActorCritic):
         actor_obs, enc = obs_dict["policy"], obs_dict["encoder"]
         critic_obs = obs_dict.get("critic", actor_obs)
         return torch.cat((actor_obs, enc), dim=1), (torch.cat((critic_obs, enc), dim=1) if self.critic_with_encoder else critic_obs)
+
+
+class ActorCriticRNNEncoder(ActorCritic):
+    """Reference loco_rl/loco_rl/modules/actor_critic_rnn_encoder.py:11-151: the RMA teacher whose encoders read a memory.  The tail of
+    the observation row goes through an RNN (`memory_a`, GRU by default), the RNN's output through an MLP encoder, and the embedding is
+    concatenated behind the head of the row; the critic has the same form (`memory_c`, `critic_encoder`) or, with
+    `critic_encoder_hidden_dims=None`, reads its whole row.  Same constructor, parameter names and registration order (`std`,
+    `actor.*`, `critic.*`, `memory_a.rnn.*`, `actor_encoder.*`, `memory_c.rnn.*`, `critic_encoder.*`).
+
+    One departure: with `critic_encoder_hidden_dims=None` the reference's `evaluate` hands the PADDED critic rows of a recurrent
+    minibatch to the critic, so its own PPO update fails with a shape error ("The size of tensor a (8) must match the size of tensor
+    b (4)") as soon as a rollout contains a done.  Here that branch unpads the rows when `masks` is given, as the reference's
+    `UnifiedActorCritic.evaluate` does."""
+
+    is_recurrent = True
+
+    def __init__(self, actor_obs_dim, critic_obs_dim, num_actions, actor_flatten_obs_end_idx, actor_encoder_obs_start_idx,
+                 actor_encoder_hidden_dims, actor_encoder_embedding_dim, actor_hidden_dims, critic_flatten_obs_end_idx,
+                 critic_encoder_obs_start_idx, critic_encoder_hidden_dims, critic_encoder_embedding_dim, critic_hidden_dims,
+                 encoder_rnn_type="gru", encoder_rnn_hidden_size=256, encoder_rnn_num_layers=1, encoder_activation="elu",
+                 encoder_final_activation=None, activation="elu", init_noise_std=1.0, **unused):
+        from .models import MLP
+
+        enc_dim = abs(actor_encoder_obs_start_idx) if actor_encoder_obs_start_idx < 0 else actor_obs_dim - actor_encoder_obs_start_idx
+        flat_dim = actor_flatten_obs_end_idx if actor_flatten_obs_end_idx > 0 else actor_obs_dim - abs(actor_flatten_obs_end_idx)
+        with_c = critic_encoder_hidden_dims is not None
+        c_enc = c_flat = 0
+        if with_c:
+            assert critic_flatten_obs_end_idx is not None, "Critic flatten obs end index is required"
+            assert critic_encoder_obs_start_idx is not None, "Critic encoder obs start index is required"
+            assert critic_encoder_embedding_dim is not None, "Critic encoder embedding dim is required"
+            c_enc = abs(critic_encoder_obs_start_idx) if critic_encoder_obs_start_idx < 0 else critic_obs_dim - critic_encoder_obs_start_idx
+            c_flat = critic_flatten_obs_end_idx if critic_flatten_obs_end_idx > 0 else critic_obs_dim - abs(critic_flatten_obs_end_idx)
+        super().__init__(num_actor_obs=flat_dim + actor_encoder_embedding_dim,
+                         num_critic_obs=(c_flat + critic_encoder_embedding_dim) if with_c else critic_obs_dim,
+                         num_actions=num_actions, actor_hidden_dims=actor_hidden_dims, critic_hidden_dims=critic_hidden_dims,
+                         activation=activation, init_noise_std=init_noise_std)
+        self.actor_encoder_obs_dim, self.actor_flatten_obs_dim = enc_dim, flat_dim
+        self.critic_with_encoder, self.critic_encoder_obs_dim, self.critic_flatten_obs_dim = with_c, c_enc, c_flat
+        # construction order (memory_a, actor_encoder, memory_c, critic_encoder) fixes the RNG draw order of the initial weights
+        self.memory_a = PolicyMemory(enc_dim, type=encoder_rnn_type, num_layers=encoder_rnn_num_layers, hidden_size=encoder_rnn_hidden_size)
+        self.actor_encoder = MLP(encoder_rnn_hidden_size, actor_encoder_hidden_dims, actor_encoder_embedding_dim,
+                                 activation=encoder_activation, final_layer_activation=encoder_final_activation)
+        if with_c:
+            self.memory_c = PolicyMemory(c_enc, type=encoder_rnn_type, num_layers=encoder_rnn_num_layers, hidden_size=encoder_rnn_hidden_size)
+            self.critic_encoder = MLP(encoder_rnn_hidden_size, critic_encoder_hidden_dims, critic_encoder_embedding_dim,
+                                      activation=encoder_activation, final_layer_activation=encoder_final_activation)
+
+    def reset(self, dones=None):
+        self.memory_a.reset(dones)
+        if self.critic_with_encoder:
+            self.memory_c.reset(dones)
+
+    def _actor_input(self, obs, masks=None, hidden_states=None):
+        from .trajectories import unpad_trajectories
+
+        flat = obs[..., :self.actor_flatten_obs_dim]
+        if masks is not None:
+            flat = unpad_trajectories(flat, masks)
+        out = self.memory_a(obs[..., -self.actor_encoder_obs_dim:], masks, hidden_states).squeeze(0)
+        return torch.cat([flat, self.actor_encoder(out)], dim=-1)
+
+    def act(self, obs, masks=None, hidden_states=None):
+        return super().act(self._actor_input(obs, masks, hidden_states))
+
+    def update_distribution_recurrent(self, observations, masks, hidden_states):
+        super().update_distribution(self._actor_input(observations, masks, hidden_states))
+
+    def act_inference(self, obs):
+        return super().act_inference(self._actor_input(obs))
+
+    def act_encoder_inference(self, encoder_obs):
+        return self.actor_encoder(self.memory_a(encoder_obs).squeeze(0))
+
+    def act_backbone_inference(self, flatten_obs, embedding):
+        return super().act_inference(torch.cat([flatten_obs, embedding], dim=-1))
+
+    def evaluate(self, obs, masks=None, hidden_states=None):
+        from .trajectories import unpad_trajectories
+
+        if self.critic_with_encoder:
+            flat = obs[..., :self.critic_flatten_obs_dim]
+            if masks is not None:
+                flat = unpad_trajectories(flat, masks)
+            out = self.memory_c(obs[..., -self.critic_encoder_obs_dim:], masks, hidden_states).squeeze(0)
+            obs = torch.cat([flat, self.critic_encoder(out)], dim=-1)
+        elif masks is not None:  # (the departure of the class docstring)
+            obs = unpad_trajectories(obs, masks)
+        return super().evaluate(obs)
+
+    def get_hidden_states(self):
+        return self.memory_a.hidden_states, (self.memory_c.hidden_states if self.critic_with_encoder else None)

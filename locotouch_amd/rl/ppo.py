@@ -54,6 +54,11 @@ class PPO:
         # (_direct_encoder_update, csrc/lt_encoder.hip); what it cannot serve is refused here and below, never run on another path
         self.fused_encoder_policy = bool(unused.get("fused_encoder_policy", False))
         self._encoders = None  # rl/encoder.py EncoderPair, built at the first update (the storage names the rows' widths)
+        if type(actor_critic).__name__ == "ActorCriticRNNEncoder":  # (first, whatever the device: this class updates through `_eager_update` alone)
+            for key in ("fused_encoder_policy", "direct_recurrent_update", "fused_recurrent_update"):
+                if getattr(self, key):
+                    raise ValueError(f"{key}: the policy is an ActorCriticRNNEncoder: its update is the eager one (the key serves "
+                                     f"{'ActorCriticEncoder' if key == 'fused_encoder_policy' else 'ActorCriticRecurrent'})")
         if self.fused_encoder_policy:
             if self.fused_recurrent_update or self.direct_recurrent_update or self.fused_gru_memories:
                 raise ValueError("fused_encoder_policy: the recurrent keys (fused_recurrent_update, direct_recurrent_update, fused_gru_memories) "

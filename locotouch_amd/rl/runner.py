@@ -17,7 +17,7 @@ from collections import deque
 import torch
 
 from .dist import Dist
-from .modules import ActorCritic, ActorCriticEncoder, ActorCriticRecurrent
+from .modules import ActorCritic, ActorCriticEncoder, ActorCriticRecurrent, ActorCriticRNNEncoder
 from .normalizer import EmpiricalNormalization
 from .ppo import PPO
 
@@ -34,9 +34,15 @@ class OnPolicyRunner:
         from . import modules as _m
 
         cls_name = self.policy_cfg.pop("class_name", "ActorCritic")  # on_policy_runner.py:42 (`eval(class_name)`)
-        if cls_name not in ("ActorCritic", "ActorCriticRecurrent", "ActorCriticEncoder"):
-            raise NotImplementedError(f"policy class {cls_name!r} is not implemented (ActorCritic, ActorCriticRecurrent, ActorCriticEncoder are)")
+        if cls_name not in ("ActorCritic", "ActorCriticRecurrent", "ActorCriticEncoder", "ActorCriticRNNEncoder"):
+            raise NotImplementedError(f"policy class {cls_name!r} is not implemented (ActorCritic, ActorCriticRecurrent, ActorCriticEncoder, "
+                                      "ActorCriticRNNEncoder are)")
+        if cls_name == "ActorCriticRNNEncoder" and self.cfg.get("fused_recurrent_rollout", False):
+            raise ValueError("fused_recurrent_rollout: the policy is an ActorCriticRNNEncoder: that key collects an ActorCriticRecurrent; "
+                             "fused_rnn_encoder_policy is the key of this class")
         self.alg_cfg.pop("class_name", None)
+        if self.cfg.get("fused_rnn_encoder_policy", False) and cls_name != "ActorCriticRNNEncoder":
+            raise ValueError(f"fused_rnn_encoder_policy: the policy is a {cls_name}, not an ActorCriticRNNEncoder")
         ac = getattr(_m, cls_name)(num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
         if "fused_recurrent_update" in self.cfg:  # opt-in (rl/ppo.py `_recurrent_update`); a refusal is PPO's ValueError
             self.alg_cfg["fused_recurrent_update"] = bool(self.cfg["fused_recurrent_update"])
@@ -177,7 +183,8 @@ class OnPolicyRunner:
         """FusedRollout when the env is the HIP env on a GPU and the policy is the plain feed-forward ActorCritic (either noise_std_type), or - behind the cfg
         key `fused_recurrent_rollout` (default False: the fused path draws its exploration noise from the kernels' Philox stream, which
         would change existing runs) - an ActorCriticRecurrent whose memories csrc/lt_memory.hip serves, or - behind `fused_encoder_policy`, for
-        the same reason - an ActorCriticEncoder whose encoders csrc/lt_encoder.hip serves."""
+        the same reason - an ActorCriticEncoder whose encoders csrc/lt_encoder.hip serves, or - behind `fused_rnn_encoder_policy`, again opt-in - an
+        ActorCriticRNNEncoder whose memories and encoders include/lt_rnn_encoder.h serves (LSTM or GRU, by that key alone)."""
         try:
             from ..env import LocoTouchVecEnv
             from .fused import FusedRollout, rollout_unsupported
@@ -186,7 +193,11 @@ class OnPolicyRunner:
         target = self.env
         if not isinstance(target, LocoTouchVecEnv):  # the scripts' wrapper (compat/runtime.py) hands the HIP env over when it adds nothing to a step
             target = getattr(self.env, "fused_target", lambda: None)()
+        rnn_encoder_key = bool(self.cfg.get("fused_rnn_encoder_policy", False))  # opt-in, and never quietly dropped: what it cannot serve raises
         if not isinstance(target, LocoTouchVecEnv) or self.cfg.get("fused_rollout", True) is False:
+            if rnn_encoder_key:
+                raise ValueError("fused_rnn_encoder_policy: there is no fused rollout to put the policy on (the env is not the HIP env, or "
+                                 "fused_rollout is off)")
             return None
         ac, kw = self.alg.actor_critic, {}
         if type(ac) is ActorCriticRecurrent:
@@ -197,6 +208,10 @@ class OnPolicyRunner:
             if not self.cfg.get("fused_encoder_policy", False):
                 return None
             kw["fused_encoder_policy"] = True
+        elif type(ac) is ActorCriticRNNEncoder:
+            if not rnn_encoder_key:
+                return None
+            kw["fused_rnn_encoder_policy"] = True
         elif type(ac) is not ActorCritic:
             return None  # the fused rollout packs the actor / critic MLPs
         if self.empirical_normalization:
@@ -208,7 +223,10 @@ class OnPolicyRunner:
         # what FusedRollout would refuse (a normaliser beside a memory or an encoder or on bf16 rows, shapes outside the kernels' limits): the
         # eager loop - rl/fused.py states it once, for its constructor and for this.  That covers normalisers whose buffers, eps or until
         # the kernels do not serve as well: this runner builds its own, which are served
-        if rollout_unsupported(self.alg, **kw) is not None:
+        why = rollout_unsupported(self.alg, **kw)
+        if why is not None:
+            if rnn_encoder_key:
+                raise ValueError(why)
             return None
         return FusedRollout(target, self.alg, **kw)
 
@@ -288,6 +306,9 @@ class OnPolicyRunner:
         self.eval_mode()
         if device is not None:
             self.alg.actor_critic.to(device)
+        if fused and type(self.alg.actor_critic) is ActorCriticRNNEncoder:
+            raise NotImplementedError("get_inference_policy(fused=True): ActorCriticRNNEncoder is not served (the fused inference step of "
+                                      "rl/fused_policy.py is memory -> actor, ActorCriticRecurrent's shape); fused=False steps it through its modules")
         if fused and getattr(self.alg.actor_critic, "is_recurrent", False):
             from .fused_policy import FusedRecurrentPolicy
 

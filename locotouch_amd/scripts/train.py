@@ -61,6 +61,10 @@ def main() -> None:
                     help="encoder policies (ActorCriticEncoder): collect on the fused rollout path and update without an autograd graph or a "
                          "host read between minibatch steps (csrc/lt_encoder.hip, rl/ppo.py `_direct_encoder_update`); exploration noise "
                          "then comes from the kernels' Philox stream instead of torch's generator")
+    ap.add_argument("--fused_rnn_encoder_policy", action="store_true",
+                    help="RNN-encoder policies (ActorCriticRNNEncoder, LSTM or GRU memories): collect on the fused rollout path "
+                         "(include/lt_rnn_encoder.h, rl/fused.py); the update stays the eager one; exploration noise then comes from the "
+                         "kernels' Philox stream instead of torch's generator")
     ap.add_argument("--symmetry_augmentation", action="store_true",
                     help="PPO's mirrored data augmentation (rl/symmetry.py `mirror_go1`): every minibatch with its left-right mirror image; "
                          "on the GPU inside the fused update (include/lt_ppo_sym.h)")
@@ -92,6 +96,8 @@ def main() -> None:
         cfg["direct_recurrent_update"] = True
     if args.fused_encoder_policy:
         cfg["fused_encoder_policy"] = True
+    if args.fused_rnn_encoder_policy:
+        cfg["fused_rnn_encoder_policy"] = True
     if args.symmetry_augmentation or args.mirror_loss_coeff is not None:
         from locotouch_amd.rl.symmetry import MIRROR_GO1
 
