@@ -122,7 +122,8 @@ _ENV_VALUE_QUERIES = (
     "lt_elu_backward_bias_nblk", "lt_head_wgrad_nblk", "lt_mlp_backward_blocks", "lt_env_kernel_name", "lt_mlp_kernel_name")
 
 # THE TABLE: one row per header of the C ABI, bound in this order.  A row is (public prefix, file under include/, whether the header may
-# use lt_env.h's structures, its value queries, the structures published as Lt* classes).  A header with prefix P is published as
+# use lt_env.h's structures - or the file name of an EARLIER row whose structures it uses -, its value queries, the structures published
+# as Lt* classes).  A header with prefix P is published as
 # P_HEADER (its path), P_CONSTS, P_SIGNATURES and P_VALUE_QUERIES; lt_env.h has no prefix (HEADER, CONSTS, SIGNATURES, VALUE_QUERIES,
 # and STRUCTS, EXPORTS).  Every header's LT_* constants are module globals as well.  Adding a header is adding a row.
 HEADERS = (
@@ -147,6 +148,8 @@ HEADERS = (
     ("ENCODER", "lt_encoder.h", False, ("lt_encoder_forward_launches",), ("lt_encoder_desc", "lt_encoder_net")),  # the encoder in front of an ActorCriticEncoder's stacks
     ("RNN_ENCODER", "lt_rnn_encoder.h", False, ("lt_rnn_encoder_forward_launches",),
      ("lt_rnn_encoder_memory", "lt_rnn_encoder_net")),  # an ActorCriticRNNEncoder's rollout: the memory step on strided rows, the encoder on the memory's output
+    ("RNN_ENCODER_TRAIN", "lt_rnn_encoder_train.h", "lt_rnn_encoder.h", ("lt_rnn_encoder_backward_launches",),
+     ("lt_rnn_encoder_grad",)),  # an ActorCriticRNNEncoder's update: the encoder's training form and its backward pass
 )
 
 
@@ -155,10 +158,12 @@ def _bind(table, include_dir):
     ImportError, naming the header and the entry point, if a value query of the row is not declared in its header, if an entry point
     returns no int (in lt_env.h: one that is no value query - there a query may return a size or a string), or if a name repeats one of an
     earlier header."""
-    bound, seen, env_structs = [], set(), None
+    bound, seen, env_structs, structs_of = [], set(), None, {}
     for prefix, fname, uses_env_structs, queries, _ in table:
         path, queries = os.path.join(include_dir, fname), frozenset(queries)
-        consts, structs, sigs = parse_header(open(path).read(), structs=env_structs if uses_env_structs else None, bases={"lt_cfg": _CfgMethods})
+        given = structs_of[uses_env_structs] if isinstance(uses_env_structs, str) else env_structs if uses_env_structs else None
+        consts, structs, sigs = parse_header(open(path).read(), structs=given, bases={"lt_cfg": _CfgMethods})
+        structs_of[fname] = structs
         if not prefix:
             env_structs = structs
         for name in sorted(queries - set(sigs)):

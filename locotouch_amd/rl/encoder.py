@@ -5,6 +5,10 @@ writes `[ obs[:, :flat_dim] | enc(obs[:, -enc_in:]) ]` for the actor and, when i
 `EncoderPair` holds the descriptors of a policy's encoders; `forward(obs, critic_obs, out, critic_out, acts=...)` is the launch - the
 rollout's form without `acts`, the update's with them (the activation behind every hidden layer and, with a final activation, the
 pre-activation embedding: what `rl/mlp.py::backward_chain` and the final activation's derivative read).
+
+`RnnEncoderPair` is the same for an `ActorCriticRNNEncoder`, whose encoders read the output rows of a memory (include/lt_rnn_encoder.h):
+`forward` in the rollout, and for `PPO._direct_rnn_encoder_update` `forward_train` and `backward` (include/lt_rnn_encoder_train.h: one
+launch from the gradient of the stacks' input rows to every layer's dz and the gradient of the memory's output).
 """
 from __future__ import annotations
 
@@ -155,8 +159,8 @@ class RnnEncoderPair:
         if lib.lt_rnn_encoder_forward_launches(ctypes.byref(self._net(0)), ctypes.byref(self._net(1))) != 1:
             raise ValueError(lib.lt_last_error().decode())
 
-    def _net(self, which: int, obs=None, h=None, out=None):
-        """LtRnnEncoderNet of network `which` (0 actor, 1 critic); without tensors: its widths alone."""
+    def _net(self, which: int, obs=None, h=None, out=None, acts=()):
+        """LtRnnEncoderNet of network `which` (0 actor, 1 critic); without tensors: its widths alone.  `acts`: the training form's buffers."""
         desc, linears, _ = self.nets[which]
         net = _abi.LtRnnEncoderNet()
         net.obs_dim, net.flat_dim, net.enc_in, net.num_layers = desc.obs_dim, desc.flat_dim, desc.enc_in, desc.num_layers
@@ -167,12 +171,65 @@ class RnnEncoderPair:
             net.obs, net.obs_stride, net.h, net.h_stride, net.out = obs.data_ptr(), obs.stride(0), h.data_ptr(), h.stride(0), out.data_ptr()
             for l, m in enumerate(linears):
                 net.weight[l], net.bias[l] = m.weight.data_ptr(), m.bias.data_ptr()
+            for l, a in enumerate(acts):
+                net.acts[l] = a.data_ptr()
         return net
+
+    @staticmethod
+    def _check_rows(*rows) -> None:
+        for x in rows:
+            if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
+                raise ValueError("the encoder reads f32 rows with unit column stride")
 
     def forward(self, obs, critic_obs, h_a, h_c, out, critic_out) -> None:
         """One launch, the inference form."""
-        for x in (obs, critic_obs, h_a, h_c):
-            if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1:
-                raise ValueError("the encoder reads f32 rows with unit column stride")
+        self._check_rows(obs, critic_obs, h_a, h_c)
         _abi.call("lt_rnn_encoder_forward", self._net(0, obs, h_a, out), self._net(1, critic_obs, h_c, critic_out), obs.shape[0],
                   _abi.stream(obs.device))
+
+    def forward_train(self, obs, critic_obs, h_a, h_c, out, critic_out):
+        """One launch, the training form (include/lt_rnn_encoder_train.h).  Returns (actor acts, critic acts): per network the activation
+        behind every hidden layer and, with a final activation, the pre-activation embedding - what `backward` reads."""
+        self._check_rows(obs, critic_obs, h_a, h_c)
+        n = obs.shape[0]
+        acts = [EncoderPair._acts(desc, n, obs.device) for desc, _, _ in self.nets]
+        _abi.call("lt_rnn_encoder_forward_train", self._net(0, obs, h_a, out, acts[0]), self._net(1, critic_obs, h_c, critic_out, acts[1]), n,
+                  _abi.stream(obs.device))
+        return acts[0], acts[1]
+
+    def backward(self, dx, outs, acts, grad_of, hs):
+        """From dx = (dx_a, dx_c), the gradients w.r.t. the rows `outs` = (out, critic_out) of `forward_train` (f32, unit column stride, any
+        row stride), to (dh_a, dh_c), each [n, enc_in]: the gradients w.r.t. `hs` = (h_a, h_c), the contiguous rows that launch read.  ONE
+        launch (`lt_rnn_encoder_backward`) leaves every layer's dz_l and dh; the encoders' weight and bias gradients dW_l = dz_l^T in_l
+        (in_0 = h, in_l = acts[l - 1]) and db_l = column sums of dz_l are then written IN PLACE into `grad_of[param]`, by the means
+        rl/memory_seq.py `direct_backward` uses."""
+        from .memory_seq import _wgrad_into
+
+        self._check_rows(*dx)
+        n, dev = dx[0].shape[0], dx[0].device
+        grads, dzs, dhs = [], [], []
+        for k, (desc, linears, width) in enumerate(self.nets):
+            g = _abi.LtRnnEncoderGrad()
+            g.flat_dim, g.enc_in, g.num_layers = desc.flat_dim, desc.enc_in, desc.num_layers
+            g.activation, g.final_activation = desc.activation, desc.final_activation
+            if not outs[k].is_contiguous() or outs[k].shape != (n, width):
+                raise ValueError("the encoder's output rows must be the contiguous [n, flat_dim + embedding] array of forward_train")
+            g.dx, g.dx_stride, g.out = dx[k].data_ptr(), dx[k].stride(0), outs[k].data_ptr()
+            dz = [torch.empty(n, desc.dims[l], device=dev, dtype=torch.float32) for l in range(desc.num_layers)]
+            dh = torch.empty(n, desc.enc_in, device=dev, dtype=torch.float32)
+            for l, m in enumerate(linears):
+                g.dims[l], g.weight[l], g.dz[l] = desc.dims[l], m.weight.data_ptr(), dz[l].data_ptr()
+            for l, a in enumerate(acts[k]):
+                g.acts[l] = a.data_ptr()
+            g.dh = dh.data_ptr()
+            grads.append(g)
+            dzs.append(dz)
+            dhs.append(dh)
+        _abi.call("lt_rnn_encoder_backward", grads[0], grads[1], n, _abi.stream(dev))
+        with torch.no_grad():
+            for k, (desc, linears, _) in enumerate(self.nets):
+                ins = [hs[k], *acts[k][:desc.num_layers - 1]]
+                for l, m in enumerate(linears):
+                    torch.sum(dzs[k][l], dim=0, out=grad_of[m.bias])
+                    _wgrad_into(grad_of[m.weight], dzs[k][l], ins[l])
+        return dhs[0], dhs[1]

@@ -7,7 +7,10 @@ branch (mirrored data augmentation and / or a mirror loss: `_symmetry_update`; o
 with augmentation and include/lt_ppo_mirror.h without).  The RND branch is not built: a `rnd_cfg` is refused.
 An `ActorCriticEncoder` updates through the op chain, or - behind the opt-in key `fused_encoder_policy` - without an autograd graph
 (`_direct_encoder_update`, include/lt_encoder.h).
-The three updates without an autograd graph (`_direct_update`, `_direct_encoder_update`, `_direct_recurrent_update`) share one skeleton -
+An `ActorCriticRNNEncoder` updates through the eager loop, or - behind the opt-in key `direct_rnn_encoder_update` - on whole rollouts
+of env blocks without an autograd graph (`_direct_rnn_encoder_update`, include/lt_rnn_encoder_train.h).
+The updates without an autograd graph (`_direct_update`, `_direct_encoder_update`, `_direct_recurrent_update`,
+`_direct_rnn_encoder_update`) share one skeleton -
 `_direct_begin`, `_direct_loss_and_rule` per step, `_direct_end` with the update's one host read - and keep only their own forward and
 backward passes; the updates that run the loss as torch ops share `_op_chain_loss`.
 
@@ -54,7 +57,11 @@ class PPO:
         # (_direct_encoder_update, csrc/lt_encoder.hip); what it cannot serve is refused here and below, never run on another path
         self.fused_encoder_policy = bool(unused.get("fused_encoder_policy", False))
         self._encoders = None  # rl/encoder.py EncoderPair, built at the first update (the storage names the rows' widths)
-        if type(actor_critic).__name__ == "ActorCriticRNNEncoder":  # (first, whatever the device: this class updates through `_eager_update` alone)
+        # opt-in: an `ActorCriticRNNEncoder` updates on whole rollouts of env blocks without padding, an autograd graph or a host read
+        # between its steps (_direct_rnn_encoder_update, include/lt_rnn_encoder_train.h); what it cannot serve is refused below
+        self.direct_rnn_encoder_update = bool(unused.get("direct_rnn_encoder_update", False))
+        self._rnn_encoders = None  # rl/encoder.py RnnEncoderPair, built at the first update
+        if type(actor_critic).__name__ == "ActorCriticRNNEncoder":  # (first, whatever the device: the keys of the other kinds do not serve this class)
             for key in ("fused_encoder_policy", "direct_recurrent_update", "fused_recurrent_update"):
                 if getattr(self, key):
                     raise ValueError(f"{key}: the policy is an ActorCriticRNNEncoder: its update is the eager one (the key serves "
@@ -85,6 +92,10 @@ class PPO:
             why = self._recurrent_update_unsupported()
             if why is not None:
                 raise ValueError(f"fused_recurrent_update: {why}")
+        if self.direct_rnn_encoder_update:
+            why = self._direct_rnn_encoder_unsupported(kernels=False)  # (the rest below, with the optimizer's flat bucket there)
+            if why is not None:
+                raise ValueError(f"direct_rnn_encoder_update: {why}")
         self._pair = None
         if on_gpu and bool(unused.get("tuned_gemms", True)):
             from . import tuned_gemms
@@ -122,6 +133,10 @@ class PPO:
             why = self._direct_encoder_unsupported()
             if why is not None:
                 raise ValueError(f"fused_encoder_policy: {why}")
+        if self.direct_rnn_encoder_update:
+            why = self._direct_rnn_encoder_unsupported()
+            if why is not None:
+                raise ValueError(f"direct_rnn_encoder_update: {why}")
 
     @staticmethod
     def _resolve_symmetry(symmetry_cfg, actor_critic):
@@ -595,6 +610,8 @@ class PPO:
             group["lr"] = self.learning_rate
 
     def update(self):
+        if self.direct_rnn_encoder_update:
+            return self._direct_rnn_encoder_update()
         if self.fused_encoder_policy:
             return self._direct_encoder_update()
         if self.direct_recurrent_update:
@@ -781,6 +798,103 @@ class PPO:
             dx = (torch.empty_like(x_a), torch.empty_like(x_c))
             pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
             direct_backward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, recs, dx, grad_of)
+            fa.step_dev(self.max_grad_norm, c.lr_dev)
+        return self._direct_end(c, with_dx=True)
+
+    def _direct_rnn_encoder_unsupported(self, kernels: bool = True) -> str | None:
+        """Why `_direct_rnn_encoder_update` does not serve this PPO (None: it does).  `kernels=False`: the first part alone - the class,
+        its critic, the symmetry cfg, the ranks and the device -, what can be said before the optimizer's flat bucket exists."""
+        from . import encoder
+        from .memory_seq import memories_unsupported
+
+        ac = self.actor_critic
+        if type(ac).__name__ != "ActorCriticRNNEncoder":
+            return f"the policy is a {type(ac).__name__}, not an ActorCriticRNNEncoder"
+        if not ac.critic_with_encoder:
+            return "the critic has no encoder"
+        if self.symmetry is not None:
+            return "symmetry_cfg is not served for this class (its hidden states have no mirror)"
+        if self.dist.world_size > 1:
+            return (f"dist.world_size is {self.dist.world_size}: the collectives of this form are not covered by a multi-rank test, it runs "
+                    "on one rank only")
+        if torch.device(self.device).type != "cuda":
+            return f"the device is {self.device!r}: its kernels run on a GPU only"
+        if not kernels:
+            return None
+        why, written = self._direct_stacks_unsupported()
+        if why is not None:
+            return why
+        why = memories_unsupported(ac.memory_a, ac.memory_c, gru_memories=True, layer_count=True)
+        if why is not None:
+            return why
+        try:  # (the rows' width is the storage's to say: here the narrowest row that holds both parts)
+            encoder.RnnEncoderPair(ac, ac.actor_flatten_obs_dim + ac.actor_encoder_obs_dim, ac.critic_flatten_obs_dim + ac.critic_encoder_obs_dim)
+        except ValueError as e:
+            return str(e)
+        written |= {id(p) for mem in (ac.memory_a, ac.memory_c) for p in (mem.rnn.weight_ih_l0, mem.rnn.weight_hh_l0, mem.rnn.bias_ih_l0, mem.rnn.bias_hh_l0)}
+        written |= {id(p) for enc in (ac.actor_encoder, ac.critic_encoder) for p in enc.parameters()}
+        return self._unwritten_gradient(written)
+
+    def _direct_rnn_encoder_update(self):
+        """The update of an `ActorCriticRNNEncoder` on the GPU with NO autograd graph, NO padded trajectories and NO host read between its
+        steps: `_direct_recurrent_update` with the encoders between the memories and the stacks, on the same skeleton and the same env
+        blocks.  Once per update and block: the observation rows laid out contiguously (their head columns are read in place), their tail
+        columns as [T, per, enc_in] (what the sequence kernels and dW_ih read), the dones as bytes, the states saved at step 0.  Per
+        optimizer step: the cell's `seq_forward` on the tails; `lt_rnn_encoder_forward_train` on the memories' outputs (the rows the
+        stacks read, the encoders' activations); the packed forward; the loss and the learning-rate rule; both stacks' backward chains
+        with the gradient w.r.t. their input rows; `lt_rnn_encoder_backward` from the embedding columns of those rows (ONE launch:
+        every layer's dz and the gradient w.r.t. the memories' outputs) and the encoders' weight and bias gradients
+        (`RnnEncoderPair.backward`); the cell's `seq_backward` from that gradient and the memories' eight parameter gradients
+        (`direct_backward`) - every gradient written in place into the flat bucket.  LSTM and GRU memories alike, as the rollout key."""
+        from .encoder import RnnEncoderPair
+        from .memory_seq import _dones_bytes, cell_of, direct_backward, direct_forward
+
+        ac, st, fa, pair = self.actor_critic, self.storage, self._flat_adam, self._pair
+        if st.observations.dtype != torch.float32 or st.privileged_observations.dtype != torch.float32:
+            raise ValueError("direct_rnn_encoder_update: bf16 observation rows: the memories and the encoder launch read f32 rows")
+        if st.saved_hidden_states_a is None or st.saved_hidden_states_c is None:
+            raise ValueError("direct_rnn_encoder_update: the storage holds no saved hidden states (no rollout of a recurrent policy filled it)")
+        D_a, D_c = st.observations.shape[-1], st.privileged_observations.shape[-1]
+        if self._rnn_encoders is None:
+            try:
+                self._rnn_encoders = RnnEncoderPair(ac, D_a, D_c)
+            except ValueError as e:
+                raise ValueError(f"direct_rnn_encoder_update: {e}") from None
+        enc = self._rnn_encoders
+        T, N, nmb = st.num_steps, st.num_envs, self.num_mini_batches
+        per = N // nmb
+        m = T * per
+        if per < 1 or (self.normalize_advantage_per_mini_batch and m < 2):
+            raise ValueError(f"direct_rnn_encoder_update: {nmb} minibatches of {N} envs x {T} steps leave a block of {m} rows")
+        dev = st.observations.device
+        cell = cell_of(ac.memory_a, True)
+        H = ac.memory_a.rnn.hidden_size
+        I_a, I_c = ac.actor_encoder_obs_dim, ac.critic_encoder_obs_dim
+        idx_all = self._block_row_index(T, N, nmb, dev)
+        c = self._direct_begin("direct_rnn_encoder_update", pair, idx_all.view(-1), m)
+        grad_of = c.grad_of
+        dones = _dones_bytes(st.dones.view(T, N))
+        blocks = []
+        for i in range(nmb):
+            sl = (slice(None), slice(i * per, (i + 1) * per))
+            states = [tuple(h[0][sl].reshape(per, H) for h in hs) for hs in (st.saved_hidden_states_a, st.saved_hidden_states_c)]
+            rows_a, rows_c = st.observations[sl].contiguous(), st.privileged_observations[sl].contiguous()
+            blocks.append((rows_a.view(m, D_a), rows_c.view(m, D_c), rows_a[..., D_a - I_a:].contiguous(), rows_c[..., D_c - I_c:].contiguous(),
+                           dones[sl], *states))
+        for step_i in range(self.num_learning_epochs * nmb):
+            i = step_i % nmb
+            rows_a, rows_c, tail_a, tail_c, d, hc_a, hc_c = blocks[i]
+            recs = direct_forward(cell, ac.memory_a, ac.memory_c, tail_a, tail_c, d, hc_a, hc_c)
+            hs = (recs[0]["out"].view(m, H), recs[1]["out"].view(m, H))
+            x_a = torch.empty(m, enc.a_width, device=dev, dtype=torch.float32)
+            x_c = torch.empty(m, enc.c_width, device=dev, dtype=torch.float32)
+            enc_acts = enc.forward_train(rows_a, rows_c, *hs, x_a, x_c)
+            (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
+            dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx_all[i], m, i)
+            dx = (torch.empty_like(x_a), torch.empty_like(x_c))
+            pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
+            dh = enc.backward(dx, (x_a, x_c), enc_acts, grad_of, hs)
+            direct_backward(cell, ac.memory_a, ac.memory_c, tail_a, tail_c, d, recs, dh, grad_of)
             fa.step_dev(self.max_grad_norm, c.lr_dev)
         return self._direct_end(c, with_dx=True)
 

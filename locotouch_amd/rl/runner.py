@@ -43,6 +43,8 @@ class OnPolicyRunner:
         self.alg_cfg.pop("class_name", None)
         if self.cfg.get("fused_rnn_encoder_policy", False) and cls_name != "ActorCriticRNNEncoder":
             raise ValueError(f"fused_rnn_encoder_policy: the policy is a {cls_name}, not an ActorCriticRNNEncoder")
+        if self.cfg.get("direct_rnn_encoder_update", False) and cls_name != "ActorCriticRNNEncoder":
+            raise ValueError(f"direct_rnn_encoder_update: the policy is a {cls_name}, not an ActorCriticRNNEncoder")
         ac = getattr(_m, cls_name)(num_obs, num_critic_obs, env.num_actions, **self.policy_cfg).to(device)
         if "fused_recurrent_update" in self.cfg:  # opt-in (rl/ppo.py `_recurrent_update`); a refusal is PPO's ValueError
             self.alg_cfg["fused_recurrent_update"] = bool(self.cfg["fused_recurrent_update"])
@@ -52,6 +54,8 @@ class OnPolicyRunner:
             self.alg_cfg["direct_recurrent_update"] = bool(self.cfg["direct_recurrent_update"])
         if "fused_encoder_policy" in self.cfg:  # opt-in: an ActorCriticEncoder on the fused rollout and `_direct_encoder_update`
             self.alg_cfg["fused_encoder_policy"] = bool(self.cfg["fused_encoder_policy"])
+        if "direct_rnn_encoder_update" in self.cfg:  # opt-in: an ActorCriticRNNEncoder updates through `_direct_rnn_encoder_update`
+            self.alg_cfg["direct_rnn_encoder_update"] = bool(self.cfg["direct_rnn_encoder_update"])
         sym = self.alg_cfg.get("symmetry_cfg")
         if sym is not None:  # on_policy_runner.py:60-63: the augmentation function is handed the env; PPO takes a plain dict
             sym = sym.to_dict() if hasattr(sym, "to_dict") else (dict(sym) if isinstance(sym, dict) else dict(vars(sym)))

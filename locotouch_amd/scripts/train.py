@@ -65,6 +65,10 @@ def main() -> None:
                     help="RNN-encoder policies (ActorCriticRNNEncoder, LSTM or GRU memories): collect on the fused rollout path "
                          "(include/lt_rnn_encoder.h, rl/fused.py); the update stays the eager one; exploration noise then comes from the "
                          "kernels' Philox stream instead of torch's generator")
+    ap.add_argument("--direct_rnn_encoder_update", action="store_true",
+                    help="RNN-encoder policies (ActorCriticRNNEncoder): update on whole rollouts of env blocks without padding, an autograd "
+                         "graph or a host read between the steps (include/lt_rnn_encoder_train.h, rl/ppo.py `_direct_rnn_encoder_update`); "
+                         "independent of --fused_rnn_encoder_policy")
     ap.add_argument("--symmetry_augmentation", action="store_true",
                     help="PPO's mirrored data augmentation (rl/symmetry.py `mirror_go1`): every minibatch with its left-right mirror image; "
                          "on the GPU inside the fused update (include/lt_ppo_sym.h)")
@@ -98,6 +102,8 @@ def main() -> None:
         cfg["fused_encoder_policy"] = True
     if args.fused_rnn_encoder_policy:
         cfg["fused_rnn_encoder_policy"] = True
+    if args.direct_rnn_encoder_update:
+        cfg["direct_rnn_encoder_update"] = True
     if args.symmetry_augmentation or args.mirror_loss_coeff is not None:
         from locotouch_amd.rl.symmetry import MIRROR_GO1
 

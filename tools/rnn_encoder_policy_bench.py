@@ -19,6 +19,13 @@ programs run on the parent commit and on this tree, and records them and whether
 Without the directory the file says "not measured".
 
     python tools/rnn_encoder_policy_bench.py [--envs 4096] [--rounds 7] [--controls DIR] [--out profiles/rnn_encoder_policy_4096.json]
+
+`--update` measures the UPDATE key instead, `direct_rnn_encoder_update` (rl/ppo.py `_direct_rnn_encoder_update`), and writes
+profiles/rnn_encoder_update_<n>.json: the rollout key is on in both legs, `update_off` runs the eager recurrent update and `update_on`
+the graph-free one; the traced kernels are then `lt_rnn_encoder_backward_kernel` and `lt_encoder_kernel`.  The parent commit has no such
+key: its `--mode on` run IS the off leg, so the controls directory also takes
+  parent_update*.txt                       the RESULT line of this tool's `--mode on` run on the parent commit's tree, one file per run
+and the file records whether its update and iteration intervals overlap this tree's `update_off` leg.
 """
 from __future__ import annotations
 
@@ -43,6 +50,7 @@ POLICY = dict(class_name="ActorCriticRNNEncoder", actor_flatten_obs_end_idx=270,
               encoder_final_activation="tanh")
 KEYS = ("rollout_ms", "update_ms", "iteration_ms")
 KERNELS = ("lt_memory_step_kernel", "lt_encoder_kernel")
+UPDATE_KERNELS = ("lt_rnn_encoder_backward_kernel", "lt_encoder_kernel")
 CONTROL_KEYS = ("rollout_ms", "rollout_graph_ms", "iteration_ms")
 
 
@@ -64,7 +72,9 @@ def make_runner(envs: int, mode: str):
 
     cfg = dict(train_cfg(TASK))
     cfg["policy"] = dict(cfg["policy"], **POLICY)
-    cfg["fused_rnn_encoder_policy"] = mode in ("on", "trace")
+    cfg["fused_rnn_encoder_policy"] = mode != "off"
+    if mode in ("update_on", "update_trace"):
+        cfg["direct_rnn_encoder_update"] = True
     return OnPolicyRunner(make(TASK, num_envs=envs, device="cuda:0", seed=1), cfg, log_dir=None, device="cuda:0")
 
 
@@ -72,9 +82,9 @@ def measure(mode: str, envs: int, rounds: int, warmup: int, commit: str | None =
     runner = make_runner(envs, mode)
     alg, fused = runner.alg, runner._make_fused()
     out = {"mode": mode, "tree": commit or tree(), "policy": type(alg.actor_critic).__name__, "key": bool(runner.cfg.get("fused_rnn_encoder_policy")),
-           "fused_rollout": fused is not None, "launches_per_step": fused.launches_per_step if fused is not None else None,
+           "update_key": bool(runner.cfg.get("direct_rnn_encoder_update")), "fused_rollout": fused is not None, "launches_per_step": fused.launches_per_step if fused is not None else None,
            "steps": runner.num_steps_per_env, "num_mini_batches": alg.num_mini_batches, "num_learning_epochs": alg.num_learning_epochs}
-    if mode == "trace":
+    if mode.endswith("trace"):
         runner.learn(2)
         return out
     runner.learn(warmup + rounds)
@@ -85,28 +95,29 @@ def measure(mode: str, envs: int, rounds: int, warmup: int, commit: str | None =
     return out
 
 
-def kernel_trace(envs: int) -> dict:
-    """Per-launch time of the memory-step and encoder kernels and their share of all kernel time: a `rocprofv3 --kernel-trace --stats`
-    run of two iterations with the key on, nothing else traced."""
+def kernel_trace(envs: int, mode: str = "trace", kernels=KERNELS) -> dict:
+    """Per-launch time of `kernels` (the memory-step and encoder kernels; with `mode="update_trace"` the encoder's backward and forward
+    kernels) and their share of all kernel time: a `rocprofv3 --kernel-trace --stats` run of two iterations with the key(s) on, nothing
+    else traced."""
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return {"error": "rocprofv3 not found"}
     tmp = tempfile.mkdtemp(prefix="rnn_encoder_policy_trace_")
     try:
         p = subprocess.run([exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "trace", "--", sys.executable,
-                            os.path.abspath(__file__), "--mode", "trace", "--envs", str(envs)], capture_output=True, text=True, timeout=600)
+                            os.path.abspath(__file__), "--mode", mode, "--envs", str(envs)], capture_output=True, text=True, timeout=600)
         if p.returncode != 0:
             return {"error": f"rocprofv3 exit {p.returncode}: {p.stderr[-500:]}"}
         rows, total_ns = {}, 0.0
         for path in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(path)):
                 total_ns += int(row["Calls"]) * float(row["AverageNs"])
-                if any(k in row.get("Name", "") for k in KERNELS):
+                if any(k in row.get("Name", "") for k in kernels):
                     rows[row["Name"]] = {"calls": int(row["Calls"]), "average_us": float(row["AverageNs"]) / 1e3,
                                          "min_us": float(row["MinNs"]) / 1e3, "max_us": float(row["MaxNs"]) / 1e3}
         for r in rows.values():  # of the whole traced run (two iterations: the rollout's launches; the eager update launches neither kernel)
             r["share_of_kernel_time"] = r["calls"] * r["average_us"] * 1e3 / total_ns
-        return rows or {"error": "no row of the two kernels in the kernel statistics"}
+        return rows or {"error": "no row of the kernels in the kernel statistics"}
     except (OSError, subprocess.TimeoutExpired, KeyError, ValueError) as exc:
         return {"error": f"{type(exc).__name__}: {exc}"}
     finally:
@@ -148,6 +159,13 @@ def controls(d: str | None):
     if len(bench) == 2:
         bench["intervals_overlap"] = overlap(bench["parent"], bench["tree"])
     out["bench"] = bench or "not measured"
+    runs = []  # the update leg's baseline: this tool's `--mode on` on the parent commit's tree
+    for path in sorted(glob.glob(os.path.join(d, "parent_update*.txt"))):
+        line = [l for l in open(path).read().splitlines() if l.startswith("RESULT ")]
+        if line:
+            runs.append(json.loads(line[-1][7:]))
+    if runs:
+        out["parent_update_off"] = {"runs": runs, **{k: {"min": min(r[k]["min"] for r in runs), "max": max(r[k]["max"] for r in runs)} for k in KEYS}}
     return out
 
 
@@ -160,13 +178,16 @@ def main() -> None:
     ap.add_argument("--commit", help="what to record as measured_on_commit (default: git rev-parse --short HEAD, null outside a checkout)")
     ap.add_argument("--controls", help="directory with the control runs of the parent commit and of this tree (module docstring)")
     ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
-    ap.add_argument("--mode", choices=["off", "on", "trace"], help="(internal) measure one leg and print it")
+    ap.add_argument("--update", action="store_true", help="measure the update key direct_rnn_encoder_update (rollout key on in both legs)")
+    ap.add_argument("--mode", choices=["off", "on", "trace", "update_off", "update_on", "update_trace"], help="(internal) measure one leg and print it")
     args = ap.parse_args()
     if args.rounds < 5:
         sys.exit("--rounds must be at least 5")
     if args.mode:
         print("RESULT " + json.dumps(measure(args.mode, args.envs, args.rounds, args.warmup, args.commit)))
         return
+    if args.update:
+        return main_update(args)
     legs = {}
     for mode in ("off", "on"):  # a fresh process each: no allocator state carried from one to the next
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--envs", str(args.envs), "--rounds", str(args.rounds),
@@ -192,6 +213,42 @@ def main() -> None:
            "on_faster_than_the_spread": {k[:-3]: outside(k) for k in KEYS},
            "controls": controls(args.controls)}
     out = args.out or os.path.join(REPO, "profiles", f"rnn_encoder_policy_{args.envs}.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+def main_update(args) -> None:
+    """The update key's file: legs `update_off` / `update_on`, the new kernel's own time, the controls."""
+    legs = {}
+    for mode in ("update_off", "update_on"):  # a fresh process each; `--commit` names the tree in each leg's record as well
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--envs", str(args.envs), "--rounds", str(args.rounds),
+                            "--warmup", str(args.warmup)] + (["--commit", args.commit] if args.commit else []),
+                           capture_output=True, text=True, timeout=900)
+        line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            sys.exit(f"{mode}: exit {p.returncode}\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}")
+        legs[mode] = json.loads(line[-1][7:])
+    off, on = legs["update_off"], legs["update_on"]
+    if off["update_key"] or not on["update_key"] or not (off["fused_rollout"] and on["fused_rollout"]):
+        sys.exit("a leg ran on another path than its name says")
+    ctl = controls(args.controls)
+    parent = ctl.get("parent_update_off") if isinstance(ctl, dict) else None
+    res = {"task": TASK, "envs": args.envs, "policy": POLICY, "measured_on_commit": args.commit or tree(),
+           "notes": {"update_off": "fused_rnn_encoder_policy on, direct_rnn_encoder_update off: the eager recurrent update",
+                     "update_on": "both keys on: rl/ppo.py _direct_rnn_encoder_update",
+                     "update_ms": "runner wall clock of alg.update()", "iteration_ms": "rollout + update",
+                     "spread": "min and max over the rounds, beside the median",
+                     "parent_update_off": "the parent commit's tree, which has no update key: its eager update, the off baseline"},
+           **legs, "kernels": None if args.no_trace else kernel_trace(args.envs, "update_trace", UPDATE_KERNELS),
+           "off_over_on": {k[:-3]: off[k]["median"] / on[k]["median"] for k in KEYS},
+           "on_faster_than_the_spread": {k[:-3]: on[k]["max"] < off[k]["min"] for k in KEYS},
+           "off_overlaps_parent": {k[:-3]: overlap(parent[k], off[k]) for k in KEYS} if parent else "not measured",
+           "on_faster_than_parent_spread": {k[:-3]: on[k]["max"] < parent[k]["min"] for k in KEYS} if parent else "not measured",
+           "controls": ctl}
+    out = args.out or os.path.join(REPO, "profiles", f"rnn_encoder_update_{args.envs}.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
