@@ -150,6 +150,8 @@ HEADERS = (
      ("lt_rnn_encoder_memory", "lt_rnn_encoder_net")),  # an ActorCriticRNNEncoder's rollout: the memory step on strided rows, the encoder on the memory's output
     ("RNN_ENCODER_TRAIN", "lt_rnn_encoder_train.h", "lt_rnn_encoder.h", ("lt_rnn_encoder_backward_launches",),
      ("lt_rnn_encoder_grad",)),  # an ActorCriticRNNEncoder's update: the encoder's training form and its backward pass
+    ("POLICY_ENCODER", "lt_policy_encoder.h", False, ("lt_policy_encoder_step_launches",),
+     ("lt_policy_encoder_desc", "lt_policy_encoder_params")),  # one inference step of an ActorCriticEncoder / ActorCriticRNNEncoder
 )
 
 

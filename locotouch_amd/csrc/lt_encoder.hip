@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "lt_device_prims.h"
+#include "lt_encoder_tile.h"
 #include "lt_env.h"
 #include "lt_host_check.h"
 #include "lt_internal.h"
@@ -46,8 +47,6 @@ static_assert(LT_RNN_ENCODER_TRAIN_MAX_LAYERS == LT_RNN_ENCODER_MAX_LAYERS, "lt_
 static_assert(LT_ENCODER_MAX_LAYERS == LT_MLP_MAX_LAYERS, "lt_encoder.h states its layer limit as lt_mlp's");
 
 namespace {
-
-using lt::f32x4;
 
 constexpr int kMaxL = LT_ENCODER_MAX_LAYERS;
 constexpr int kLdsBytes = 160 * 1024;
@@ -65,45 +64,7 @@ struct EncNet {
 struct EncArgs { EncNet net[2]; int n, RB, PM, off_b, off_panel; };  // off_*: float offsets of buffer B and the panel in LDS
 
 __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-__host__ __device__ inline int lds_stride(int width) { return round_up(width, 16) + 8; }
-
-__device__ __forceinline__ float activate(int kind, float x) {
-  if (kind == LT_ACT_ELU) return x > 0.f ? x : expm1f(x);
-  if (kind == LT_ACT_RELU) return x > 0.f ? x : 0.f;
-  if (kind == LT_ACT_TANH) return tanhf(x);
-  return x;
-}
-
-// floor(2^32 / d) + 1 (d a power of two: 2^32 / d): __umulhi(i, .) is i / d exactly while i * d < 2^32 - here i < 64 * 512, d <= 512
-__device__ __forceinline__ unsigned div_magic(int d) { return 0xFFFFFFFFu / (unsigned)d + 1u; }
-
-// Stages a [rows][cols] tile (elements of type V: float, or f32x4 where the source allows 16-byte loads; cols in elements) into LDS rows
-// of dst_stride FLOATS: element (r, c) from src + r * src_stride floats where r < rows_ok and c < cols_ok, else zeros.  The loads of a
-// thread are independent and U of them are in flight before the first LDS write: a load per loop trip would expose the whole
-// global-memory latency once per element (measured: 110 us of a 112 us launch at 4096 rows).
-template <int U, class V>
-__device__ __forceinline__ void stage(const float* __restrict__ src, long long src_stride, int rows_ok, int cols_ok, float* __restrict__ dst,
-                                      int dst_stride, int rows, int cols, int tid) {
-  constexpr int VW = sizeof(V) / sizeof(float);
-  const int total = rows * cols;
-  const unsigned magic = div_magic(cols);
-  for (int base = 0; base < total; base += 256 * U) {
-    V v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int idx = base + 256 * u + tid;
-      const int r = (int)__umulhi((unsigned)idx, magic), c = idx - r * cols;
-      v[u] = V{};
-      if (idx < total && r < rows_ok && c < cols_ok) v[u] = *(const V*)(src + (long long)r * src_stride + VW * c);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int idx = base + 256 * u + tid;
-      const int r = (int)__umulhi((unsigned)idx, magic), c = idx - r * cols;
-      if (idx < total) *(V*)(dst + r * dst_stride + VW * c) = v[u];
-    }
-  }
-}
+// (lds_stride, activate, stage, stage_panel and tile_sum: lt_encoder_tile.h)
 
 __global__ __launch_bounds__(256) void lt_encoder_kernel(const EncArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -155,31 +116,14 @@ __global__ __launch_bounds__(256) void lt_encoder_kernel(const EncArgs a) {
       // left the previous panel - and, for a layer's first panel, until the previous layer's activations are all written
       const int pm16 = min(PM, round_up(O - p0, 16)), mtiles = pm16 / 16;
       __syncthreads();
-      if ((K & 3) == 0 && ((uintptr_t)w & 15) == 0)
-        stage<8, f32x4>(w + (long long)p0 * K, K, O - p0, K / 4, panel, kp, pm16, K16 / 4, tid);
-      else
-        stage<16, float>(w + (long long)p0 * K, K, O - p0, K, panel, kp, pm16, K16, tid);
+      stage_panel(w, K, O, p0, pm16, panel, tid);
       __syncthreads();
       for (int tile = wave; tile < mtiles * nsub; tile += 4) {
         const int mt = tile % mtiles, s = tile / mtiles;
         const float* ap = panel + (16 * mt + i) * kp + 4 * q;
         const float* bp = in + (16 * s + i) * sin + 4 * q;
-        f32x4 acc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int b0 = 0; b0 < nblk; b0 += 4) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (b0 + u < nblk) {
-              const f32x4 wv = *(const f32x4*)(ap + 16 * (b0 + u));
-              const f32x4 xv = *(const f32x4*)(bp + 16 * (b0 + u));
-#pragma unroll
-              for (int e = 0; e < 4; ++e) acc[u] = lt::mfma_16x16x4(wv[e], xv[e], acc[u]);
-            }
-          }
-        }
         // epilogue: sum[v] of lane (i, q) is D[4 q + v][i] = feature f0 + v of row 16 s + i
-        const f32x4 sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        const f32x4 sum = tile_sum(ap, bp, nblk);
         const int f0 = p0 + 16 * mt + 4 * q, row = 16 * s + i;
         const bool row_ok = row < rows;
         const long long gr = r0 + row;
@@ -335,22 +279,8 @@ __global__ __launch_bounds__(256) void lt_rnn_encoder_backward_kernel(const EncG
         const int mt = tile % mtiles, s = tile / mtiles;
         const float* ap = panel + (16 * mt + i) * op + 4 * q;
         const float* bp = in + (16 * s + i) * sin + 4 * q;
-        f32x4 acc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int b0 = 0; b0 < nblk; b0 += 4) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            if (b0 + u < nblk) {
-              const f32x4 wv = *(const f32x4*)(ap + 16 * (b0 + u));
-              const f32x4 gv = *(const f32x4*)(bp + 16 * (b0 + u));
-#pragma unroll
-              for (int e = 0; e < 4; ++e) acc[u] = lt::mfma_16x16x4(wv[e], gv[e], acc[u]);
-            }
-          }
-        }
         // epilogue: sum[v] of lane (i, q) is D[4 q + v][i] = input feature f0 + v of row 16 s + i
-        const f32x4 sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        const f32x4 sum = tile_sum(ap, bp, nblk);
         const int f0 = p0 + 16 * mt + 4 * q, row = 16 * s + i;
         const bool row_ok = row < rows;
         const long long gr = r0 + row;

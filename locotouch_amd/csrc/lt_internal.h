@@ -51,3 +51,10 @@ void lt_set_error(const char* msg);
 // at the first call per (kernel, device) and remembered once it is set (thread-safe; one size per kernel).  Returns a hipError_t
 // value as int.
 int lt_ensure_dynamic_lds(const void* kernel, int bytes);
+
+// implemented in lt_policy.hip ----------------------------------------------------------------------
+// The memory launch of lt_policy_step (lt_policy_memory_kernel) on validated operands: an LT_* status.  rnn_type: lt_policy_rnn; x: rows
+// of I columns read in place, x_stride floats apart; mem->norm_mean / norm_std: [I] or both NULL.
+struct lt_policy_memory;
+int lt_policy_memory_launch(int rnn_type, const lt_policy_memory* mem, int I, int H, const float* x, long long x_stride, const uint8_t* done_mask,
+                            const float* h_in, const float* c_in, float* h_out, float* c_out, int n, void* stream);

@@ -61,6 +61,14 @@ template <class Cell, bool TRAIN> using step_args = std::conditional_t<TRAIN, Se
 constexpr int kLdsBytes = 160 * 1024;
 
 __host__ __device__ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// The IEEE quotient (v_div_scale / v_div_fmas / v_div_fixup): the build's -freciprocal-math turns `/` - and `__fdiv_rn`, which this
+// toolchain defines as `/` - into a multiplication by v_rcp_f32, one ulp off where torch's normaliser is not.
+__device__ __forceinline__ float ieee_div(float a, float b) {
+#pragma clang fp reciprocal(off)
+  return a / b;
+}
+
 // LDS row stride: IP + H + 8 is an odd multiple of 8 floats (IP, H multiples of 16): the 16 lanes of a ds_read_b128 lane group (rows
 // {0-3, 12-15} at one q, rows 4-11 at the next) then start at 16 distinct multiples of 4 banks
 __host__ __device__ inline int panel_stride(int I, int H) { return round_up(I, 16) + H + 8; }

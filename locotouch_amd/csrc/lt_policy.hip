@@ -63,7 +63,9 @@ template <class Cell> __global__ __launch_bounds__(256) void lt_policy_memory_ke
     float v = 0.f;
     if (row0 + r < n && k < I) {
       v = a.x[(long long)(row0 + r) * a.xstride + k];
-      if (a.mean) v = __fdiv_rn(v - a.mean[k], a.std[k] + a.eps);  // (a correctly rounded quotient, whatever -freciprocal-math makes of `/`)
+      // (the torch normaliser's statement bit for bit: the IEEE quotient.  `__fdiv_rn` is not: this toolchain defines it as `/`, which
+      // -freciprocal-math makes v_rcp_f32 and a multiplication, one ulp off now and then)
+      if (a.mean) v = ieee_div(v - a.mean[k], a.std[k] + a.eps);
     }
     rows[r * S + k] = v;
   }
@@ -190,6 +192,19 @@ template <class Cell> int launch_memory(const PolicyArgs& a, void* stream) {
 
 }  // namespace
 
+// The memory launch alone, on operands its caller has validated (lt_internal.h): lt_policy_step below, and lt_policy_encoder_step
+// (csrc/lt_policy_encoder.hip), which hands it the tail columns of its rows and the tail slices of the statistics.
+int lt_policy_memory_launch(int rnn_type, const lt_policy_memory* mem, int I, int H, const float* x, long long x_stride, const uint8_t* done_mask,
+                            const float* h_in, const float* c_in, float* h_out, float* c_out, int n, void* stream) {
+  PolicyArgs a;
+  a.x = x; a.xstride = x_stride; a.done = done_mask;
+  a.w_ih = mem->w_ih; a.w_hh = mem->w_hh; a.b_ih = mem->b_ih; a.b_hh = mem->b_hh;
+  a.mean = mem->norm_mean; a.std = mem->norm_std; a.eps = mem->norm_eps;
+  a.s_in[0] = h_in; a.s_in[1] = c_in; a.s_out[0] = h_out; a.s_out[1] = c_out;
+  a.n = n; a.I = I; a.IP = round_up(I, 16); a.H = H; a.S = a.IP + H + 4;
+  return rnn_type == LT_POLICY_RNN_LSTM ? launch_memory<LstmCell>(a, stream) : launch_memory<GruCell>(a, stream);
+}
+
 extern "C" {
 
 int lt_policy_validate(const lt_policy_desc* desc) { return check_desc("lt_policy_validate", desc); }
@@ -231,13 +246,8 @@ int lt_policy_step(const lt_policy_desc* desc, const lt_policy_memory* mem, cons
     for (const float* in : {h_in, c_in})
       if (e.p && in && overlaps(e.p, nH, in, nH)) return refuse(fn, "", e.name, "a buffer that does not overlap h_in / c_in (ping-pong)");
 
-  PolicyArgs a;
-  a.x = obs; a.xstride = obs_row_stride; a.done = done_mask;
-  a.w_ih = mem->w_ih; a.w_hh = mem->w_hh; a.b_ih = mem->b_ih; a.b_hh = mem->b_hh;
-  a.mean = mem->norm_mean; a.std = mem->norm_std; a.eps = mem->norm_eps;
-  a.s_in[0] = h_in; a.s_in[1] = c_in; a.s_out[0] = h_out; a.s_out[1] = c_out;
-  a.n = (int)n; a.I = I; a.IP = round_up(I, 16); a.H = H; a.S = a.IP + H + 4;
-  if (const int rc = lstm ? launch_memory<LstmCell>(a, stream) : launch_memory<GruCell>(a, stream)) return rc;
+  if (const int rc = lt_policy_memory_launch(desc->rnn_type, mem, I, H, obs, obs_row_stride, done_mask, h_in, c_in, h_out, c_out, (int)n, stream))
+    return rc;
   return lt_mlp_forward(&desc->actor, actor_packed, h_out, n, actions_out, stream);
 }
 

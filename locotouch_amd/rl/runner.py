@@ -29,7 +29,7 @@ class OnPolicyRunner:
         self.policy_cfg = dict(train_cfg["policy"])
         self.device, self.env, self.dist = device, env, dist or Dist()
         obs, extras = env.get_observations()
-        num_obs = obs.shape[1]
+        self.num_obs = num_obs = obs.shape[1]
         num_critic_obs = extras["observations"]["critic"].shape[1] if "critic" in extras["observations"] else num_obs
         from . import modules as _m
 
@@ -305,15 +305,27 @@ class OnPolicyRunner:
         return self.alg.actor_critic.actor.state_dict()
 
     def get_inference_policy(self, device=None, fused=False):  # reference on_policy_runner.py:424-436
-        """`fused=True` with a recurrent policy: the opt-in front of rl/fused_policy.py (one memory launch and one actor launch per
-        step, the normaliser folded into the first); it raises for what the kernels do not serve.  Everything else is the reference's."""
+        """`fused=True`: the opt-in fronts of rl/fused_policy.py, the normaliser folded into their first launch - `FusedRecurrentPolicy` for
+        a recurrent policy (one memory launch and one actor launch per step), `FusedEncoderPolicy` for an ActorCriticRNNEncoder (two
+        launches) or an ActorCriticEncoder (one) whose parameters are on a GPU; they raise for what the kernels do not serve.  Everything
+        else is the reference's."""
         self.eval_mode()
         if device is not None:
             self.alg.actor_critic.to(device)
-        if fused and type(self.alg.actor_critic) is ActorCriticRNNEncoder:
-            raise NotImplementedError("get_inference_policy(fused=True): ActorCriticRNNEncoder is not served (the fused inference step of "
-                                      "rl/fused_policy.py is memory -> actor, ActorCriticRecurrent's shape); fused=False steps it through its modules")
-        if fused and getattr(self.alg.actor_critic, "is_recurrent", False):
+        ac = self.alg.actor_critic
+        if fused and type(ac) in (ActorCriticEncoder, ActorCriticRNNEncoder):
+            if next(ac.parameters()).is_cuda:
+                from .fused_policy import FusedEncoderPolicy
+
+                if self.empirical_normalization and device is not None:
+                    self.obs_normalizer.to(device)
+                return FusedEncoderPolicy.for_actor_critic(ac, self.obs_normalizer if self.empirical_normalization else None, obs_dim=self.num_obs)
+            if type(ac) is ActorCriticRNNEncoder:
+                raise NotImplementedError("get_inference_policy(fused=True): the fused inference step of an ActorCriticRNNEncoder "
+                                          "(rl/fused_policy.py, FusedEncoderPolicy) runs on a GPU only and this policy is on the CPU; "
+                                          "fused=False steps it through its modules")
+            # (an ActorCriticEncoder on the CPU: the eager policy below, as ever)
+        elif fused and getattr(ac, "is_recurrent", False):
             from .fused_policy import FusedRecurrentPolicy
 
             if self.empirical_normalization and device is not None:

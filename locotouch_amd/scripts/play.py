@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Play a trained policy: the reference's `locotouch/scripts/play.py` flow on the MI355X-native env: the loop steps the policy, prints
 episode statistics, optionally exports the actor (with its memory, for a recurrent policy) as TorchScript for the robot-side runtime,
-with `--fused_policy` serves a recurrent policy from the fused HIP inference step (include/lt_policy.h), and with `--video` records env 0 (animated
+with `--fused_policy` serves a recurrent or an encoder policy from its fused HIP inference step (include/lt_policy.h,
+include/lt_policy_encoder.h), and with `--video` records env 0 (animated
 PNG, locotouch_amd/video.py) into <run>/videos/play.  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
 `policy` and `empirical_normalization` entries take the place of the registered agent cfg's, so a recurrent checkpoint loads.
 
@@ -28,7 +29,8 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=None, help="stop after this many env steps (default: run until interrupted)")
     ap.add_argument("--export", action="store_true", help="write <run>/exported/policy.pt (TorchScript: normaliser -> actor)")
     ap.add_argument("--fused_policy", action="store_true",
-                    help="recurrent policies: step through the fused HIP inference step (rl/fused_policy.py) and reset the memory of finished envs")
+                    help="ActorCriticRecurrent, ActorCriticEncoder and ActorCriticRNNEncoder policies: step through the fused HIP inference "
+                         "step (rl/fused_policy.py) and reset the memory of finished envs")
     from locotouch_amd.video import add_video_args
 
     add_video_args(ap)
