@@ -10,23 +10,14 @@ import torch
 from locotouch_amd import _abi
 from locotouch_amd.distill import Student, distillation_cfg
 from tests import distill_synth as S
+from tests import student_ref as R
 
 TASK = "Isaac-RandCylinderTransportStudent_SingleBinaryTac_CNNRNN_Mon-LocoTouch-v1"
 C = _abi.CONSTS
 
 
 def registered_desc():
-    d = _abi.LtStudentDesc()
-    d.img_channels, d.img_height, d.img_width, d.num_convs, d.use_maxpool = 2, 17, 13, 3, 1
-    for i, (c, k, s) in enumerate(zip((24, 24, 24), (4, 3, 2), (2, 1, 1))):
-        d.conv_channels[i], d.conv_kernel[i], d.conv_stride[i], d.conv_padding[i] = c, k, s, 0
-    d.conv_activation, d.conv_norm, d.head_out = C["LT_ACT_RELU"], 0, 64
-    d.rnn_type, d.rnn_layers, d.rnn_hidden, d.proprio_dim = _abi.LT_STUDENT_RNN_GRU, 1, 512, 270
-    for m, dims in ((d.encoder, (512, 256, 128, 64, 64)), (d.backbone, (334, 512, 256, 128, 12))):
-        m.num_layers, m.activation, m.input_format = len(dims) - 1, C["LT_ACT_ELU"], C["LT_ROWS_F32"]
-        for i, v in enumerate(dims):
-            m.dims[i] = v
-    return d
+    return R.desc_of(R.CASES["reg"])
 
 
 def test_header_is_part_of_the_abi_and_bound_from_itself():
@@ -72,6 +63,41 @@ def test_size_queries_agree_with_the_documented_layout():
         assert 1 <= lib.lt_student_step_launches(ctypes.byref(d), n) <= 4
     with pytest.raises(RuntimeError, match="lt_student_ws_floats"):
         _abi.call("lt_student_ws_floats", d, 0, ctypes.byref(size))
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_size_queries_agree_with_the_documented_layout_over_the_family(name):
+    case = R.CASES[name]
+    d = R.desc_of(case)
+    lib = _abi.load()
+    assert lib.lt_student_validate(ctypes.byref(d)) == 0, lib.lt_last_error().decode()
+    pad16, pad4 = R.pad16, R.pad4
+    maps = R.geometry(case)
+    D, H, P = case["D"], case["H"], case["P"]
+    want = 0
+    for (cin, _, _), (c, k, _) in zip(maps, case["convs"]):
+        want += pad4(cin * k * k * c) + pad4(c)                  # transposed weight [Cin K K][Cout], bias
+    flat = maps[-1][0] * maps[-1][1] * maps[-1][2]
+    want += pad4(flat * D) + D                                   # head [flat][D], bias
+    want += 3 * H * (D + H) + 2 * 3 * H                          # [W_ih | W_hh], b_ih, b_hh
+    cat_pad = pad16(P + pad16(case["enc"][-1]))                  # the backbone's input row: proprioception | padded embedding
+    assert case["bb"][0] == P + case["enc"][-1] and cat_pad == R.cat_pad(case)
+    for dims in (case["enc"], (cat_pad,) + tuple(case["bb"][1:])):
+        for a, b in zip(dims[:-1], dims[1:]):
+            want += pad16(b) * pad16(a) + pad16(b)
+    if name == "wide":
+        assert cat_pad == 528 and flat == 1444
+    if name == "reg":
+        assert cat_pad == 336 and flat == 192
+    blocks, total = R.packed_blocks(case)
+    assert total == want and all(off % 4 == 0 for _, off, _, _ in blocks)
+    size = ctypes.c_size_t()
+    _abi.call("lt_student_packed_floats", d, ctypes.byref(size))
+    assert size.value == want
+    for n in R.NS + (4112,):
+        _abi.call("lt_student_ws_floats", d, n, ctypes.byref(size))
+        assert size.value == n * (D + H)
+        assert 1 <= lib.lt_student_step_launches(ctypes.byref(d), n) <= 4
 
 
 @pytest.mark.parametrize("field, mutate", [

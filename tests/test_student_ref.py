@@ -1,9 +1,12 @@
 """The float64 restatement of the student step (tests/student_ref.py) against `Student.forward` run in float64 on the CPU and
-against the reference's own step vectors in tests/golden/distill.npz.  CPU only."""
+against the reference's own step vectors in tests/golden/distill.npz; over the descriptor family of `student_ref.CASES`, its stages
+against torch's own modules in float64, and the power of each case's inputs to show a fault.  CPU only."""
 import os
 
 import numpy as np
+import pytest
 import torch
+import torch.nn as nn
 
 from locotouch_amd.distill import Student, distillation_cfg
 from tests import distill_synth as S
@@ -54,3 +57,132 @@ def test_restatement_equals_the_reference_step_vectors(tmp_path):
         assert abs(np.abs(h).sum() - gold["st_step_hidden_abs_sum"][i]) < 1e-3
         if i == 1:
             h = np.zeros_like(h)
+
+
+# ---- the descriptor family (student_ref.CASES) ------------------------------------------------------------------------------------------
+N = 130
+
+
+def torch_stages(P, proprio, tactile, h, done, dtype):
+    """The step from torch's OWN modules (nn.Conv2d, nn.MaxPool2d, nn.GRU, nn.Linear, nn.ELU) in `dtype`: the stages of R.stages."""
+    t = lambda a: torch.as_tensor(np.asarray(a), dtype=dtype)  # noqa: E731
+
+    def load(m, w, b):
+        with torch.no_grad():
+            m.weight.copy_(t(w)), m.bias.copy_(t(b))
+        return m
+
+    def seq(layers):
+        mods = []
+        for l, (w, b) in enumerate(layers):
+            mods += [load(nn.Linear(w.shape[1], w.shape[0]).to(dtype), w, b)] + ([nn.ELU()] if l < len(layers) - 1 else [])
+        return nn.Sequential(*mods)
+
+    n = tactile.shape[0]
+    out = dict(maps=[])
+    with torch.no_grad():
+        x = t(tactile).reshape(n, *P["img"])
+        for i, (w, b, s) in enumerate(P["convs"]):
+            x = torch.relu(load(nn.Conv2d(w.shape[1], w.shape[0], w.shape[2], stride=s).to(dtype), w, b)(x))
+            if i in P["pool"]:
+                x = nn.MaxPool2d(P["pool"][i])(x)
+            out["maps"].append(x)
+        out["head"] = seq(P["head"])(x.reshape(n, -1))
+        w_ih, w_hh, b_ih, b_hh = P["gru"]
+        gru = nn.GRU(w_ih.shape[1], w_hh.shape[1]).to(dtype)
+        for name, a in zip(("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"), P["gru"]):
+            with torch.no_grad():
+                getattr(gru, name).copy_(t(a))
+        h0 = t(h)
+        if done is not None:
+            h0 = torch.where(torch.as_tensor(np.asarray(done) != 0)[:, None], torch.zeros_like(h0), h0)
+        out["h_new"] = gru(out["head"][None], h0[None])[1][0]
+        H = w_hh.shape[1]
+        gi, gh = out["head"] @ t(w_ih).T + t(b_ih), h0 @ t(w_hh).T + t(b_hh)
+        out["r"], out["z"] = torch.sigmoid(gi[:, :H] + gh[:, :H]), torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+        out["n"] = torch.tanh(gi[:, 2 * H:] + out["r"] * gh[:, 2 * H:])
+        out["emb"] = seq(P["enc"])(out["h_new"])
+        out["actions"] = seq(P["bb"])(torch.cat([t(proprio).reshape(n, -1), out["emb"]], dim=1))
+    return out
+
+
+def case_inputs(name, n=N, nan_in_done_rows=True):
+    """(P, proprio, tactile, h, done) of a case at its fixed seed, the mixed mask in front of the step; the done rows hold NaN."""
+    case, seed = R.CASES[name], R.SEEDS[name]
+    prop, tac, h = R.random_inputs(case, n, seed)
+    done = R.mixed_mask(n, seed)
+    if nan_in_done_rows:
+        h = np.where(done[:, None] != 0, np.nan, h)
+    return R.random_params(case, seed), prop, tac, h, done
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_stages_equal_torchs_own_modules_in_float64(name):
+    P, prop, tac, h, done = case_inputs(name, n=17)
+    got = R.stages(P, prop, tac, h, done)
+    want = torch_stages(P, prop, tac, h, done, torch.float64)
+    assert [m.shape[1:] for m in got["maps"]] == list(R.geometry(R.CASES[name])[1:])
+    assert np.isfinite(got["h_new"]).all() and np.isfinite(got["actions"]).all()   # the NaN of the done rows was selected away
+    for key in ("head", "r", "z", "n", "h_new", "emb", "actions"):
+        np.testing.assert_allclose(got[key], want[key].numpy(), rtol=0, atol=1e-12, err_msg=key)
+    for l, (a, b) in enumerate(zip(got["maps"], want["maps"], strict=True)):
+        np.testing.assert_allclose(a, b.numpy(), rtol=0, atol=1e-12, err_msg=f"map {l}")
+    a, hn = R.step(P, prop, tac, h, done)
+    assert np.array_equal(a, got["actions"]) and np.array_equal(hn, got["h_new"])
+    a0, h0 = R.step(P, prop, tac, np.where(done[:, None] != 0, 0.0, h))             # a done row = the row from a zero state
+    assert np.array_equal(a0, a) and np.array_equal(h0, hn)
+
+
+def _errors(T32_step, want):
+    a, hn = T32_step
+    return (float(np.abs(hn.double().numpy() - want["h_new"]).max()), float(np.abs(a.double().numpy() - want["actions"]).max()))
+
+
+def _allowance(err32, ref):
+    """Section "Accuracy" of tests/test_hip_student_f64.py: what a kernel may be off by, given the f32 composition's error."""
+    return max(R.FACTOR * err32, R.ulp32(float(np.abs(ref).max())))
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_the_f32_composition_stays_under_the_rule_against_the_stages(name):
+    """The yardstick of the GPU tests (R.compose: unfold + matmul, F.linear) run in f32 on the CPU, judged by the rule it will judge the
+    kernels by, with torch's own modules in f32 as ITS yardstick: the reference, the composition and the rule agree."""
+    P, prop, tac, h, done = case_inputs(name, nan_in_done_rows=False)
+    want = R.stages(P, prop, tac, h, done)
+    t32 = lambda a: torch.as_tensor(a, dtype=torch.float32)  # noqa: E731
+    with torch.no_grad():
+        comp = R.compose(R.to_torch(P, "cpu", torch.float32), t32(prop), t32(tac), t32(h), torch.as_tensor(done))
+    mods = torch_stages(P, prop, tac, h, done, torch.float32)
+    for what, e_c, e_m, ref in zip(("h", "actions"), _errors(comp, want), _errors((mods["actions"], mods["h_new"]), want), (want["h_new"], want["actions"])):
+        bound = _allowance(e_m, ref)
+        print(f"\nSTUDENTF32 case={name} n={N} {what}: max |err| vs f64  composition {e_c:.3e}  modules {e_m:.3e}  bound {bound:.3e}")
+        assert e_c <= bound, (name, what, e_c, e_m, bound)
+    # in float64 the composition IS the restatement
+    with torch.no_grad():
+        a64, h64 = R.compose(R.to_torch(P, "cpu", torch.float64), *(torch.as_tensor(v) for v in (prop, tac, h, done)))
+    np.testing.assert_allclose(a64.numpy(), want["actions"], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(h64.numpy(), want["h_new"], rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_inputs_have_the_power_to_show_every_fault(name):
+    """A condition on the SEEDS, not a measurement: at the seed student_ref.SEEDS fixes for the case, every fault of R.faults() moves
+    h_new or the actions by at least 1000 times the error of the plain f32 composition against float64 (and 500 ulps) - 500 times what
+    the GPU test allows a kernel.  A kernel with that fault cannot pass there."""
+    P, prop, tac, h, done = case_inputs(name)
+    want = R.stages(P, prop, tac, h, done)
+    t32 = lambda a: torch.as_tensor(np.nan_to_num(a), dtype=torch.float32)  # noqa: E731
+    with torch.no_grad():
+        e_h, e_a = _errors(R.compose(R.to_torch(P, "cpu", torch.float32), t32(prop), t32(tac), t32(h), torch.as_tensor(done)), want)
+    need_h, need_a = 500.0 * _allowance(e_h, want["h_new"]), 500.0 * _allowance(e_a, want["actions"])
+    print(f"\nSTUDENTFAULT case={name} seed={R.SEEDS[name]} n={N}: f32 composition error h {e_h:.2e} actions {e_a:.2e}")
+    tried = 0
+    for fault, applies, mutate in R.faults():
+        if not applies(P):
+            continue
+        got = R.stages(mutate(P), prop, tac, np.nan_to_num(h, nan=0.25) if fault == "done mask ignored" else h, done)
+        d_h, d_a = float(np.abs(got["h_new"] - want["h_new"]).max()), float(np.abs(got["actions"] - want["actions"]).max())
+        print(f"STUDENTFAULT case={name} {fault}: moves h by {d_h:.2e} ({d_h / e_h:.1e} x f32 error), actions by {d_a:.2e} ({d_a / e_a:.1e} x)")
+        assert d_h >= need_h or d_a >= need_a, (name, fault, d_h, need_h, d_a, need_a)
+        tried += 1
+    assert tried >= 11 and (name != "odd" or "pool takes the row the floor drops" in [f for f, ap, _ in R.faults() if ap(P)])
