@@ -11,8 +11,9 @@ An `ActorCriticRNNEncoder` updates through the eager loop, or - behind the opt-i
 of env blocks without an autograd graph (`_direct_rnn_encoder_update`, include/lt_rnn_encoder_train.h).
 The updates without an autograd graph (`_direct_update`, `_direct_encoder_update`, `_direct_recurrent_update`,
 `_direct_rnn_encoder_update`) share one skeleton -
-`_direct_begin`, `_direct_loss_and_rule` per step, `_direct_end` with the update's one host read - and keep only their own forward and
-backward passes; the updates that run the loss as torch ops share `_op_chain_loss`.
+`_direct_begin`, `_direct_loss_and_rule` per step (for the three that need dx inside `_direct_stacks_step`), `_direct_end` with the update's
+one host read - and keep only their own forward and backward passes; the updates that run the loss as torch ops share `_op_chain_loss`.
+What the opt-in keys need is stated once (`_keys_unsupported`), and `_update_form` names the update that `update()` runs.
 
 Data parallelism (new): gradients live in one flat fp32 bucket that is all-reduced (mean) between
 `backward()` and the gradient clip, and the KL estimate is all-reduced before the learning-rate decision.
@@ -50,53 +51,19 @@ class PPO:
         self.fused_recurrent_update = bool(unused.get("fused_recurrent_update", False))
         # opt-in: `fused_recurrent_update` serves GRU memories as well (csrc/lt_memory_gru.hip); on its own it does nothing
         self.fused_gru_memories = bool(unused.get("fused_gru_memories", False))
-        # opt-in, on top of `fused_recurrent_update`: that update without an autograd graph and without a host read between its steps
-        # (_direct_recurrent_update); what it cannot serve is refused here and below, never run on another path
+        # opt-in, on top of `fused_recurrent_update`: that update without an autograd graph or a host read between its steps (_direct_recurrent_update)
         self.direct_recurrent_update = bool(unused.get("direct_recurrent_update", False))
-        # opt-in: an `ActorCriticEncoder` updates without an autograd graph and without a host read between its minibatch steps
-        # (_direct_encoder_update, csrc/lt_encoder.hip); what it cannot serve is refused here and below, never run on another path
+        # opt-in: an `ActorCriticEncoder` updates without an autograd graph or a host read between its minibatch steps (_direct_encoder_update, csrc/lt_encoder.hip)
         self.fused_encoder_policy = bool(unused.get("fused_encoder_policy", False))
         self._encoders = None  # rl/encoder.py EncoderPair, built at the first update (the storage names the rows' widths)
         # opt-in: an `ActorCriticRNNEncoder` updates on whole rollouts of env blocks without padding, an autograd graph or a host read
-        # between its steps (_direct_rnn_encoder_update, include/lt_rnn_encoder_train.h); what it cannot serve is refused below
+        # between its steps (_direct_rnn_encoder_update, include/lt_rnn_encoder_train.h)
         self.direct_rnn_encoder_update = bool(unused.get("direct_rnn_encoder_update", False))
         self._rnn_encoders = None  # rl/encoder.py RnnEncoderPair, built at the first update
-        if type(actor_critic).__name__ == "ActorCriticRNNEncoder":  # (first, whatever the device: the keys of the other kinds do not serve this class)
-            for key in ("fused_encoder_policy", "direct_recurrent_update", "fused_recurrent_update"):
-                if getattr(self, key):
-                    raise ValueError(f"{key}: the policy is an ActorCriticRNNEncoder: its update is the eager one (the key serves "
-                                     f"{'ActorCriticEncoder' if key == 'fused_encoder_policy' else 'ActorCriticRecurrent'})")
-        if self.fused_encoder_policy:
-            if self.fused_recurrent_update or self.direct_recurrent_update or self.fused_gru_memories:
-                raise ValueError("fused_encoder_policy: the recurrent keys (fused_recurrent_update, direct_recurrent_update, fused_gru_memories) "
-                                 "belong to ActorCriticRecurrent: an encoder policy has no memories")
-            if self.symmetry is not None:
-                raise ValueError("fused_encoder_policy: symmetry_cfg is not served for an encoder policy (the mirror tables cover the plain ActorCritic's rows)")
-            if self.dist.world_size > 1:
-                raise ValueError(f"fused_encoder_policy: dist.world_size is {self.dist.world_size}: the collectives of this form are not "
-                                 "covered by a multi-rank test, it runs on one rank only")
-            if not on_gpu:
-                raise ValueError(f"fused_encoder_policy: the device is {device!r}: its kernels run on a GPU only")
-        if self.direct_recurrent_update:
-            if not self.fused_recurrent_update:
-                raise ValueError("direct_recurrent_update: it is a form of the whole-rollout update: set fused_recurrent_update=True as well")
-            if not on_gpu:
-                raise ValueError(f"direct_recurrent_update: the device is {device!r}: its kernels run on a GPU only")
-            if self.dist.world_size > 1:
-                raise ValueError(f"direct_recurrent_update: dist.world_size is {self.dist.world_size}: the collectives of this form are not "
-                                 "covered by a multi-rank test, it runs on one rank only")
-            why = self._recurrent_update_unsupported()
-            if why is not None:
-                raise ValueError(f"direct_recurrent_update: {why}")
-        if self.fused_recurrent_update:
-            why = self._recurrent_update_unsupported()
-            if why is not None:
-                raise ValueError(f"fused_recurrent_update: {why}")
-        if self.direct_rnn_encoder_update:
-            why = self._direct_rnn_encoder_unsupported(kernels=False)  # (the rest below, with the optimizer's flat bucket there)
-            if why is not None:
-                raise ValueError(f"direct_rnn_encoder_update: {why}")
         self._pair = None
+        why = self._keys_unsupported(flat_bucket=False)  # (before anything is broadcast or flattened; the rest below, with the bucket there)
+        if why is not None:
+            raise ValueError(why)
         if on_gpu and bool(unused.get("tuned_gemms", True)):
             from . import tuned_gemms
 
@@ -125,18 +92,55 @@ class PPO:
 
             self._flat_adam = FlatAdam(self.optimizer)
             self._flat_grad = self._flat_adam.flat_g  # also the all-reduce bucket of a multi-rank job
-        if self.direct_recurrent_update:
-            why = self._direct_recurrent_unsupported()
-            if why is not None:
-                raise ValueError(f"direct_recurrent_update: {why}")
+        why = self._keys_unsupported(flat_bucket=True)
+        if why is not None:
+            raise ValueError(why)
+
+    def _keys_unsupported(self, flat_bucket: bool) -> str | None:
+        """Why the opt-in keys that are set cannot be served, with the key's name in front (None: they can): what is refused is never
+        run on another path.  `flat_bucket`: the optimizer's flat bucket exists, so what a form needs of it and of the kernels behind
+        it is asked as well (`_direct_stacks_unsupported` builds `self._pair`); without it only what can be said before that."""
+        ac, kind = self.actor_critic, type(self.actor_critic).__name__
+        ranks = device = None  # what every graph-free opt-in form needs: one rank and a GPU
+        if self.dist.world_size > 1:
+            ranks = (f"dist.world_size is {self.dist.world_size}: the collectives of this form are not covered by a multi-rank test, it runs "
+                     "on one rank only")
+        if torch.device(self.device).type != "cuda":
+            device = f"the device is {self.device!r}: its kernels run on a GPU only"
+        if kind == "ActorCriticRNNEncoder":  # (first, whatever the device: the keys of the other kinds do not serve this class)
+            for key in ("fused_encoder_policy", "direct_recurrent_update", "fused_recurrent_update"):
+                if getattr(self, key):
+                    return (f"{key}: the policy is an ActorCriticRNNEncoder: its update is the eager one (the key serves "
+                            f"{'ActorCriticEncoder' if key == 'fused_encoder_policy' else 'ActorCriticRecurrent'})")
         if self.fused_encoder_policy:
-            why = self._direct_encoder_unsupported()
+            if self.fused_recurrent_update or self.direct_recurrent_update or self.fused_gru_memories:
+                return ("fused_encoder_policy: the recurrent keys (fused_recurrent_update, direct_recurrent_update, fused_gru_memories) "
+                        "belong to ActorCriticRecurrent: an encoder policy has no memories")
+            if self.symmetry is not None:
+                return "fused_encoder_policy: symmetry_cfg is not served for an encoder policy (the mirror tables cover the plain ActorCritic's rows)"
+            why = ranks or device or (self._direct_encoder_unsupported() if flat_bucket else None)
             if why is not None:
-                raise ValueError(f"fused_encoder_policy: {why}")
+                return f"fused_encoder_policy: {why}"
+        if self.direct_recurrent_update:
+            if not self.fused_recurrent_update:
+                return "direct_recurrent_update: it is a form of the whole-rollout update: set fused_recurrent_update=True as well"
+            why = device or ranks or self._recurrent_update_unsupported() or (self._direct_recurrent_unsupported() if flat_bucket else None)
+            if why is not None:
+                return f"direct_recurrent_update: {why}"
+        if self.fused_recurrent_update:
+            why = self._recurrent_update_unsupported()
+            if why is not None:
+                return f"fused_recurrent_update: {why}"
         if self.direct_rnn_encoder_update:
-            why = self._direct_rnn_encoder_unsupported()
+            if kind != "ActorCriticRNNEncoder":
+                why = f"the policy is a {kind}, not an ActorCriticRNNEncoder"
+            elif not ac.critic_with_encoder:
+                why = "the critic has no encoder"
+            else:  # (no word on symmetry_cfg: `_resolve_symmetry` has refused it for this class, whose `is_recurrent` is True)
+                why = ranks or device or (self._direct_rnn_encoder_unsupported() if flat_bucket else None)
             if why is not None:
-                raise ValueError(f"direct_rnn_encoder_update: {why}")
+                return f"direct_rnn_encoder_update: {why}"
+        return None
 
     @staticmethod
     def _resolve_symmetry(symmetry_cfg, actor_critic):
@@ -267,8 +271,6 @@ class PPO:
         stats = torch.zeros(3, device=obs.device)
         pair = self._packed_pair()
         std_p, std_is_log = std_param(ac)
-        if pair is not None and self._flat_adam is not None and self.direct_update and std_p.requires_grad:
-            return self._direct_update(pair)
         if pair is not None:
             pair.arm_domain_check()  # the first minibatch of the update reports the largest layer input (LT_MLP_INPUT_CLAMP)
         perm, mb = st.mini_batch_permutation(self.num_mini_batches)
@@ -303,7 +305,7 @@ class PPO:
 
     def _direct_update(self, pair, split_buckets: bool = True):
         """The update of the plain ActorCritic on the GPU with NO host read between its minibatch steps and no autograd graph.  The
-        skeleton it shares with `_direct_encoder_update` and `_direct_recurrent_update`: `_direct_begin` (device state, std, bucket
+        skeleton it shares with `_direct_encoder_update`, `_direct_recurrent_update` and `_direct_rnn_encoder_update`: `_direct_begin` (device state, std, bucket
         views, [`lt_adv_stats`]); per step a forward, `_direct_loss_and_rule` - ONE loss launch that also writes d loss / d (mu, value,
         std) (csrc/lt_ppo.hip) and the adaptive-KL learning-rate rule as a one-lane launch on a device scalar (`lt_ppo_lr_rule`,
         ppo.py:273-281) -, the two stacks' backward chains writing their gradients straight into the flat bucket (rl/mlp.py
@@ -382,7 +384,7 @@ class PPO:
         return self._direct_end(c, with_dx=False)
 
     def _direct_begin(self, key: str, pair, index, m: int, symmetric: bool = False):
-        """What the three graph-free updates set up alike, as one namespace: the storage's rows (`obs`, `cobs`, `small` with its
+        """What the graph-free updates set up alike, as one namespace: the storage's rows (`obs`, `cobs`, `small` with its
         one-column tensors as vectors), `a_dim`, the device `state` ([0] learning rate, [1..3] sums of (value loss, surrogate, entropy),
         with `symmetric` [4] of the symmetry loss) and its views `lr_dev` and `stats`, the bucket's `grad_of`, the std parameter
         (`std_p`, `std_is_log`, `std_c`), the `stream`, the armed domain check of `pair`, and `mb_stats`: `lt_adv_stats` of the
@@ -435,6 +437,15 @@ class PPO:
                 kl = self.dist.all_reduce_mean_(kl.clone())
         _abi.call("lt_ppo_lr_rule", kl, float(self.desired_kl or 0.0), 1e-5, 1e-2, 1.5, c.lr_dev, c.stats, out, c.grad_of[c.std_p], c.a_dim, c.stream)
         return dmu, dvalue, acc
+
+    def _direct_stacks_step(self, c, x_a, x_c, idx, m: int, i: int):
+        """One step of the two stacks for the forms whose rows `x_a`, `x_c` come out of an encoder or a memory: the packed forward,
+        `_direct_loss_and_rule`, both backward chains into the bucket -> (dx_a, dx_c), the gradient w.r.t. those rows (include/lt_mlp_dx.h)."""
+        (mu, value), acts = c.pair.forward_raw(x_a, x_c, with_dx=True)
+        dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx, m, i)
+        dx = (torch.empty_like(x_a), torch.empty_like(x_c))
+        c.pair.backward_raw(x_a, x_c, acts, dmu, dvalue, c.grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
+        return dx
 
     def _direct_end(self, c, with_dx: bool):
         """The end of every graph-free update: ONE host read (the device state, the backward chain's saturation count, the domain record),
@@ -501,19 +512,16 @@ class PPO:
         """Whether `_direct_update` serves this symmetric update: any of the four modes with this package's `mirror_go1` (the kernels
         mirror through its tables) on the conditions the direct update has without symmetry, on one rank; without augmentation the two
         networks differ in their row counts, which the fused backward pass alone serves.  Everything else runs `_symmetry_update`."""
-        from .fused_loss import std_param
         from .symmetry import mirror_go1
 
         sym = self.symmetry
         if not (sym["data_augmentation_func"] is mirror_go1 and self.dist.world_size == 1):
             return False
-        if not (self.direct_update and self._flat_adam is not None and self._fused_loss_ok(None) and std_param(self.actor_critic)[0].requires_grad):
-            return False
-        if self.normalize_advantage_per_mini_batch and (self.storage.num_envs * self.storage.num_steps) // self.num_mini_batches < 2:
+        if not self._fused_loss_ok(None) or self._one_row_minibatches() or not self._graph_free_ok():
             return False
         pair = self._packed_pair()
-        if pair is None or sym["use_data_augmentation"]:
-            return pair is not None
+        if sym["use_data_augmentation"]:
+            return True
         dev = self.storage.observations.device
         return pair._fused_backward_possible(*(torch.empty(0, net.in_features, device=dev) for net in (pair.a, pair.b)))
 
@@ -610,15 +618,38 @@ class PPO:
             group["lr"] = self.learning_rate
 
     def update(self):
+        form = self._update_form()
+        return form(self._packed_pair()) if form == self._direct_update else form()  # (the one form that is handed its stacks)
+
+    def _update_form(self):
+        """The update that serves this policy, its keys and its storage, as a bound method; the whole decision is here.  An opt-in key
+        runs its form or was refused at construction; with `symmetry_cfg` and without, the graph-free update where its conditions hold;
+        for the plain class otherwise the fused update; everything else the minibatch loop of `_eager_update`."""
         if self.direct_rnn_encoder_update:
-            return self._direct_rnn_encoder_update()
+            return self._direct_rnn_encoder_update
         if self.fused_encoder_policy:
-            return self._direct_encoder_update()
+            return self._direct_encoder_update
         if self.direct_recurrent_update:
-            return self._direct_recurrent_update()
+            return self._direct_recurrent_update
         if self.fused_recurrent_update:
-            return self._recurrent_update()
-        return self._eager_update()
+            return self._recurrent_update
+        if self.symmetry is not None:  # (never a recurrent policy: refused at construction)
+            return self._direct_update if self._symmetry_direct_ok() else self._symmetry_update
+        if self._fused_loss_ok(None) and not getattr(self.actor_critic, "is_recurrent", False) and not self._one_row_minibatches():
+            return self._direct_update if self._graph_free_ok() else self._fused_update
+        return self._eager_update
+
+    def _one_row_minibatches(self) -> bool:
+        """Per-minibatch advantage normalisation rides on the fused and the graph-free update too; minibatches of one row, whose std is
+        NaN in the reference, keep the op chain."""
+        return self.normalize_advantage_per_mini_batch and (self.storage.num_envs * self.storage.num_steps) // self.num_mini_batches < 2
+
+    def _graph_free_ok(self) -> bool:
+        """What `_direct_update` needs of the PPO object, with `symmetry_cfg` and without: the key, the flat bucket its gradients are
+        written into, a std whose gradient the learning-rate launch writes there, and the two stacks as a PackedPair."""
+        from .fused_loss import std_param
+
+        return self.direct_update and self._flat_adam is not None and std_param(self.actor_critic)[0].requires_grad and self._packed_pair() is not None
 
     def _direct_stacks_unsupported(self):
         """What the encoder and recurrent graph-free updates need of the optimizer, the two stacks and std -> (why, None), or, with all of
@@ -722,10 +753,7 @@ class PPO:
             x_a = torch.empty(m, enc.a_width, device=dev, dtype=torch.float32)
             x_c = torch.empty(m, enc.c_width, device=dev, dtype=torch.float32) if enc.c_desc is not None else co
             enc_acts = enc.forward(o, co, x_a, x_c if enc.c_desc is not None else None, train=True)
-            (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
-            dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx, m, i)
-            dx = (torch.empty_like(x_a), torch.empty_like(x_c))
-            pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
+            dx = self._direct_stacks_step(c, x_a, x_c, idx, m, i)
             sums = SumJobs()
             for k, (d, linears, _) in enumerate(nets):
                 L, flat = d.num_layers, d.flat_dim
@@ -740,11 +768,13 @@ class PPO:
 
     def _direct_recurrent_unsupported(self) -> str | None:
         """What `_direct_recurrent_update` needs beyond `_recurrent_update_unsupported`, a GPU and one rank (None: it is all there)."""
+        from .memory_seq import _params
+
         ac = self.actor_critic
         why, written = self._direct_stacks_unsupported()
         if why is not None:
             return why
-        written |= {id(p) for mem in (ac.memory_a, ac.memory_c) for p in (mem.rnn.weight_ih_l0, mem.rnn.weight_hh_l0, mem.rnn.bias_ih_l0, mem.rnn.bias_hh_l0)}
+        written |= {id(p) for mem in (ac.memory_a, ac.memory_c) for p in _params(mem)}
         return self._unwritten_gradient(written)
 
     @staticmethod
@@ -754,6 +784,34 @@ class PPO:
         per = N // num_mini_batches
         ar = lambda n, *shape: torch.arange(n, device=device, dtype=torch.int64).view(*shape)  # noqa: E731
         return (ar(T, 1, T, 1) * N + ar(num_mini_batches, num_mini_batches, 1, 1) * per + ar(per, 1, 1, per)).reshape(num_mini_batches, T * per)
+
+    def _env_blocks(self, key: str, tails=None):
+        """The env blocks of the two graph-free whole-rollout updates, laid out once per update -> (m = T * per, `_block_row_index`,
+        per block (observation rows, critic rows, dones as bytes, actor states, critic states at step 0 as [per, H])): the rows contiguous
+        [T, per, D], or with `tails` = (width, width) of the RNN-encoder form as [m, D] with their tail columns [T, per, width] as two
+        more entries behind them.  `key` names the form in a refusal."""
+        from .memory_seq import _dones_bytes
+
+        st, nmb = self.storage, self.num_mini_batches
+        if st.saved_hidden_states_a is None or st.saved_hidden_states_c is None:
+            raise ValueError(f"{key}: the storage holds no saved hidden states (no rollout of a recurrent policy filled it)")
+        T, N = st.num_steps, st.num_envs
+        per = N // nmb
+        m = T * per
+        if per < 1 or (self.normalize_advantage_per_mini_batch and m < 2):
+            raise ValueError(f"{key}: {nmb} minibatches of {N} envs x {T} steps leave a block of {m} rows")
+        H = self.actor_critic.memory_a.rnn.hidden_size
+        idx_all = self._block_row_index(T, N, nmb, st.observations.device)
+        dones = _dones_bytes(st.dones.view(T, N))
+        blocks = []
+        for i in range(nmb):
+            sl = (slice(None), slice(i * per, (i + 1) * per))
+            states = [tuple(h[0][sl].reshape(per, H) for h in hs) for hs in (st.saved_hidden_states_a, st.saved_hidden_states_c)]
+            rows = [st.observations[sl].contiguous(), st.privileged_observations[sl].contiguous()]
+            if tails is not None:
+                rows = [r.view(m, -1) for r in rows] + [r[..., r.shape[-1] - width:].contiguous() for r, width in zip(rows, tails)]
+            blocks.append((*rows, dones[sl], *states))
+        return m, idx_all, blocks
 
     def _direct_recurrent_update(self):
         """`_recurrent_update` with NO autograd graph and NO host read between its steps, as `_direct_update` is to `_fused_update` and
@@ -766,61 +824,28 @@ class PPO:
         why = self._recurrent_update_unsupported()  # (with the storage now: the observation rows' dtype)
         if why is not None:
             raise ValueError(f"direct_recurrent_update: {why}")
-        from .memory_seq import _dones_bytes, cell_of, direct_backward, direct_forward
+        from .memory_seq import cell_of, direct_backward, direct_forward
 
-        ac, st, fa, pair = self.actor_critic, self.storage, self._flat_adam, self._pair
-        if st.saved_hidden_states_a is None or st.saved_hidden_states_c is None:
-            raise ValueError("direct_recurrent_update: the storage holds no saved hidden states (no rollout of a recurrent policy filled it)")
-        T, N, nmb = st.num_steps, st.num_envs, self.num_mini_batches
-        per = N // nmb
-        m = T * per
-        if per < 1 or (self.normalize_advantage_per_mini_batch and m < 2):
-            raise ValueError(f"direct_recurrent_update: {nmb} minibatches of {N} envs x {T} steps leave a block of {m} rows")
-        dev = st.observations.device
+        ac, fa, nmb = self.actor_critic, self._flat_adam, self.num_mini_batches
+        m, idx_all, blocks = self._env_blocks("direct_recurrent_update")
         cell = cell_of(ac.memory_a, self.fused_gru_memories)
         H = ac.memory_a.rnn.hidden_size
-        idx_all = self._block_row_index(T, N, nmb, dev)
-        c = self._direct_begin("direct_recurrent_update", pair, idx_all.view(-1), m)
-        grad_of = c.grad_of
-        dones = _dones_bytes(st.dones.view(T, N))
-        blocks = []
-        for i in range(nmb):
-            sl = (slice(None), slice(i * per, (i + 1) * per))
-            states = [tuple(h[0][sl].reshape(per, H) for h in hs) for hs in (st.saved_hidden_states_a, st.saved_hidden_states_c)]
-            blocks.append((st.observations[sl].contiguous(), st.privileged_observations[sl].contiguous(), dones[sl], *states))
+        c = self._direct_begin("direct_recurrent_update", self._pair, idx_all.view(-1), m)
         for step_i in range(self.num_learning_epochs * nmb):
             i = step_i % nmb
             obs, cobs, d, hc_a, hc_c = blocks[i]
             recs = direct_forward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, hc_a, hc_c)
-            x_a, x_c = recs[0]["out"].view(m, H), recs[1]["out"].view(m, H)
-            (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
-            dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx_all[i], m, i)
-            dx = (torch.empty_like(x_a), torch.empty_like(x_c))
-            pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
-            direct_backward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, recs, dx, grad_of)
+            dx = self._direct_stacks_step(c, recs[0]["out"].view(m, H), recs[1]["out"].view(m, H), idx_all[i], m, i)
+            direct_backward(cell, ac.memory_a, ac.memory_c, obs, cobs, d, recs, dx, c.grad_of)
             fa.step_dev(self.max_grad_norm, c.lr_dev)
         return self._direct_end(c, with_dx=True)
 
-    def _direct_rnn_encoder_unsupported(self, kernels: bool = True) -> str | None:
-        """Why `_direct_rnn_encoder_update` does not serve this PPO (None: it does).  `kernels=False`: the first part alone - the class,
-        its critic, the symmetry cfg, the ranks and the device -, what can be said before the optimizer's flat bucket exists."""
+    def _direct_rnn_encoder_unsupported(self) -> str | None:
+        """What `_direct_rnn_encoder_update` needs beyond the class with an encoder in its critic, a GPU and one rank (None: it is all there)."""
         from . import encoder
-        from .memory_seq import memories_unsupported
+        from .memory_seq import _params, memories_unsupported
 
         ac = self.actor_critic
-        if type(ac).__name__ != "ActorCriticRNNEncoder":
-            return f"the policy is a {type(ac).__name__}, not an ActorCriticRNNEncoder"
-        if not ac.critic_with_encoder:
-            return "the critic has no encoder"
-        if self.symmetry is not None:
-            return "symmetry_cfg is not served for this class (its hidden states have no mirror)"
-        if self.dist.world_size > 1:
-            return (f"dist.world_size is {self.dist.world_size}: the collectives of this form are not covered by a multi-rank test, it runs "
-                    "on one rank only")
-        if torch.device(self.device).type != "cuda":
-            return f"the device is {self.device!r}: its kernels run on a GPU only"
-        if not kernels:
-            return None
         why, written = self._direct_stacks_unsupported()
         if why is not None:
             return why
@@ -831,7 +856,7 @@ class PPO:
             encoder.RnnEncoderPair(ac, ac.actor_flatten_obs_dim + ac.actor_encoder_obs_dim, ac.critic_flatten_obs_dim + ac.critic_encoder_obs_dim)
         except ValueError as e:
             return str(e)
-        written |= {id(p) for mem in (ac.memory_a, ac.memory_c) for p in (mem.rnn.weight_ih_l0, mem.rnn.weight_hh_l0, mem.rnn.bias_ih_l0, mem.rnn.bias_hh_l0)}
+        written |= {id(p) for mem in (ac.memory_a, ac.memory_c) for p in _params(mem)}
         written |= {id(p) for enc in (ac.actor_encoder, ac.critic_encoder) for p in enc.parameters()}
         return self._unwritten_gradient(written)
 
@@ -847,40 +872,22 @@ class PPO:
         (`RnnEncoderPair.backward`); the cell's `seq_backward` from that gradient and the memories' eight parameter gradients
         (`direct_backward`) - every gradient written in place into the flat bucket.  LSTM and GRU memories alike, as the rollout key."""
         from .encoder import RnnEncoderPair
-        from .memory_seq import _dones_bytes, cell_of, direct_backward, direct_forward
+        from .memory_seq import cell_of, direct_backward, direct_forward
 
-        ac, st, fa, pair = self.actor_critic, self.storage, self._flat_adam, self._pair
+        ac, st, fa, nmb = self.actor_critic, self.storage, self._flat_adam, self.num_mini_batches
         if st.observations.dtype != torch.float32 or st.privileged_observations.dtype != torch.float32:
             raise ValueError("direct_rnn_encoder_update: bf16 observation rows: the memories and the encoder launch read f32 rows")
-        if st.saved_hidden_states_a is None or st.saved_hidden_states_c is None:
-            raise ValueError("direct_rnn_encoder_update: the storage holds no saved hidden states (no rollout of a recurrent policy filled it)")
-        D_a, D_c = st.observations.shape[-1], st.privileged_observations.shape[-1]
         if self._rnn_encoders is None:
             try:
-                self._rnn_encoders = RnnEncoderPair(ac, D_a, D_c)
+                self._rnn_encoders = RnnEncoderPair(ac, st.observations.shape[-1], st.privileged_observations.shape[-1])
             except ValueError as e:
                 raise ValueError(f"direct_rnn_encoder_update: {e}") from None
         enc = self._rnn_encoders
-        T, N, nmb = st.num_steps, st.num_envs, self.num_mini_batches
-        per = N // nmb
-        m = T * per
-        if per < 1 or (self.normalize_advantage_per_mini_batch and m < 2):
-            raise ValueError(f"direct_rnn_encoder_update: {nmb} minibatches of {N} envs x {T} steps leave a block of {m} rows")
-        dev = st.observations.device
+        m, idx_all, blocks = self._env_blocks("direct_rnn_encoder_update", tails=(ac.actor_encoder_obs_dim, ac.critic_encoder_obs_dim))
         cell = cell_of(ac.memory_a, True)
         H = ac.memory_a.rnn.hidden_size
-        I_a, I_c = ac.actor_encoder_obs_dim, ac.critic_encoder_obs_dim
-        idx_all = self._block_row_index(T, N, nmb, dev)
-        c = self._direct_begin("direct_rnn_encoder_update", pair, idx_all.view(-1), m)
-        grad_of = c.grad_of
-        dones = _dones_bytes(st.dones.view(T, N))
-        blocks = []
-        for i in range(nmb):
-            sl = (slice(None), slice(i * per, (i + 1) * per))
-            states = [tuple(h[0][sl].reshape(per, H) for h in hs) for hs in (st.saved_hidden_states_a, st.saved_hidden_states_c)]
-            rows_a, rows_c = st.observations[sl].contiguous(), st.privileged_observations[sl].contiguous()
-            blocks.append((rows_a.view(m, D_a), rows_c.view(m, D_c), rows_a[..., D_a - I_a:].contiguous(), rows_c[..., D_c - I_c:].contiguous(),
-                           dones[sl], *states))
+        c = self._direct_begin("direct_rnn_encoder_update", self._pair, idx_all.view(-1), m)
+        dev, grad_of = c.dev, c.grad_of
         for step_i in range(self.num_learning_epochs * nmb):
             i = step_i % nmb
             rows_a, rows_c, tail_a, tail_c, d, hc_a, hc_c = blocks[i]
@@ -889,10 +896,7 @@ class PPO:
             x_a = torch.empty(m, enc.a_width, device=dev, dtype=torch.float32)
             x_c = torch.empty(m, enc.c_width, device=dev, dtype=torch.float32)
             enc_acts = enc.forward_train(rows_a, rows_c, *hs, x_a, x_c)
-            (mu, value), acts = pair.forward_raw(x_a, x_c, with_dx=True)
-            dmu, dvalue, acc = self._direct_loss_and_rule(c, mu, value, idx_all[i], m, i)
-            dx = (torch.empty_like(x_a), torch.empty_like(x_c))
-            pair.backward_raw(x_a, x_c, acts, dmu, dvalue, grad_of, dy_amax=(acc[20:21], acc[21:22]), dx_out=dx)
+            dx = self._direct_stacks_step(c, x_a, x_c, idx_all[i], m, i)
             dh = enc.backward(dx, (x_a, x_c), enc_acts, grad_of, hs)
             direct_backward(cell, ac.memory_a, ac.memory_c, tail_a, tail_c, d, recs, dh, grad_of)
             fa.step_dev(self.max_grad_norm, c.lr_dev)
@@ -976,17 +980,12 @@ class PPO:
         return sv, ss, se, None, None
 
     def _eager_update(self):
+        """The reference's minibatch loop (ppo.py:216-337) on any device and for every class: a recurrent policy on padded whole
+        trajectories, the loss as one launch where `_fused_loss_ok` holds, else as the op chain."""
         ac = self.actor_critic
-        if self.symmetry is not None:  # (never a recurrent policy: refused at construction)
-            return self._direct_update(self._packed_pair()) if self._symmetry_direct_ok() else self._symmetry_update()
         sum_value = sum_surr = sum_ent = 0.0
         stats = None
         recurrent = getattr(ac, "is_recurrent", False)
-        # (per-minibatch advantage normalisation rides on the fused update too; minibatches of one row, whose std is NaN in the
-        # reference, keep the op chain below)
-        one_row = self.normalize_advantage_per_mini_batch and (self.storage.num_envs * self.storage.num_steps) // self.num_mini_batches < 2
-        if not recurrent and not one_row and self._fused_loss_ok(None):
-            return self._fused_update()
         batches = (self.storage.recurrent_mini_batches(self.num_mini_batches, self.num_learning_epochs) if recurrent
                    else self.storage.mini_batches(self.num_mini_batches, self.num_learning_epochs))
         for raw in batches:
