@@ -139,6 +139,7 @@ HEADERS = (
     ("MEMORY_SEQ", "lt_memory_seq.h", False, ("lt_memory_seq_backward_units",), ("lt_memory_seq_net", "lt_memory_seq_grad")),  # the two memories over a whole rollout
     ("MEMORY_GRU", "lt_memory_gru.h", False, ("lt_memory_gru_seq_backward_units",),
      ("lt_memory_gru_net", "lt_memory_gru_seq_net", "lt_memory_gru_seq_grad")),  # GRU memories, one rollout step and whole rollouts
+    ("MEMORY_DX", "lt_memory_dx.h", False, ("lt_memory_input_grad_launches",), ("lt_memory_dx_net",)),  # the input gradient of a recurrent policy's two memories
     ("POLICY", "lt_policy.h", True, ("lt_policy_step_launches",), ("lt_policy_desc", "lt_policy_memory")),  # one inference step of a recurrent policy
     ("PPO_OPTS", "lt_ppo_opts.h", False, (), ()),  # the log-std policy and per-minibatch advantage statistics
     ("MLP_DX", "lt_mlp_dx.h", True, (), ()),  # the input gradient of the actor and critic stacks (recurrent policies: the memories' dout)

@@ -25,10 +25,12 @@ checkpoints are unaffected), in two forms as rl/lstm.py:
   * `_SeqHip`: the cell's `seq_forward` (T launches, both networks in each, the observation rows read in place) and `seq_backward` (T
     launches) - both cells on the one row-block kernel of csrc/lt_memory_tile.h.  What is not sequential stays outside the loop, one
     call each (`_finish`): the two weight gradients through rl/gru.py `_wgrad`, the bias gradients as column sums.
-The observations and the initial states carry no gradient: dX and the gradients of the initial states are not computed.
+The initial states carry no gradient.  The rows do where they ask for one (`requires_grad`: a layer stands in front of the memory):
+dX = d_ih W_ih, `input_grad` - csrc/lt_memory_dx.hip, include/lt_memory_dx.h, ONE launch for both networks behind `seq_backward` - in
+the HIP form, the same product as a PyTorch op in `_SeqOps`.  Rows that ask for none launch nothing more than before.
 
 `direct_forward` / `direct_backward` are the HIP form WITHOUT the autograd Function, for `PPO._direct_recurrent_update`: the records out,
-(dout_a, dout_c) in, the eight parameter gradients written in place into given views.
+(dout_a, dout_c) in, the eight parameter gradients written in place into given views - and, given `dx_out`, the two input gradients.
 """
 from __future__ import annotations
 
@@ -236,22 +238,24 @@ class _SeqOps(torch.autograd.Function):
         ra = cell.forward_ops(x_a, done_rows, *states[:ns], *params[:4])
         rc = cell.forward_ops(x_c, done_rows, *states[ns:], *params[4:])
         ctx.cell = cell
-        ctx.save_for_backward(x_a, x_c, done_rows, params[1], params[5], *ra, *rc)
+        ctx.save_for_backward(x_a, x_c, done_rows, params[1], params[5], params[0], params[4], *ra, *rc)
         ctx.set_materialize_grads(False)
         return ra[0], rc[0]
 
     @staticmethod
     def backward(ctx, dout_a, dout_c):
         cell = ctx.cell
-        x_a, x_c, done_rows, w_hh_a, w_hh_c, *saved = ctx.saved_tensors
-        grads = []
-        for x, dout, w_hh, rec in zip((x_a, x_c), (dout_a, dout_c), (w_hh_a, w_hh_c), _records(cell, saved)):
+        x_a, x_c, done_rows, w_hh_a, w_hh_c, w_ih_a, w_ih_c, *saved = ctx.saved_tensors
+        grads, dxs = [], [None, None]
+        for k, (x, dout, w_hh, w_ih, rec) in enumerate(zip((x_a, x_c), (dout_a, dout_c), (w_hh_a, w_hh_c), (w_ih_a, w_ih_c), _records(cell, saved))):
             if dout is None:
                 grads += [None] * 4
                 continue
-            dgs = cell.backward_ops(dout, done_rows, w_hh, *(rec[k] for k in cell.reads))
-            grads += _finish(cell, x, dict(zip((k for k, _ in cell.dgates), dgs)), rec["h_prev"])
-        return (None,) * (4 + 2 * len(cell.state)) + tuple(grads)
+            dgs = dict(zip((key for key, _ in cell.dgates), cell.backward_ops(dout, done_rows, w_hh, *(rec[key] for key in cell.reads))))
+            grads += _finish(cell, x, dgs, rec["h_prev"])
+            if ctx.needs_input_grad[1 + k]:  # the rows ask: dX = d_ih W_ih
+                dxs[k] = (dgs[cell.d_ih].reshape(-1, w_ih.shape[0]) @ w_ih).view(x.shape).to(x.dtype)
+        return (None, *dxs, None) + (None,) * (2 * len(cell.state)) + tuple(grads)
 
 
 # ---- the HIP form ---------------------------------------------------------------------------------------------------------------------
@@ -300,6 +304,29 @@ def hip_backward(cell, douts, dones, w_hhs, recs):
     return dgs
 
 
+def input_grad(cell, dgs, w_ihs, outs=None):
+    """The gradients of the two networks' input rows, dx_k = d_ih_k W_ih_k, in ONE launch (include/lt_memory_dx.h).  dgs: the two
+    gate-gradient dicts `hip_backward` returns; w_ihs: the two [gates * H, I_k] weights (views of a flat bucket will do).  outs: None -
+    two new [T, E, I_k] tensors - or a pair of f32 views to write, each [T, E, I_k] or [T * E, I_k] with unit stride along I_k and evenly
+    spaced rows (the tail columns of a wider gradient row): every element of the views is written, nothing outside them.  Returns the
+    pair."""
+    d = [dg[cell.d_ih] for dg in dgs]
+    T, E, K = d[0].shape
+    gates = dict(cell.dgates)[cell.d_ih]
+    ws = [w.detach().contiguous() for w in w_ihs]
+    outs = [g.new_empty(T, E, w.shape[1]) for g, w in zip(d, ws)] if outs is None else list(outs)
+    nets = []
+    for g, w, out in zip(d, ws, outs):
+        I = w.shape[1]
+        assert g.is_contiguous() and g.shape == (T, E, K) and w.shape[0] == K
+        assert out.dtype == torch.float32 and out.shape in ((T, E, I), (T * E, I)), "dx views: f32 [T, E, I] or [T * E, I]"
+        rows = out.view(T * E, I)  # (raises unless the rows are evenly spaced)
+        assert rows.stride(1) == 1 or I == 1, "dx views: unit stride along I"
+        nets.append(_abi.LtMemoryDxNet(dg=g.data_ptr(), w_ih=w.data_ptr(), I=I, dx=rows.data_ptr(), dx_stride=rows.stride(0) if T * E > 1 else I))
+    _abi.call("lt_memory_input_grad", nets[0], nets[1], T * E, K // gates, gates, _abi.stream(d[0].device))
+    return tuple(outs)
+
+
 def _wgrad_into(dst, dy2d, x2d) -> None:
     """`dst` = rl/gru.py `_wgrad(dy2d, x2d)`, the same operations in the same order, the last of them writing in place."""
     from .linear import pick_splits
@@ -322,11 +349,12 @@ def direct_forward(cell, memory_a, memory_c, x_a, x_c, dones, hc0_a, hc0_c):
         return hip_forward(cell, x_a, x_c, dones, (*_state(cell, hc0_a, E), *_state(cell, hc0_c, E)), (*_params(memory_a), *_params(memory_c)))
 
 
-def direct_backward(cell, memory_a, memory_c, x_a, x_c, dones, recs, douts, grad_of) -> None:
+def direct_backward(cell, memory_a, memory_c, x_a, x_c, dones, recs, douts, grad_of, dx_out=None) -> None:
     """From (dout_a, dout_c), each [T, E, H] (or [T * E, H]) contiguous f32, to the eight parameter gradients, written IN PLACE into
     `grad_of[param]` (views of the flat gradient bucket; every element of each is written): the cell's `seq_backward`, then per network
     what `_finish` does - dW_ih, dW_hh as split-K GEMMs, db_ih, db_hh as column sums - with the last operation of each writing its
-    view.  One code path for both cells, through the `Cell` table."""
+    view.  One code path for both cells, through the `Cell` table.  dx_out: None, or a pair of views as `input_grad` takes them: the
+    gradients of the two networks' input rows are written there as well, from the gate gradients already at hand (one launch more)."""
     with torch.no_grad():
         T, E, H = recs[0]["out"].shape
         mems = (memory_a, memory_c)
@@ -341,6 +369,8 @@ def direct_backward(cell, memory_a, memory_c, x_a, x_c, dones, recs, douts, grad
                 torch.sum(d_hh, dim=0, out=grad_of[b_hh])
             _wgrad_into(grad_of[w_ih], d_ih, x.reshape(T * E, -1))
             _wgrad_into(grad_of[w_hh], d_hh, rec["h_prev"].view(T * E, H))
+        if dx_out is not None:
+            input_grad(cell, dgs, tuple(_params(m)[0] for m in mems), dx_out)
 
 
 class _SeqHip(torch.autograd.Function):
@@ -351,20 +381,23 @@ class _SeqHip(torch.autograd.Function):
         ns = len(cell.state)
         ra, rc = hip_forward(cell, x_a, x_c, dones, rest[:2 * ns], rest[2 * ns:])
         ctx.cell = cell
-        ctx.save_for_backward(x_a, x_c, dones, rest[2 * ns + 1], rest[2 * ns + 5], *ra.values(), *rc.values())
+        ctx.save_for_backward(x_a, x_c, dones, rest[2 * ns + 1], rest[2 * ns + 5], rest[2 * ns], rest[2 * ns + 4], *ra.values(), *rc.values())
         ctx.set_materialize_grads(False)
         return ra["out"], rc["out"]
 
     @staticmethod
     def backward(ctx, dout_a, dout_c):
         cell = ctx.cell
-        x_a, x_c, dones, w_hh_a, w_hh_c, *saved = ctx.saved_tensors
+        x_a, x_c, dones, w_hh_a, w_hh_c, w_ih_a, w_ih_c, *saved = ctx.saved_tensors
         recs = _records(cell, saved)
         dgs = hip_backward(cell, (dout_a, dout_c), dones, (w_hh_a, w_hh_c), recs)
         grads = []
         for x, dg, rec in zip((x_a, x_c), dgs, recs):
             grads += _finish(cell, x, dg, rec["h_prev"])
-        return (None,) * (4 + 2 * len(cell.state)) + tuple(grads)
+        dxs = (None, None)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:  # one launch serves both; a row's bits do not depend on the other network
+            dxs = tuple(dx if need else None for dx, need in zip(input_grad(cell, dgs, (w_ih_a, w_ih_c)), ctx.needs_input_grad[1:3]))
+        return (None, *dxs, None) + (None,) * (2 * len(cell.state)) + tuple(grads)
 
 
 # ---- what is served, and the entry point ----------------------------------------------------------------------------------------------
@@ -427,6 +460,9 @@ def memory_rollout_sequence(memory_a, memory_c, obs, critic_obs, dones, hc0_a, h
     obs / critic_obs may be views `storage[:, e0:e1]`: the forward pass reads them in place.  The weight gradient dW_ih = dgates^T X
     wants contiguous rows, though, so the BACKWARD pass of a call on such a view copies the block (`reshape`) each time; a caller that
     runs the same blocks more than once hands over contiguous copies made once, as `PPO._recurrent_update` does per update.
+
+    Rows that require a gradient get it: dX = d_ih W_ih, one launch more in the HIP form (`input_grad`); rows that require none cost
+    nothing more than before, and the parameter gradients are the same bits either way.  The initial states get none.
 
     Rows whose dtype is not the memories' own, multi-layer memories, and GRU memories without `gru_memories=True` raise `ValueError`;
     there is no quiet change of path on them.  The HIP form runs where `serves` says so, the PyTorch-op form elsewhere (the CPU, other
