@@ -153,6 +153,8 @@ HEADERS = (
      ("lt_rnn_encoder_grad",)),  # an ActorCriticRNNEncoder's update: the encoder's training form and its backward pass
     ("POLICY_ENCODER", "lt_policy_encoder.h", False, ("lt_policy_encoder_step_launches",),
      ("lt_policy_encoder_desc", "lt_policy_encoder_params")),  # one inference step of an ActorCriticEncoder / ActorCriticRNNEncoder
+    ("TACTILE_PANEL", "lt_tactile_panel.h", False, ("lt_tactile_panel_launches",),
+     ("lt_panel_signal", "lt_panel_desc")),  # the taxel panel drawn over rendered frames (--video_tactile)
 )
 
 

@@ -102,7 +102,10 @@ class DeviceTactileRecorder:
             _abi.call("lt_delay_push", self._state, self.env_num, self.dim, self.depth, rows, rows.stride(0), o0, o0.stride(0),
                       o1, 0 if o1 is None else o1.stride(0), src, 0 if src is None else src.stride(0), dst, 0 if dst is None else dst.stride(0),
                       cd, _abi.stream(self.device))
+        self.last_delayed = o0
         return out
+
+    last_delayed = None  # the delayed rows `push` wrote last (what the student read): a viewer's handle, no copy and no launch
 
     def after_step(self, reward: torch.Tensor, dones: torch.Tensor, reward_out: torch.Tensor, done_out: torch.Tensor) -> None:
         """Behind an env step: `reward_out = reward`, `done_out = dones != 0` (bool or uint8 [env_num]: what a student's `reset`

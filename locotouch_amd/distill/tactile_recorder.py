@@ -43,5 +43,8 @@ class TactileRecorder:
         self.tactile_buffer = torch.where(first, filled, shifted)
         self.first_signal_recorded = torch.zeros_like(self.first_signal_recorded)
 
+    last_delayed = None  # the delayed rows handed out last (what the student read): a viewer's handle, no copy and no launch
+
     def get_tactile_signals(self) -> torch.Tensor:
-        return self.tactile_buffer[self.env_idx, self.delay_steps]
+        self.last_delayed = self.tactile_buffer[self.env_idx, self.delay_steps]
+        return self.last_delayed

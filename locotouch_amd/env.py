@@ -388,6 +388,49 @@ class LocoTouchVecEnv:
         _abi.call("lt_env_render", self._handle, desc, views, len(env_ids), rgba, dep, idt, pos, _abi.stream(self.device))
         return res
 
+    def tactile_groups(self) -> dict:
+        """The env's own tactile observation groups, in the panel's order: `tactile`, `original_tactile`, `processed_tactile`, as
+        far as the task has them.  ValueError, naming the task, for a task without one."""
+        if not getattr(self, "tactile", False):
+            raise ValueError(f"task {self.task!r} has no tactile observation group: there is nothing to draw a tactile panel from")
+        groups = {"tactile": self.obs_tactile}
+        if self.obs_tactile_original is not None:
+            groups["original_tactile"] = self.obs_tactile_original
+        if self.obs_tactile_processed is not None:
+            groups["processed_tactile"] = self.obs_tactile_processed
+        return groups
+
+    def draw_tactile_panel(self, rgba: torch.Tensor, env_ids, signals=None, panel=None, maps=None) -> torch.Tensor:
+        """Draw the taxel panel of env `env_ids[v]` over frame v of `rgba`, int32 [V, H, W] packed RGBA8 (what `render` returns as
+        "rgba"), in place: one launch of lt_tactile_panel_draw behind whatever wrote the frames (no host sync; include/lt_tactile_panel.h
+        has the layout and the colour arithmetic).  `signals`: an ordered mapping name -> [N, C * 221] float32 device tensor, drawn top
+        to bottom (default: `tactile_groups()`).  `panel`: a render.TactilePanel.  Channel 0 of a signal is drawn with the binary map,
+        as is channel 1 of a two-channel signal when cfg.tactile_format is LT_TACTILE_BINARY; force and level channels with the ramp
+        (`maps`: name -> maps per channel, to say otherwise).  A CPU env or tensor raises: there is no fall-back."""
+        from . import render as R
+
+        if signals is None:
+            signals = self.tactile_groups()
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("draw_tactile_panel needs a HIP device (the panel is drawn by a HIP kernel; there is no CPU path)")
+        if not isinstance(rgba, torch.Tensor) or not rgba.is_cuda or rgba.dtype != torch.int32 or rgba.dim() != 3 or not rgba.is_contiguous():
+            raise TypeError(f"draw_tactile_panel: rgba must be a contiguous int32 [V, H, W] tensor on {self.device}")
+        for name, t in signals.items():
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise TypeError(f"draw_tactile_panel: signal {name!r} must be a float32 tensor on {self.device}")
+        panel = panel or R.TactilePanel()
+        env_ids = [int(e) for e in (env_ids.tolist() if hasattr(env_ids, "tolist") else env_ids)]
+        if len(env_ids) != rgba.shape[0]:
+            raise ValueError(f"draw_tactile_panel: {len(env_ids)} env ids for {rgba.shape[0]} frames")
+        sig = R.panel_signals(signals, maps, int(self.cfg.tactile_format))
+        height, width = int(rgba.shape[1]), int(rgba.shape[2])
+        x0, y0 = panel.origin(R.panel_size(panel, signals), width, height)
+        ids = (ctypes.c_int32 * len(env_ids))(*env_ids)
+        with torch.cuda.device(self.device):
+            _abi.call("lt_tactile_panel_draw", R.panel_desc(panel, len(sig), x0, y0), sig, ids, len(env_ids), rgba, width, height,
+                      _abi.stream(self.device))
+        return rgba
+
     @property
     def contact_forces_w_history(self) -> torch.Tensor:
         """(N, 3, 17, 3): the robot contact sensor's net_forces_w_history [DEP] - world-frame force on each body at the last three

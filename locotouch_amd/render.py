@@ -99,5 +99,80 @@ def rgba_to_rgb(rgba):
     return np.ascontiguousarray(rgba).view(np.uint8).reshape(*rgba.shape, 4)[..., :3]
 
 
+PANEL_CORNERS = ("top-left", "top-right", "bottom-left", "bottom-right")
+PC = _abi.TACTILE_PANEL_CONSTS
+MAP_BINARY, MAP_RAMP = PC["LT_PANEL_MAP_BINARY"], PC["LT_PANEL_MAP_RAMP"]
+
+
+@dataclasses.dataclass
+class TactilePanel:
+    """The taxel panel drawn over a rendered frame (include/lt_tactile_panel.h): `cell` pixels per taxel edge, `gap` pixels between
+    grids and between signals, `margin` pixels between the panel and the frame's `corner`, `opacity` 0 ... 255."""
+    cell: int = 4
+    gap: int = 2
+    corner: str = "top-right"
+    margin: int = 8
+    opacity: int = 224
+
+    def origin(self, size: tuple[int, int], width: int, height: int) -> tuple[int, int]:
+        """(x0, y0) of a panel of `size` (panel_size) in a width x height frame."""
+        if self.corner not in PANEL_CORNERS:
+            raise ValueError(f"TactilePanel.corner {self.corner!r} is not one of {PANEL_CORNERS}")
+        pw, ph = size
+        v, h = self.corner.split("-")
+        return (int(self.margin) if h == "left" else int(width) - int(self.margin) - pw,
+                int(self.margin) if v == "top" else int(height) - int(self.margin) - ph)
+
+
+def channel_maps(tactile_format: int, channels: int) -> list[int]:
+    """The colour map per channel of a tactile group of `channels` channels.  Channel 0 is the contact bit in every TactileSignals
+    format: the binary map.  LT_TACTILE_BINARY repeats it in channel 1; every other channel is a force or a level: the ramp."""
+    if channels == 2 and int(tactile_format) == C["LT_TACTILE_BINARY"]:
+        return [MAP_BINARY, MAP_BINARY]
+    return [MAP_BINARY] + [MAP_RAMP] * (int(channels) - 1)
+
+
+def panel_signals(signals, maps=None, tactile_format: int = C["LT_TACTILE_BINARY"]):
+    """The `lt_panel_signal` array of an ordered mapping name -> [N, C * 221] tensor (anything with shape, stride() and data_ptr();
+    unit column stride).  `maps`: name -> list of colour maps per channel; a name it does not hold gets `channel_maps` of a
+    two-channel group in `tactile_format`, of a four-channel one as it stands."""
+    taxels = PC["LT_PANEL_TAXELS"]
+    if not signals:
+        raise ValueError("a tactile panel needs at least one signal")
+    arr = (_abi.LtPanelSignal * len(signals))()
+    for s, (name, t) in zip(arr, signals.items()):
+        if len(t.shape) != 2 or t.shape[1] % taxels or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"tactile panel: signal {name!r} must be [N, C * {taxels}] with unit column stride, got {tuple(t.shape)}")
+        s.rows, s.row_stride, s.n_envs, s.channels = t.data_ptr(), t.stride(0), t.shape[0], t.shape[1] // taxels
+        for c, m in enumerate((maps or {}).get(name) or channel_maps(tactile_format, s.channels)):
+            if c < PC["LT_PANEL_MAX_CHANNELS"]:
+                s.maps[c] = int(m)
+    return arr
+
+
+def panel_desc(panel: TactilePanel, nsignals: int, x0: int = 0, y0: int = 0) -> _abi.LtPanelDesc:
+    d = _abi.LtPanelDesc()
+    d.nsignals, d.cell, d.gap, d.x0, d.y0, d.opacity = int(nsignals), int(panel.cell), int(panel.gap), int(x0), int(y0), int(panel.opacity)
+    return d
+
+
+def panel_size(panel: TactilePanel, signals) -> tuple[int, int]:
+    """(width, height) in pixels of `panel` for `signals`: an ordered mapping name -> [N, C * 221] tensor, or a sequence of channel
+    counts.  lt_tactile_panel_size: host only, no device is touched."""
+    import ctypes
+
+    if hasattr(signals, "items"):
+        counts = [t.shape[1] // PC["LT_PANEL_TAXELS"] for t in signals.values()]
+    else:
+        counts = [int(c) for c in signals]
+    arr = (_abi.LtPanelSignal * max(1, len(counts)))()
+    for s, c in zip(arr, counts):
+        s.channels = c
+    w, h = ctypes.c_int(), ctypes.c_int()
+    _abi.call("lt_tactile_panel_size", panel_desc(panel, len(counts)), arr, ctypes.byref(w), ctypes.byref(h))
+    return w.value, h.value
+
+
 __all__ = ["Camera", "chase_camera", "from_viewer_cfg", "basis", "ray_directions", "parse_resolution", "rgba_to_rgb", "ORIGIN_WORLD",
-           "ORIGIN_ASSET_ROOT", "DEFAULT_FLAGS", "DEPTH_MISS"]
+           "ORIGIN_ASSET_ROOT", "DEFAULT_FLAGS", "DEPTH_MISS", "TactilePanel", "panel_size", "panel_signals", "panel_desc", "channel_maps",
+           "MAP_BINARY", "MAP_RAMP"]

@@ -7,7 +7,9 @@
 
 Flags follow the reference CLI (locotouch/scripts/cli_args.py:11-33,92-124, distill.py:8-20).  The teacher checkpoint is looked
 up as the reference does: logs/rsl_rl/<teacher experiment>/<--load_run>/<--checkpoint> (latest matching).  `--video` records env 0
-(animated PNG, locotouch_amd/video.py) into <distill log root>/videos/{train,play}.
+(animated PNG, locotouch_amd/video.py) into <distill log root>/videos/{train,play}; `--video --video_tactile` draws the tactile signals
+into the frames' top-right corner, top to bottom: `policy` (the delayed rows the student reads), `tactile`, and on the -Play- env
+`original_tactile` and `processed_tactile` (include/lt_tactile_panel.h) - the reference play loop's three ROS topics plus the undelayed signal.
 """
 from __future__ import annotations
 
@@ -44,10 +46,11 @@ def main() -> None:
     ap.add_argument("--fused_bc_step", action="store_true",
                     help="assemble batches, compute the masked BC loss and step AdamW through the HIP kernels of lt_bc.h (lt_bc_gather, "
                          "lt_bc_loss_forward / _backward, lt_adamw_step)")
-    from locotouch_amd.video import add_video_args
+    from locotouch_amd.video import add_video_args, refuse_video_tactile
 
     add_video_args(ap)
     args, _unknown = ap.parse_known_args()
+    refuse_video_tactile(args, args.task)
 
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.distill import distillation_cfg
@@ -64,18 +67,38 @@ def main() -> None:
     env = make(args.task, num_envs=args.num_envs, device=args.device, seed=args.seed if args.seed is not None else agent["seed"])
     distill_root = os.path.abspath(os.path.join(cfg.log_root_path, cfg.experiment_name))
     recorder = None
+    delay_line: dict = {}  # "recorder": the Distillation's tactile recorder, once there is one (_run)
     if args.video:
         from locotouch_amd.video import recorder_for
 
-        recorder = recorder_for(env, args, os.path.join(distill_root, "videos", "train" if args.training else "play"))
+        recorder = recorder_for(env, args, os.path.join(distill_root, "videos", "train" if args.training else "play"),
+                                tactile_signals=panel_signals_of(env, delay_line) if args.video_tactile else None)
     try:
-        _run(args, cfg, agent, env, distill_root)
+        _run(args, cfg, agent, env, distill_root, delay_line)
     finally:
         if recorder is not None:
             recorder.close()
 
 
-def _run(args, cfg, agent, env, distill_root) -> None:
+def panel_signals_of(env, delay_line: dict):
+    """The callable `recorder_for(..., tactile_signals=)` asks for the --video_tactile panel's rows, top to bottom: `policy` - the DELAYED
+    rows the student reads, as the loops' delay line handed them out last (`last_delayed` of delay_line["recorder"]: the loops' own
+    buffer, no copy and no launch; zeros until the first push, as the delay line itself answers then) - and the env's own groups:
+    `tactile`, and on the -Play- env `original_tactile` and `processed_tactile`.  These are the reference play loop's three topics
+    (distillation.py:132-143, 202-211) plus the undelayed signal."""
+    groups = env.tactile_groups()  # ValueError, naming the task, without a tactile group
+    zeros = torch.zeros_like(groups["tactile"], memory_format=torch.contiguous_format)
+
+    def signals():
+        rec = delay_line.get("recorder")
+        delayed = getattr(rec, "last_delayed", None)
+        policy = zeros if delayed is None else delayed.reshape(delayed.shape[0], -1)  # (a view: the rows are contiguous inside)
+        return {"policy": policy, **groups}
+
+    return signals
+
+
+def _run(args, cfg, agent, env, distill_root, delay_line: dict | None = None) -> None:
     from locotouch_amd.compat.runtime import get_checkpoint_path
     from locotouch_amd.distill import Distillation
     from locotouch_amd.rl import OnPolicyRunner
@@ -92,11 +115,16 @@ def _run(args, cfg, agent, env, distill_root) -> None:
                          teacher_backbone_weights=None if mono else runner.get_backbone_weights(), training=True,
                          fused_student_inference=args.fused_student, fused_collection=args.fused_collect, device_ledger=args.device_ledger,
                          fused_cnn_training=args.fused_cnn_train, fused_bc_step=args.fused_bc_step)
+        if delay_line is not None:
+            delay_line["recorder"] = d.tactile_recorder
         d.train()
     else:
-        ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or ".*", args.checkpoint_distill or "model_.*.pt")
+        # (`--video` keeps its recordings in <distill root>/videos, beside the runs: that folder is no run)
+        ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or r"(?!videos$).*", args.checkpoint_distill or "model_.*.pt")
         d = Distillation(env, cfg, training=False, checkpoint=ckpt, fused_student_inference=args.fused_student, fused_collection=args.fused_collect,
                          device_ledger=args.device_ledger)
+        if delay_line is not None:
+            delay_line["recorder"] = d.tactile_recorder
         d.play(num_steps=args.play_steps)
 
 

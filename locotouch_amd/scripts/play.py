@@ -3,7 +3,8 @@
 episode statistics, optionally exports the actor (with its memory, for a recurrent policy) as TorchScript for the robot-side runtime,
 with `--fused_policy` serves a recurrent or an encoder policy from its fused HIP inference step (include/lt_policy.h,
 include/lt_policy_encoder.h), and with `--video` records env 0 (animated
-PNG, locotouch_amd/video.py) into <run>/videos/play.  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
+PNG, locotouch_amd/video.py) into <run>/videos/play (`--video_tactile`: with the env's tactile groups drawn into the frames, on a tactile
+task; refused by name for a task without one).  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
 `policy` and `empirical_normalization` entries take the place of the registered agent cfg's, so a recurrent checkpoint loads.
 
     python -m locotouch_amd.scripts.play --task Isaac-RandCylinderTransportTeacher-LocoTouch-Play-v1 --num_envs 50 --steps 1000 --export
@@ -31,10 +32,11 @@ def main() -> None:
     ap.add_argument("--fused_policy", action="store_true",
                     help="ActorCriticRecurrent, ActorCriticEncoder and ActorCriticRNNEncoder policies: step through the fused HIP inference "
                          "step (rl/fused_policy.py) and reset the memory of finished envs")
-    from locotouch_amd.video import add_video_args
+    from locotouch_amd.video import add_video_args, refuse_video_tactile
 
     add_video_args(ap)
     args, _unknown = ap.parse_known_args()
+    refuse_video_tactile(args, args.task)  # --video_tactile: tactile tasks only, refused by name before anything is built
 
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.compat.runtime import export_policy_as_jit, get_checkpoint_path

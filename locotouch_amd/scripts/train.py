@@ -5,7 +5,8 @@
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m locotouch_amd.scripts.train --task ... (one rank per GPU)
 
 Flags follow the reference CLI (locotouch/scripts/cli_args.py:11-33, train.py:17-29); `--headless` is accepted and ignored.  `--video`
-records env 0 every --video_interval env steps for --video_length steps (animated PNG, locotouch_amd/video.py) into <log_dir>/videos/train.
+records env 0 every --video_interval env steps for --video_length steps (animated PNG, locotouch_amd/video.py) into <log_dir>/videos/train;
+on a tactile task `--video_tactile` draws the env's tactile groups into the frames (refused by name for a task without one).
 Logs: logs/rsl_rl/<experiment>/<timestamp>/{progress.jsonl, model_<it>.pt, params/{env,agent}.{yaml,pkl}, videos/train/*.apng}.
 """
 from __future__ import annotations
@@ -74,10 +75,11 @@ def main() -> None:
                          "on the GPU inside the fused update (include/lt_ppo_sym.h)")
     ap.add_argument("--mirror_loss_coeff", type=float, default=None, metavar="FLOAT",
                     help="PPO's mirror loss with this coefficient (the symmetry loss is logged as Loss/symmetry either way)")
-    from locotouch_amd.video import add_video_args
+    from locotouch_amd.video import add_video_args, refuse_video_tactile
 
     add_video_args(ap)
     args, _unknown = ap.parse_known_args()  # hydra-style overrides of the reference CLI are tolerated and ignored
+    refuse_video_tactile(args, args.task)  # --video_tactile: tactile tasks only, refused by name before anything is built
 
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.env import make

@@ -235,20 +235,46 @@ class VideoRecorder:
 
 def add_video_args(ap) -> None:
     """--video, --video_length, --video_interval (the reference's CLI, train.py:17-29: defaults 200 and 2000), --video_camera, and
-    --video_resolution WxH.  (`--video` itself is declared by each script.)"""
+    --video_resolution WxH, and --video_tactile (the taxel panel of tactile tasks).  (`--video` itself is declared by each script.)"""
     ap.add_argument("--video_length", type=int, default=200, help="frames (env steps) per recorded video")
     ap.add_argument("--video_interval", type=int, default=2000, help="env steps between the starts of two videos")
     ap.add_argument("--video_camera", choices=("viewer", "follow"), default="follow",
                     help="follow: the chase camera on the robot; viewer: the task's ViewerCfg camera (the reference's default viewpoint)")
     ap.add_argument("--video_resolution", default="640x360", help="WxH of the recorded frames")
+    ap.add_argument("--video_tactile", action="store_true",
+                    help="with --video: draw the tactile observation groups as a panel of taxel grids in the frame's top-right corner "
+                         "(tactile tasks only; include/lt_tactile_panel.h)")
 
 
-def recorder_for(vec, args, video_folder: str, viewer=None) -> VideoRecorder:
+def refuse_video_tactile(args, task, has_tactile: bool | None = None) -> None:
+    """ValueError, naming the flag and the task, when --video_tactile is asked without --video or of a task without a tactile
+    observation group.  `has_tactile` None: looked up in the task's registered preset (host only: the scripts ask before they build
+    an env)."""
+    if not getattr(args, "video_tactile", False):
+        return
+    if hasattr(args, "video") and not args.video:
+        raise ValueError("--video_tactile draws into the frames --video records: give --video as well")
+    if has_tactile is None:
+        from . import _abi
+
+        has_tactile = bool(_abi.preset_cfg(task).tactile_enabled)
+    if not has_tactile:
+        raise ValueError(f"--video_tactile: task {task!r} has no tactile observation group")
+
+
+def recorder_for(vec, args, video_folder: str, viewer=None, tactile_signals=None) -> VideoRecorder:
     """A VideoRecorder of env 0 of the HIP env `vec` from the script arguments (add_video_args), attached as `vec.recorder` so that
-    env.step and the fused rollout feed it; videos go to `video_folder`."""
+    env.step and the fused rollout feed it; videos go to `video_folder`.  With `--video_tactile` every frame gets the taxel panel
+    (vec.draw_tactile_panel, one launch behind the render, into the same buffer) of `tactile_signals()`: a callable that returns the
+    ordered mapping name -> [N, C * 221] tensor for the current step (default: the env's own tactile groups).  Without the flag nothing
+    is drawn and `tactile_signals` is never called."""
     from . import render as R
 
     w, h = R.parse_resolution(args.video_resolution)
+    tactile = bool(getattr(args, "video_tactile", False))
+    if tactile:
+        refuse_video_tactile(args, getattr(vec, "task", None), bool(getattr(vec, "tactile", False)))
+        panel = R.TactilePanel()
     env_index = 0
     cam = R.chase_camera()
     if args.video_camera == "viewer":
@@ -260,6 +286,8 @@ def recorder_for(vec, args, video_folder: str, viewer=None) -> VideoRecorder:
 
     def render_fn():
         bufs.update(vec.render([env_index], cam, width=w, height=h, out=bufs if bufs else None))
+        if tactile:
+            vec.draw_tactile_panel(bufs["rgba"], [env_index], signals=None if tactile_signals is None else tactile_signals(), panel=panel)
         return bufs["rgba"][0]
 
     interval = max(1, int(args.video_interval))
@@ -269,4 +297,4 @@ def recorder_for(vec, args, video_folder: str, viewer=None) -> VideoRecorder:
     return rec
 
 
-__all__ = ["VideoRecorder", "add_video_args", "recorder_for", "apng_bytes", "deflate_frame", "write_apng", "PNG_SIGNATURE"]
+__all__ = ["VideoRecorder", "add_video_args", "recorder_for", "refuse_video_tactile", "apng_bytes", "deflate_frame", "write_apng", "PNG_SIGNATURE"]
