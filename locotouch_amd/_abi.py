@@ -155,6 +155,8 @@ HEADERS = (
      ("lt_policy_encoder_desc", "lt_policy_encoder_params")),  # one inference step of an ActorCriticEncoder / ActorCriticRNNEncoder
     ("TACTILE_PANEL", "lt_tactile_panel.h", False, ("lt_tactile_panel_launches",),
      ("lt_panel_signal", "lt_panel_desc")),  # the taxel panel drawn over rendered frames (--video_tactile)
+    ("TELEMETRY", "lt_telemetry.h", False, ("lt_telemetry_record_launches", "lt_telemetry_chart_launches"),
+     ("lt_telemetry_channel", "lt_chart_plot", "lt_chart_desc")),  # the per-step telemetry ring and its strip charts (--telemetry, --video_telemetry)
 )
 
 

@@ -35,6 +35,7 @@ REWARD_TERM_NAMES = [  # manager order == enum lt_reward_term
     "joint_acceleration", "joint_velocity", "joint_torque", "action_rate", "thigh_calf_collision", "object_xy_position",
     "object_xy_velocity", "object_z_contact", "object_z_velocity", "object_roll_pitch_angle", "object_roll_pitch_velocity",
     "object_yaw_alignment", "object_dangerous_state"]
+LEG_NAMES = ("FR", "FL", "RR", "RL")  # lane order of every per-leg quad array (include/lt_go1_model.h)
 TERMINATION_NAMES = ["time_out", "base_orientation", "base_height_below_minimum", "base_contact", "hip_contact",
                      "object_below_robot", "object_bad_orientation"]
 
@@ -184,6 +185,8 @@ class LocoTouchVecEnv:
         if actions.dtype != torch.float32 or not actions.is_contiguous() or actions.shape != (self.num_envs, 12):
             actions = actions.to(torch.float32).reshape(self.num_envs, 12).contiguous()
         _abi.call("lt_env_step", self._handle, actions, _abi.stream(self.device))
+        if self.telemetry is not None:  # before the recorder: the frame of step t charts the sample of step t
+            self.telemetry.record()
         if self.recorder is not None:
             self.recorder.after_step()
         return self.obs_policy, self.reward_buf, self.dones_buf, self._extras()
@@ -347,6 +350,7 @@ class LocoTouchVecEnv:
 
     # ---- rendering (lt_env_render) -------------------------------------------------------------------
     recorder = None  # a video.VideoRecorder attached by the gymnasium shim's RecordVideo; the fused rollout calls it after each step
+    telemetry = None  # a telemetry.Telemetry: env.step and the fused rollout call its record() behind each step, before the recorder
 
     def render(self, env_ids=None, camera=None, width: int = 320, height: int = 240, depth: bool = False, ids: bool = False, out=None,
                poses: bool = False, flags: int | None = None, light_dir=None) -> dict:
@@ -428,6 +432,77 @@ class LocoTouchVecEnv:
         ids = (ctypes.c_int32 * len(env_ids))(*env_ids)
         with torch.cuda.device(self.device):
             _abi.call("lt_tactile_panel_draw", R.panel_desc(panel, len(sig), x0, y0), sig, ids, len(env_ids), rgba, width, height,
+                      _abi.stream(self.device))
+        return rgba
+
+    def telemetry_channels(self) -> dict:
+        """name -> (view, element offset): the stored scalars a telemetry.Telemetry can record by name.  `view` is an arena view (or
+        the contact-force buffer, env-major) whose first dimension is the env; the value of env e is element e * view.stride(0) +
+        offset behind view.data_ptr().  Quad fields keep the layout's own component order (include/lt_layout.h): joints and forces
+        per link type, then per leg.  Only what the arena stores: nothing derived."""
+        out: dict = {}
+
+        def quad(prefix, field, names):
+            v = self.field(field)
+            for c, name in enumerate(names):
+                out[f"{prefix}.{name}"] = (v, (c // 4) * v.stride(1) + (c % 4) * v.stride(2))
+
+        xyz, wxyz = ("x", "y", "z"), ("w", "x", "y", "z")
+        joints = [f"{leg}_{part}" for part in ("hip", "thigh", "calf") for leg in LEG_NAMES]  # component = link type * 4 + leg
+        quad("root_pos", "LT_F_ROOT_POS", xyz)
+        quad("root_quat", "LT_F_ROOT_QUAT", wxyz)
+        quad("root_lin_vel_w", "LT_F_ROOT_LIN_VEL_W", xyz)
+        quad("root_ang_vel_w", "LT_F_ROOT_ANG_VEL_W", xyz)
+        quad("joint_pos", "LT_F_JOINT_POS", joints)
+        quad("joint_vel", "LT_F_JOINT_VEL", joints)
+        quad("applied_torque", "LT_F_APPLIED_TORQUE", joints)
+        quad("action", "LT_F_ACT_RAW", joints)
+        quad("cmd", "LT_F_CMD", ("vx", "vy", "wz"))
+        fh = self.field("LT_F_FORCE_HIST")  # [slot 3][type 4] quad arrays, newest slot first: the feet of slot 0 are quad 3
+        for leg, name in enumerate(LEG_NAMES):
+            out[f"foot_force.{name}"] = (fh, 3 * fh.stride(1) + leg * fh.stride(2))
+        quad("foot_pos_w", "LT_F_FOOT_POS_W", [f"{leg}_{a}" for a in xyz for leg in LEG_NAMES])
+        quad("obj_pos", "LT_F_OBJ_POS", xyz)
+        quad("obj_quat", "LT_F_OBJ_QUAT", wxyz)
+        quad("obj_lin_vel_w", "LT_F_OBJ_LIN_VEL_W", xyz)
+        out["reward"] = (self.reward_buf, 0)
+        quad("reward_term", "LT_F_REWARD_TERMS", REWARD_TERM_NAMES)  # (written by the step kernel under cfg.debug_terms)
+        out["dones"] = (self.dones_buf, 0)
+        out["time_out"] = (self.time_out_buf, 0)
+        out["term_bits"] = (self.view(C["LT_F_TERM_BITS"]), 0)
+        out["ep_len"] = (self._ep_len, 0)
+        if self._fvec is not None:  # [slot 3][k 14][npad][4]: the newest slot, env-major; k = type * 3 + comp per leg lane, 12 trunk, 13 object
+            f = self._fvec.permute(2, 0, 1, 3)
+            for t, part in enumerate(("hip", "thigh", "calf", "foot")):
+                for comp, a in enumerate(xyz):
+                    for leg, name in enumerate(LEG_NAMES):
+                        out[f"contact_force_w.{name}_{part}_{a}"] = (f, (t * 3 + comp) * f.stride(2) + leg * f.stride(3))
+            for comp, a in enumerate(xyz):
+                out[f"contact_force_w.trunk_{a}"] = (f, 12 * f.stride(2) + comp * f.stride(3))
+                out[f"contact_force_w.object_{a}"] = (f, 13 * f.stride(2) + comp * f.stride(3))
+        return out
+
+    def draw_telemetry_chart(self, rgba: torch.Tensor, env_ids, telemetry, chart=None) -> torch.Tensor:
+        """Draw strip charts of the newest records of `telemetry` (a telemetry.Telemetry) for env `env_ids[v]` over frame v of `rgba`,
+        int32 [V, H, W] packed RGBA8, in place: one launch of lt_telemetry_chart_draw behind whatever wrote the frames (no host sync;
+        include/lt_telemetry.h has the layout and the arithmetic).  `chart`: a render.TelemetryChart (default: render.default_chart of
+        the frame's size).  The counterpart of `draw_tactile_panel`; every env id must be one the telemetry records."""
+        from . import render as R
+
+        if torch.device(self.device).type != "cuda":
+            raise RuntimeError("draw_telemetry_chart needs a HIP device (the chart is drawn by a HIP kernel; there is no CPU path)")
+        if not isinstance(rgba, torch.Tensor) or not rgba.is_cuda or rgba.dtype != torch.int32 or rgba.dim() != 3 or not rgba.is_contiguous():
+            raise TypeError(f"draw_telemetry_chart: rgba must be a contiguous int32 [V, H, W] tensor on {self.device}")
+        env_ids = [int(e) for e in (env_ids.tolist() if hasattr(env_ids, "tolist") else env_ids)]
+        if len(env_ids) != rgba.shape[0]:
+            raise ValueError(f"draw_telemetry_chart: {len(env_ids)} env ids for {rgba.shape[0]} frames")
+        height, width = int(rgba.shape[1]), int(rgba.shape[2])
+        chart = chart or R.default_chart(width, height)
+        x0, y0 = chart.origin(R.chart_size(chart), width, height)
+        slots = (ctypes.c_int32 * max(1, len(env_ids)))(*[telemetry.slot_of(e) for e in env_ids])
+        with torch.cuda.device(self.device):
+            _abi.call("lt_telemetry_chart_draw", R.chart_desc(chart, telemetry.names, x0, y0), telemetry.ring, telemetry.head,
+                      len(telemetry.env_ids), len(telemetry.names), telemetry.capacity, slots, len(env_ids), rgba, width, height,
                       _abi.stream(self.device))
         return rgba
 

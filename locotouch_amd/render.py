@@ -173,6 +173,84 @@ def panel_size(panel: TactilePanel, signals) -> tuple[int, int]:
     return w.value, h.value
 
 
-__all__ = ["Camera", "chase_camera", "from_viewer_cfg", "basis", "ray_directions", "parse_resolution", "rgba_to_rgb", "ORIGIN_WORLD",
+TC = _abi.TELEMETRY_CONSTS
+
+
+@dataclasses.dataclass
+class TelemetryChart:
+    """Strip charts of a telemetry ring drawn over a rendered frame (include/lt_telemetry.h): `plots`, top to bottom, each
+    (channel names - at most four -, (lo, hi)): value `hi` lies on a plot's top row and `lo` on its bottom row; what lies outside is
+    drawn on the edge row.  Every plot is `pw` x `ph` pixels (one column per env step, the newest at the right), `gap` pixels apart;
+    `margin` pixels between the panel and the frame's `corner`; `opacity` 0 ... 255."""
+    plots: tuple = ()
+    pw: int = 240
+    ph: int = 48
+    gap: int = 2
+    corner: str = "bottom-left"
+    margin: int = 8
+    opacity: int = 224
+
+    def origin(self, size: tuple[int, int], width: int, height: int) -> tuple[int, int]:
+        """(x0, y0) of a panel of `size` (chart_size) in a width x height frame."""
+        return TactilePanel(corner=self.corner, margin=self.margin).origin(size, width, height)
+
+    def scale(self, lo: float, hi: float) -> tuple[float, int]:
+        """(k, y_zero) of a plot with the range lo ... hi: k = float32((ph - 1) / (hi - lo)) pixels per unit and y_zero = round(hi * k),
+        the row of value 0.  Formed here, once: the kernel's one float operation is k * v."""
+        if not hi > lo:
+            raise ValueError(f"TelemetryChart: a plot's range must have lo < hi, got ({lo}, {hi})")
+        k = float(np.float32((int(self.ph) - 1) / (float(hi) - float(lo))))
+        return k, int(round(float(hi) * k))
+
+
+# The default chart's ranges (README): the command's covers every task's cfg.cmd_range_max (wz up to pi / 2) without clipping; the
+# foot forces of a recorded play window peaked at 81 N; the reward's is the starting value - it clips while a policy still falls, and
+# was not yet looked at in a video of a trained teacher.
+DEFAULT_CHART_PLOTS = ((("cmd.vx", "cmd.vy", "cmd.wz"), (-1.6, 1.6)),
+                       (("foot_force.FR", "foot_force.FL", "foot_force.RR", "foot_force.RL"), (0.0, 150.0)),
+                       (("reward",), (-0.1, 0.1)))
+
+
+def default_chart(width: int = 640, height: int = 360) -> TelemetryChart:
+    """The chart of --video_telemetry for a width x height frame: the command, the four foot forces and the reward, in the bottom-left
+    corner, 3/8 of the frame wide and 5/12 of it high (240 x 48 pixel plots in a 640 x 360 frame)."""
+    gap = 2
+    pw = max(TC["LT_CHART_MIN_PLOT"], min(TC["LT_CHART_MAX_PLOT_WIDTH"], int(width) * 3 // 8))
+    ph = max(TC["LT_CHART_MIN_PLOT"], min(TC["LT_CHART_MAX_PLOT_HEIGHT"], (int(height) * 5 // 12 - 2 - 2 * gap) // 3))
+    return TelemetryChart(plots=DEFAULT_CHART_PLOTS, pw=pw, ph=ph, gap=gap)
+
+
+def chart_desc(chart: TelemetryChart, names=None, x0: int = 0, y0: int = 0) -> _abi.LtChartDesc:
+    """The lt_chart_desc of `chart`; `names`: the telemetry's channel names, in its order (None: sizes only, no plots are filled in).
+    ValueError for a plot with no or more than four channels, or a channel the telemetry does not record."""
+    d = _abi.LtChartDesc()
+    d.nplots, d.pw, d.ph, d.gap, d.x0, d.y0, d.opacity = len(chart.plots), int(chart.pw), int(chart.ph), int(chart.gap), int(x0), int(y0), int(chart.opacity)
+    if names is None:
+        return d
+    if not 1 <= len(chart.plots) <= TC["LT_CHART_MAX_PLOTS"]:
+        raise ValueError(f"TelemetryChart: 1 ... {TC['LT_CHART_MAX_PLOTS']} plots, got {len(chart.plots)}")
+    names = list(names)
+    for plot, (channels, (lo, hi)) in zip(d.plots, chart.plots):
+        if not 1 <= len(channels) <= TC["LT_CHART_MAX_SERIES"]:
+            raise ValueError(f"TelemetryChart: a plot shows 1 ... {TC['LT_CHART_MAX_SERIES']} channels, got {tuple(channels)}")
+        for s, name in enumerate(channels):
+            if name not in names:
+                raise ValueError(f"TelemetryChart: channel {name!r} is not recorded (recorded: {', '.join(names)})")
+            plot.channels[s] = names.index(name)
+        plot.nseries = len(channels)
+        plot.k, plot.y_zero = chart.scale(lo, hi)
+    return d
+
+
+def chart_size(chart: TelemetryChart) -> tuple[int, int]:
+    """(width, height) in pixels of `chart`'s panel.  lt_telemetry_chart_size: host only, no device is touched."""
+    import ctypes
+
+    w, h = ctypes.c_int(), ctypes.c_int()
+    _abi.call("lt_telemetry_chart_size", chart_desc(chart), ctypes.byref(w), ctypes.byref(h))
+    return w.value, h.value
+
+
+__all__ = ["Camera", "chase_camera", "TelemetryChart", "default_chart", "chart_desc", "chart_size", "DEFAULT_CHART_PLOTS", "from_viewer_cfg", "basis", "ray_directions", "parse_resolution", "rgba_to_rgb", "ORIGIN_WORLD",
            "ORIGIN_ASSET_ROOT", "DEFAULT_FLAGS", "DEPTH_MISS", "TactilePanel", "panel_size", "panel_signals", "panel_desc", "channel_maps",
            "MAP_BINARY", "MAP_RAMP"]

@@ -528,6 +528,8 @@ class FusedRollout:
         else:
             self._step_torch(t, last)
         self.alg.storage.step = t + 1
+        if getattr(self.env, "telemetry", None) is not None:  # telemetry.Telemetry: one record launch on this stream, before the frame that charts it
+            self.env.telemetry.record()
         if self.env.recorder is not None:  # video.VideoRecorder: a render launch on this stream, between two step launches
             self.env.recorder.after_step()
 

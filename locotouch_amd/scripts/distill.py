@@ -10,6 +10,9 @@ up as the reference does: logs/rsl_rl/<teacher experiment>/<--load_run>/<--check
 (animated PNG, locotouch_amd/video.py) into <distill log root>/videos/{train,play}; `--video --video_tactile` draws the tactile signals
 into the frames' top-right corner, top to bottom: `policy` (the delayed rows the student reads), `tactile`, and on the -Play- env
 `original_tactile` and `processed_tactile` (include/lt_tactile_panel.h) - the reference play loop's three ROS topics plus the undelayed signal.
+`--telemetry` (both modes) records chosen scalars of chosen envs behind every env step on the device (locotouch_amd/telemetry.py) and
+writes <distill log root>/telemetry/{train,play}.npz at exit; `--video --video_telemetry` charts env 0's command, foot forces and reward
+in the frames' bottom-left corner.
 """
 from __future__ import annotations
 
@@ -46,11 +49,14 @@ def main() -> None:
     ap.add_argument("--fused_bc_step", action="store_true",
                     help="assemble batches, compute the masked BC loss and step AdamW through the HIP kernels of lt_bc.h (lt_bc_gather, "
                          "lt_bc_loss_forward / _backward, lt_adamw_step)")
-    from locotouch_amd.video import add_video_args, refuse_video_tactile
+    from locotouch_amd.telemetry import add_telemetry_args, save_for, telemetry_for
+    from locotouch_amd.video import add_video_args, refuse_video_tactile, refuse_video_telemetry
 
     add_video_args(ap)
+    add_telemetry_args(ap)
     args, _unknown = ap.parse_known_args()
     refuse_video_tactile(args, args.task)
+    refuse_video_telemetry(args)
 
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.distill import distillation_cfg
@@ -66,18 +72,21 @@ def main() -> None:
     agent = train_cfg(args.task)
     env = make(args.task, num_envs=args.num_envs, device=args.device, seed=args.seed if args.seed is not None else agent["seed"])
     distill_root = os.path.abspath(os.path.join(cfg.log_root_path, cfg.experiment_name))
+    mode = "train" if args.training else "play"
+    telemetry = telemetry_for(env, args)  # None without --telemetry / --video_telemetry: nothing is launched then
     recorder = None
     delay_line: dict = {}  # "recorder": the Distillation's tactile recorder, once there is one (_run)
     if args.video:
         from locotouch_amd.video import recorder_for
 
-        recorder = recorder_for(env, args, os.path.join(distill_root, "videos", "train" if args.training else "play"),
-                                tactile_signals=panel_signals_of(env, delay_line) if args.video_tactile else None)
+        recorder = recorder_for(env, args, os.path.join(distill_root, "videos", mode),
+                                tactile_signals=panel_signals_of(env, delay_line) if args.video_tactile else None, telemetry=telemetry)
     try:
         _run(args, cfg, agent, env, distill_root, delay_line)
     finally:
         if recorder is not None:
             recorder.close()
+        save_for(telemetry, args, distill_root, mode)
 
 
 def panel_signals_of(env, delay_line: dict):
@@ -119,8 +128,8 @@ def _run(args, cfg, agent, env, distill_root, delay_line: dict | None = None) ->
             delay_line["recorder"] = d.tactile_recorder
         d.train()
     else:
-        # (`--video` keeps its recordings in <distill root>/videos, beside the runs: that folder is no run)
-        ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or r"(?!videos$).*", args.checkpoint_distill or "model_.*.pt")
+        # (`--video` and `--telemetry` keep their files in <distill root>/videos and /telemetry, beside the runs: those folders are no runs)
+        ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or r"(?!(videos|telemetry)$).*", args.checkpoint_distill or "model_.*.pt")
         d = Distillation(env, cfg, training=False, checkpoint=ckpt, fused_student_inference=args.fused_student, fused_collection=args.fused_collect,
                          device_ledger=args.device_ledger)
         if delay_line is not None:

@@ -4,7 +4,9 @@ episode statistics, optionally exports the actor (with its memory, for a recurre
 with `--fused_policy` serves a recurrent or an encoder policy from its fused HIP inference step (include/lt_policy.h,
 include/lt_policy_encoder.h), and with `--video` records env 0 (animated
 PNG, locotouch_amd/video.py) into <run>/videos/play (`--video_tactile`: with the env's tactile groups drawn into the frames, on a tactile
-task; refused by name for a task without one).  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
+task; refused by name for a task without one; `--video_telemetry`: with strip charts of env 0's command, foot forces and reward).
+`--telemetry` records chosen scalars of chosen envs behind every step on the device (locotouch_amd/telemetry.py; `--telemetry_envs`,
+`--telemetry_channels`) and writes <run>/telemetry/play.npz at exit.  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
 `policy` and `empirical_normalization` entries take the place of the registered agent cfg's, so a recurrent checkpoint loads.
 
     python -m locotouch_amd.scripts.play --task Isaac-RandCylinderTransportTeacher-LocoTouch-Play-v1 --num_envs 50 --steps 1000 --export
@@ -32,11 +34,14 @@ def main() -> None:
     ap.add_argument("--fused_policy", action="store_true",
                     help="ActorCriticRecurrent, ActorCriticEncoder and ActorCriticRNNEncoder policies: step through the fused HIP inference "
                          "step (rl/fused_policy.py) and reset the memory of finished envs")
-    from locotouch_amd.video import add_video_args, refuse_video_tactile
+    from locotouch_amd.telemetry import add_telemetry_args, save_for, telemetry_for
+    from locotouch_amd.video import add_video_args, refuse_video_tactile, refuse_video_telemetry
 
     add_video_args(ap)
+    add_telemetry_args(ap)
     args, _unknown = ap.parse_known_args()
     refuse_video_tactile(args, args.task)  # --video_tactile: tactile tasks only, refused by name before anything is built
+    refuse_video_telemetry(args)  # --video_telemetry without --video
 
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.compat.runtime import export_policy_as_jit, get_checkpoint_path
@@ -68,11 +73,12 @@ def main() -> None:
         out = export_policy_as_jit(runner.alg.actor_critic, runner.obs_normalizer if runner.empirical_normalization else None,
                                    path=os.path.join(os.path.dirname(resume), "exported"), filename="policy.pt")
         print(f"[INFO]: Exported policy to: {out}")
+    telemetry = telemetry_for(env, args)  # None without --telemetry / --video_telemetry: nothing is launched then
     recorder = None
     if args.video:
         from locotouch_amd.video import recorder_for
 
-        recorder = recorder_for(env, args, os.path.join(os.path.dirname(resume), "videos", "play"))
+        recorder = recorder_for(env, args, os.path.join(os.path.dirname(resume), "videos", "play"), telemetry=telemetry)
     obs, _ = env.get_observations()
     t, finished, ret_sum = 0, 0, torch.zeros(env.num_envs, device=env.device)
     try:
@@ -89,6 +95,7 @@ def main() -> None:
     finally:
         if recorder is not None:
             recorder.close()
+        save_for(telemetry, args, os.path.dirname(resume), "play")
 
 
 if __name__ == "__main__":

@@ -6,7 +6,10 @@
 
 Flags follow the reference CLI (locotouch/scripts/cli_args.py:11-33, train.py:17-29); `--headless` is accepted and ignored.  `--video`
 records env 0 every --video_interval env steps for --video_length steps (animated PNG, locotouch_amd/video.py) into <log_dir>/videos/train;
-on a tactile task `--video_tactile` draws the env's tactile groups into the frames (refused by name for a task without one).
+on a tactile task `--video_tactile` draws the env's tactile groups into the frames (refused by name for a task without one), and
+`--video_telemetry` strip charts of env 0's command, foot forces and reward.  `--telemetry` records chosen scalars of chosen envs
+behind every env step on the device (locotouch_amd/telemetry.py) and writes <log_dir>/telemetry/train.npz at the end (the newest
+--telemetry_capacity steps).
 Logs: logs/rsl_rl/<experiment>/<timestamp>/{progress.jsonl, model_<it>.pt, params/{env,agent}.{yaml,pkl}, videos/train/*.apng}.
 """
 from __future__ import annotations
@@ -75,11 +78,14 @@ def main() -> None:
                          "on the GPU inside the fused update (include/lt_ppo_sym.h)")
     ap.add_argument("--mirror_loss_coeff", type=float, default=None, metavar="FLOAT",
                     help="PPO's mirror loss with this coefficient (the symmetry loss is logged as Loss/symmetry either way)")
-    from locotouch_amd.video import add_video_args, refuse_video_tactile
+    from locotouch_amd.telemetry import add_telemetry_args, save_for, telemetry_for
+    from locotouch_amd.video import add_video_args, refuse_video_tactile, refuse_video_telemetry
 
     add_video_args(ap)
+    add_telemetry_args(ap)
     args, _unknown = ap.parse_known_args()  # hydra-style overrides of the reference CLI are tolerated and ignored
     refuse_video_tactile(args, args.task)  # --video_tactile: tactile tasks only, refused by name before anything is built
+    refuse_video_telemetry(args)  # --video_telemetry without --video
 
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.env import make
@@ -122,10 +128,11 @@ def main() -> None:
     log_dir = os.path.join(args.log_root, cfg["experiment_name"], datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S"))
     runner = OnPolicyRunner(env, cfg, log_dir=log_dir, device=device, dist=dist)
     recorder = None
-    if args.video and dist.is_main:  # only the main rank records
+    telemetry = telemetry_for(env, args) if dist.is_main else None  # only the main rank records; None without the flags
+    if args.video and dist.is_main:
         from locotouch_amd.video import recorder_for
 
-        recorder = recorder_for(env, args, os.path.join(log_dir, "videos", "train"))
+        recorder = recorder_for(env, args, os.path.join(log_dir, "videos", "train"), telemetry=telemetry)
     if args.resume:  # train.py:131-137 of the reference: newest matching run / checkpoint under the experiment's log root
         from locotouch_amd.compat.runtime import get_checkpoint_path
 
@@ -141,6 +148,7 @@ def main() -> None:
         print({k: last[k] for k in ("iter", "Perf/total_fps", "Loss/value_function", "Loss/surrogate", "Loss/learning_rate")})
     if recorder is not None:
         recorder.close()
+    save_for(telemetry, args, log_dir, "train")
     dist.shutdown()
 
 

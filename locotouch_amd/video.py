@@ -235,7 +235,8 @@ class VideoRecorder:
 
 def add_video_args(ap) -> None:
     """--video, --video_length, --video_interval (the reference's CLI, train.py:17-29: defaults 200 and 2000), --video_camera, and
-    --video_resolution WxH, and --video_tactile (the taxel panel of tactile tasks).  (`--video` itself is declared by each script.)"""
+    --video_resolution WxH, --video_tactile (the taxel panel of tactile tasks) and --video_telemetry (strip charts of the telemetry
+    ring).  (`--video` itself is declared by each script.)"""
     ap.add_argument("--video_length", type=int, default=200, help="frames (env steps) per recorded video")
     ap.add_argument("--video_interval", type=int, default=2000, help="env steps between the starts of two videos")
     ap.add_argument("--video_camera", choices=("viewer", "follow"), default="follow",
@@ -244,6 +245,9 @@ def add_video_args(ap) -> None:
     ap.add_argument("--video_tactile", action="store_true",
                     help="with --video: draw the tactile observation groups as a panel of taxel grids in the frame's top-right corner "
                          "(tactile tasks only; include/lt_tactile_panel.h)")
+    ap.add_argument("--video_telemetry", action="store_true",
+                    help="with --video: draw strip charts of the recorded env's telemetry (command, foot forces, reward) in the frame's "
+                         "bottom-left corner (include/lt_telemetry.h)")
 
 
 def refuse_video_tactile(args, task, has_tactile: bool | None = None) -> None:
@@ -262,15 +266,31 @@ def refuse_video_tactile(args, task, has_tactile: bool | None = None) -> None:
         raise ValueError(f"--video_tactile: task {task!r} has no tactile observation group")
 
 
-def recorder_for(vec, args, video_folder: str, viewer=None, tactile_signals=None) -> VideoRecorder:
+def refuse_video_telemetry(args) -> None:
+    """ValueError, naming the flag, when --video_telemetry is asked without --video."""
+    if getattr(args, "video_telemetry", False) and hasattr(args, "video") and not args.video:
+        raise ValueError("--video_telemetry draws into the frames --video records: give --video as well")
+
+
+def recorder_for(vec, args, video_folder: str, viewer=None, tactile_signals=None, telemetry=None, telemetry_chart=None) -> VideoRecorder:
     """A VideoRecorder of env 0 of the HIP env `vec` from the script arguments (add_video_args), attached as `vec.recorder` so that
     env.step and the fused rollout feed it; videos go to `video_folder`.  With `--video_tactile` every frame gets the taxel panel
     (vec.draw_tactile_panel, one launch behind the render, into the same buffer) of `tactile_signals()`: a callable that returns the
     ordered mapping name -> [N, C * 221] tensor for the current step (default: the env's own tactile groups).  Without the flag nothing
-    is drawn and `tactile_signals` is never called."""
+    is drawn and `tactile_signals` is never called.  With `--video_telemetry` every frame gets strip charts of the newest records of
+    `telemetry` (a telemetry.Telemetry that records the filmed env; vec.draw_telemetry_chart, one launch behind the render and behind
+    the taxel panel's, into the same buffer) in the bottom-left corner: `telemetry_chart` (a render.TelemetryChart; default:
+    render.default_chart of the resolution).  Without that flag `telemetry` is not looked at."""
     from . import render as R
 
     w, h = R.parse_resolution(args.video_resolution)
+    charted = bool(getattr(args, "video_telemetry", False))
+    if charted:
+        refuse_video_telemetry(args)
+        if telemetry is None:
+            raise ValueError("--video_telemetry: recorder_for needs the telemetry.Telemetry whose ring it charts (telemetry=...)")
+        chart = telemetry_chart or R.default_chart(w, h)
+        R.chart_desc(chart, telemetry.names)  # a channel the telemetry does not record is refused here, by name, not at the first frame
     tactile = bool(getattr(args, "video_tactile", False))
     if tactile:
         refuse_video_tactile(args, getattr(vec, "task", None), bool(getattr(vec, "tactile", False)))
@@ -282,12 +302,16 @@ def recorder_for(vec, args, video_folder: str, viewer=None, tactile_signals=None
             cam = R.Camera(eye=(5.0, 5.0, 4.0), lookat=(-2.0, -2.0, 0.0), origin=R.ORIGIN_WORLD)  # the reference's ViewerCfg
         else:
             cam, env_index, _ = R.from_viewer_cfg(viewer)
+    if charted:
+        telemetry.slot_of(env_index)  # ValueError, naming the env, if the telemetry does not record the filmed one
     bufs: dict = {}
 
     def render_fn():
         bufs.update(vec.render([env_index], cam, width=w, height=h, out=bufs if bufs else None))
         if tactile:
             vec.draw_tactile_panel(bufs["rgba"], [env_index], signals=None if tactile_signals is None else tactile_signals(), panel=panel)
+        if charted:
+            vec.draw_telemetry_chart(bufs["rgba"], [env_index], telemetry, chart)
         return bufs["rgba"][0]
 
     interval = max(1, int(args.video_interval))
@@ -297,4 +321,4 @@ def recorder_for(vec, args, video_folder: str, viewer=None, tactile_signals=None
     return rec
 
 
-__all__ = ["VideoRecorder", "add_video_args", "recorder_for", "refuse_video_tactile", "apng_bytes", "deflate_frame", "write_apng", "PNG_SIGNATURE"]
+__all__ = ["VideoRecorder", "add_video_args", "recorder_for", "refuse_video_tactile", "refuse_video_telemetry", "apng_bytes", "deflate_frame", "write_apng", "PNG_SIGNATURE"]
