@@ -157,6 +157,8 @@ HEADERS = (
      ("lt_panel_signal", "lt_panel_desc")),  # the taxel panel drawn over rendered frames (--video_tactile)
     ("TELEMETRY", "lt_telemetry.h", False, ("lt_telemetry_record_launches", "lt_telemetry_chart_launches"),
      ("lt_telemetry_channel", "lt_chart_plot", "lt_chart_desc")),  # the per-step telemetry ring and its strip charts (--telemetry, --video_telemetry)
+    ("EPISODE_STATS", "lt_episode_stats.h", "lt_telemetry.h", ("lt_episode_stats_step_launches", "lt_episode_stats_reduce_launches"),
+     ("lt_episode_stats_pair", "lt_episode_stats_metric")),  # statistics over the finished episodes of all envs (--episode_stats)
 )
 
 

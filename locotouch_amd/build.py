@@ -34,6 +34,11 @@ def deps() -> list[str]:
                               + glob.glob(os.path.join(REPO, "include", "*.h")))
 
 
+# Sources whose arithmetic is stated operation by operation and held to a numpy twin bit for bit: behind the common flags they get these,
+# which take the relaxed-math switches back (no FMA contraction, NaN and signed zeros as IEEE has them, true division and square root).
+PRECISE_FLAGS = ["-ffp-contract=off", "-fno-finite-math-only", "-fsigned-zeros", "-fno-reciprocal-math"]
+PRECISE_SOURCES = ("lt_episode_stats.hip",)
+
 STEP_KERNEL_SOURCES = ("lt_env.hip", "lt_physics_crba.h", "lt_post.h", "lt_device_math.h", "lt_device_prims.h")
 
 
@@ -82,7 +87,8 @@ def build_lib(force: bool = False, verbose: bool = False, extra_flags: list[str]
         o = os.path.join(obj_dir, os.path.basename(s) + ".o")
         # NOTE: one translation unit per hipcc call - mixing `-x hip` and `-x c++` inputs in one command makes
         # the hipcc wrapper drop --offload-arch and emit gfx906 device code.
-        cmd = [hipcc(), f"--offload-arch={ARCH}"] + common + ["-c", s, "-o", o]
+        precise = PRECISE_FLAGS if os.path.basename(s) in PRECISE_SOURCES else []
+        cmd = [hipcc(), f"--offload-arch={ARCH}"] + common + precise + ["-c", s, "-o", o]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)

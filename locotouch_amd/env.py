@@ -159,6 +159,8 @@ class LocoTouchVecEnv:
 
     def reset(self):
         _abi.call("lt_env_reset_all", self._handle, _abi.stream(self.device))
+        if self.episode_stats is not None:  # no `dones` tells it: the episodes cut off here are dropped, not merged into the next ones
+            self.episode_stats.restart_running()
         return self.get_observations()
 
     def _extras(self) -> dict:
@@ -187,6 +189,8 @@ class LocoTouchVecEnv:
         _abi.call("lt_env_step", self._handle, actions, _abi.stream(self.device))
         if self.telemetry is not None:  # before the recorder: the frame of step t charts the sample of step t
             self.telemetry.record()
+        if self.episode_stats is not None:  # one launch over all envs, beside the telemetry record
+            self.episode_stats.step()
         if self.recorder is not None:
             self.recorder.after_step()
         return self.obs_policy, self.reward_buf, self.dones_buf, self._extras()
@@ -351,6 +355,7 @@ class LocoTouchVecEnv:
     # ---- rendering (lt_env_render) -------------------------------------------------------------------
     recorder = None  # a video.VideoRecorder attached by the gymnasium shim's RecordVideo; the fused rollout calls it after each step
     telemetry = None  # a telemetry.Telemetry: env.step and the fused rollout call its record() behind each step, before the recorder
+    episode_stats = None  # an episode_stats.EpisodeStats: env.step and the fused rollout call its step() behind each step, beside the telemetry
 
     def render(self, env_ids=None, camera=None, width: int = 320, height: int = 240, depth: bool = False, ids: bool = False, out=None,
                poses: bool = False, flags: int | None = None, light_dir=None) -> dict:
@@ -480,6 +485,16 @@ class LocoTouchVecEnv:
             for comp, a in enumerate(xyz):
                 out[f"contact_force_w.trunk_{a}"] = (f, 12 * f.stride(2) + comp * f.stride(3))
                 out[f"contact_force_w.object_{a}"] = (f, 13 * f.stride(2) + comp * f.stride(3))
+        return out
+
+    def episode_stats_channels(self) -> dict:
+        """`telemetry_channels()` plus `cmd_metric.{error_vel_xy, error_vel_yaw, foot_air_time_variance}`: the snapshot the step kernel
+        takes in an env's reset path (LT_F_LAST_CMD_METRICS).  It is written at the done step from the values the finished episode's
+        last command update left, so an episode_stats metric reads it there, with `reduce="last"`."""
+        out = self.telemetry_channels()
+        last = self.field("LT_F_LAST_CMD_METRICS")
+        for lane, name in enumerate(("error_vel_xy", "error_vel_yaw", "foot_air_time_variance")):
+            out[f"cmd_metric.{name}"] = (last, lane * last.stride(2))
         return out
 
     def draw_telemetry_chart(self, rgba: torch.Tensor, env_ids, telemetry, chart=None) -> torch.Tensor:

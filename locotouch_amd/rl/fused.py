@@ -530,6 +530,8 @@ class FusedRollout:
         self.alg.storage.step = t + 1
         if getattr(self.env, "telemetry", None) is not None:  # telemetry.Telemetry: one record launch on this stream, before the frame that charts it
             self.env.telemetry.record()
+        if getattr(self.env, "episode_stats", None) is not None:  # episode_stats.EpisodeStats: one launch over all envs on this stream
+            self.env.episode_stats.step()
         if self.env.recorder is not None:  # video.VideoRecorder: a render launch on this stream, between two step launches
             self.env.recorder.after_step()
 

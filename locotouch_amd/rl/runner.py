@@ -162,6 +162,8 @@ class OnPolicyRunner:
                 if fused is not None:  # the env's own per-episode accumulators stand in for rewbuffer / lenbuffer
                     rec["Train/mean_reward"] = rec.get("Episode/reward")
                     rec["Train/mean_episode_length"] = rec.get("Episode/length")
+            if getattr(env, "episode_stats", None) is not None:  # --episode_stats: the iteration's finished episodes, then cleared
+                rec.update(env.episode_stats.eval_record(clear=True))
             self.history.append(rec)
             if self.log_dir is not None:
                 os.makedirs(self.log_dir, exist_ok=True)

@@ -12,7 +12,8 @@ into the frames' top-right corner, top to bottom: `policy` (the delayed rows the
 `original_tactile` and `processed_tactile` (include/lt_tactile_panel.h) - the reference play loop's three ROS topics plus the undelayed signal.
 `--telemetry` (both modes) records chosen scalars of chosen envs behind every env step on the device (locotouch_amd/telemetry.py) and
 writes <distill log root>/telemetry/{train,play}.npz at exit; `--video --video_telemetry` charts env 0's command, foot forces and reward
-in the frames' bottom-left corner.
+in the frames' bottom-left corner.  `--episode_stats` (both modes) keeps statistics over the finished episodes of all envs on the device
+(locotouch_amd/episode_stats.py), prints their table and writes <distill log root>/episode_stats/{train,play}.json at exit.
 """
 from __future__ import annotations
 
@@ -49,12 +50,15 @@ def main() -> None:
     ap.add_argument("--fused_bc_step", action="store_true",
                     help="assemble batches, compute the masked BC loss and step AdamW through the HIP kernels of lt_bc.h (lt_bc_gather, "
                          "lt_bc_loss_forward / _backward, lt_adamw_step)")
+    from locotouch_amd.episode_stats import add_episode_stats_args, episode_stats_for, refuse_episode_stats_metrics, report_for
     from locotouch_amd.telemetry import add_telemetry_args, save_for, telemetry_for
     from locotouch_amd.video import add_video_args, refuse_video_tactile, refuse_video_telemetry
 
     add_video_args(ap)
     add_telemetry_args(ap)
+    add_episode_stats_args(ap)
     args, _unknown = ap.parse_known_args()
+    refuse_episode_stats_metrics(args)
     refuse_video_tactile(args, args.task)
     refuse_video_telemetry(args)
 
@@ -74,6 +78,7 @@ def main() -> None:
     distill_root = os.path.abspath(os.path.join(cfg.log_root_path, cfg.experiment_name))
     mode = "train" if args.training else "play"
     telemetry = telemetry_for(env, args)  # None without --telemetry / --video_telemetry: nothing is launched then
+    stats = episode_stats_for(env, args, skip_running=args.training)  # play: the env was reset just now; None without --episode_stats
     recorder = None
     delay_line: dict = {}  # "recorder": the Distillation's tactile recorder, once there is one (_run)
     if args.video:
@@ -87,6 +92,7 @@ def main() -> None:
         if recorder is not None:
             recorder.close()
         save_for(telemetry, args, distill_root, mode)
+        report_for(stats, distill_root, mode)
 
 
 def panel_signals_of(env, delay_line: dict):
@@ -128,8 +134,9 @@ def _run(args, cfg, agent, env, distill_root, delay_line: dict | None = None) ->
             delay_line["recorder"] = d.tactile_recorder
         d.train()
     else:
-        # (`--video` and `--telemetry` keep their files in <distill root>/videos and /telemetry, beside the runs: those folders are no runs)
-        ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or r"(?!(videos|telemetry)$).*", args.checkpoint_distill or "model_.*.pt")
+        # (`--video`, `--telemetry` and `--episode_stats` keep their files in <distill root>/videos, /telemetry and /episode_stats, beside the runs:
+        # those folders are no runs)
+        ckpt = get_checkpoint_path(distill_root, args.log_dir_distill or r"(?!(videos|telemetry|episode_stats)$).*", args.checkpoint_distill or "model_.*.pt")
         d = Distillation(env, cfg, training=False, checkpoint=ckpt, fused_student_inference=args.fused_student, fused_collection=args.fused_collect,
                          device_ledger=args.device_ledger)
         if delay_line is not None:

@@ -6,7 +6,9 @@ include/lt_policy_encoder.h), and with `--video` records env 0 (animated
 PNG, locotouch_amd/video.py) into <run>/videos/play (`--video_tactile`: with the env's tactile groups drawn into the frames, on a tactile
 task; refused by name for a task without one; `--video_telemetry`: with strip charts of env 0's command, foot forces and reward).
 `--telemetry` records chosen scalars of chosen envs behind every step on the device (locotouch_amd/telemetry.py; `--telemetry_envs`,
-`--telemetry_channels`) and writes <run>/telemetry/play.npz at exit.  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
+`--telemetry_channels`) and writes <run>/telemetry/play.npz at exit.  `--episode_stats` keeps statistics over the finished episodes of
+all envs on the device (locotouch_amd/episode_stats.py; `--episode_stats_metrics`), prints their table and writes
+<run>/episode_stats/play.json at exit.  Where the run directory holds `params/agent.yaml` (scripts/train.py writes it), its
 `policy` and `empirical_normalization` entries take the place of the registered agent cfg's, so a recurrent checkpoint loads.
 
     python -m locotouch_amd.scripts.play --task Isaac-RandCylinderTransportTeacher-LocoTouch-Play-v1 --num_envs 50 --steps 1000 --export
@@ -34,12 +36,15 @@ def main() -> None:
     ap.add_argument("--fused_policy", action="store_true",
                     help="ActorCriticRecurrent, ActorCriticEncoder and ActorCriticRNNEncoder policies: step through the fused HIP inference "
                          "step (rl/fused_policy.py) and reset the memory of finished envs")
+    from locotouch_amd.episode_stats import add_episode_stats_args, episode_stats_for, refuse_episode_stats_metrics, report_for
     from locotouch_amd.telemetry import add_telemetry_args, save_for, telemetry_for
     from locotouch_amd.video import add_video_args, refuse_video_tactile, refuse_video_telemetry
 
     add_video_args(ap)
     add_telemetry_args(ap)
+    add_episode_stats_args(ap)
     args, _unknown = ap.parse_known_args()
+    refuse_episode_stats_metrics(args)  # an unknown metric name: refused by name before anything is built
     refuse_video_tactile(args, args.task)  # --video_tactile: tactile tasks only, refused by name before anything is built
     refuse_video_telemetry(args)  # --video_telemetry without --video
 
@@ -74,6 +79,7 @@ def main() -> None:
                                    path=os.path.join(os.path.dirname(resume), "exported"), filename="policy.pt")
         print(f"[INFO]: Exported policy to: {out}")
     telemetry = telemetry_for(env, args)  # None without --telemetry / --video_telemetry: nothing is launched then
+    stats = episode_stats_for(env, args, skip_running=False)  # (the env was reset just now: no episode is running); None without the flag
     recorder = None
     if args.video:
         from locotouch_amd.video import recorder_for
@@ -96,6 +102,7 @@ def main() -> None:
         if recorder is not None:
             recorder.close()
         save_for(telemetry, args, os.path.dirname(resume), "play")
+        report_for(stats, os.path.dirname(resume), "play")
 
 
 if __name__ == "__main__":

@@ -9,7 +9,8 @@ records env 0 every --video_interval env steps for --video_length steps (animate
 on a tactile task `--video_tactile` draws the env's tactile groups into the frames (refused by name for a task without one), and
 `--video_telemetry` strip charts of env 0's command, foot forces and reward.  `--telemetry` records chosen scalars of chosen envs
 behind every env step on the device (locotouch_amd/telemetry.py) and writes <log_dir>/telemetry/train.npz at the end (the newest
---telemetry_capacity steps).
+--telemetry_capacity steps).  `--episode_stats` keeps statistics over the finished episodes of all envs on the device
+(locotouch_amd/episode_stats.py) and adds `Eval/<metric>/mean` and `Eval/termination/<name>` to every iteration's record.
 Logs: logs/rsl_rl/<experiment>/<timestamp>/{progress.jsonl, model_<it>.pt, params/{env,agent}.{yaml,pkl}, videos/train/*.apng}.
 """
 from __future__ import annotations
@@ -78,14 +79,17 @@ def main() -> None:
                          "on the GPU inside the fused update (include/lt_ppo_sym.h)")
     ap.add_argument("--mirror_loss_coeff", type=float, default=None, metavar="FLOAT",
                     help="PPO's mirror loss with this coefficient (the symmetry loss is logged as Loss/symmetry either way)")
+    from locotouch_amd.episode_stats import add_episode_stats_args, episode_stats_for, refuse_episode_stats_metrics
     from locotouch_amd.telemetry import add_telemetry_args, save_for, telemetry_for
     from locotouch_amd.video import add_video_args, refuse_video_tactile, refuse_video_telemetry
 
     add_video_args(ap)
+    add_episode_stats_args(ap)
     add_telemetry_args(ap)
     args, _unknown = ap.parse_known_args()  # hydra-style overrides of the reference CLI are tolerated and ignored
     refuse_video_tactile(args, args.task)  # --video_tactile: tactile tasks only, refused by name before anything is built
     refuse_video_telemetry(args)  # --video_telemetry without --video
+    refuse_episode_stats_metrics(args)  # an unknown metric name: refused by name before anything is built
 
     from locotouch_amd.agents import train_cfg
     from locotouch_amd.env import make
@@ -129,6 +133,7 @@ def main() -> None:
     runner = OnPolicyRunner(env, cfg, log_dir=log_dir, device=device, dist=dist)
     recorder = None
     telemetry = telemetry_for(env, args) if dist.is_main else None  # only the main rank records; None without the flags
+    episode_stats_for(env, args)  # every rank keeps its own envs' statistics (the runner logs them); nothing without --episode_stats
     if args.video and dist.is_main:
         from locotouch_amd.video import recorder_for
 
